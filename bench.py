@@ -10,16 +10,27 @@ then the per-pair Schur solve and SE(3) (+) log-depth update) of EVERY frame pai
 level 0 (full resolution, the heaviest level).  Each rank holds --pairs independent pairs (weak scaling: frame
 pairs shard embarrassingly, there is no data-path collective; the only exchange is the final gather of poses and
 log-depths, done once after the timed region).  `value` = pair-iterations per second over all ranks with every
-input already resident in HBM.
+input already resident in HBM; `ms_per_step` = the wall time of one of the exactly --steps timed steps.
+
+A plain run sets up, settles the clocks, starts again from the initial values, runs --warmup steps, times --steps
+steps and prints the line.  --dump-outputs DIR then writes what the last timed step left a caller of gn_step /
+adam_step: poses.npy (pairs x 4 x 4), log_depths.npy (every pair's segment log-depths, concatenated) and costs.npy (the
+returned per-pair costs, at the parameters before that step), float32, rank 0, over all ranks.  The inputs are seeded,
+so the same arguments give the same inputs on any build.
+
+    python bench.py --gpus 1 --steps 200 --warmup 100 --full
+
+also runs every side measurement below (and, under torch.distributed.run, the whole-job frame-pair legs).
 
 Extra objects on the JSON line:
   roofline      HBM roofline of the dominant kernel (k_cost_pairs<GN>): algorithmic bytes per launch
                 (20 B/segment pixel + 12 B/target pixel) / its mean duration measured with HIP events
-                on the launch stream inside the timed region; peak 8000 GB/s (MI355X_MICROARCH.md).
-  cpu_baseline  the oracle's dense PyTorch-CPU restatement of the reference loop (cost + backward + Adam.step) on
+                on the launch stream inside the timed region; peak 8000 GB/s (MI355X_MICROARCH.md).  --full adds the
+                HBM traffic and the VALU ceiling of that kernel, measured by child runs under rocprofv3.
+  cpu_baseline  (--full) the oracle's dense PyTorch-CPU restatement of the reference loop (cost + backward + Adam.step) on
                 the host cores of this box, rank 0 / N=1 only, on a bounded sample (configs 1 and 2,
                 3 warm-up iterations, median and p10/p90 of 10, all threads and one thread).  Baseline only.
-  frame_pairs_per_sec  whole coarse-to-fine schedules per second, on the schedule that tests/test_gpu_fullsize.py
+  frame_pairs_per_sec  (--full) whole coarse-to-fine schedules per second, on the schedule that tests/test_gpu_fullsize.py
                 requires to land within 1e-4 rad / 1e-4 t / 1e-3 depth of the reference's minimiser
                 (optim.pair_batch.FRAME_PAIR_SCHEDULE), started from the initial values; the in-run deviation from the
                 synthetic ground truth is reported next to it.
@@ -90,10 +101,17 @@ def parse(argv=None):
     ap.add_argument("--settle-ms", type=float, default=150.0,
                     help="untimed steps run for this long before the W warm-up steps, so the clocks of a box that was idle "
                          "have ramped to their steady state (DESIGN.md §6); 0 disables")
-    ap.add_argument("--min-timed-ms", type=float, default=200.0,
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
                     help="the timed region of exactly --steps steps (barrier + synchronize on both sides) is REPEATED, each repetition bracketed "
                          "the same way, until this much time has been timed in total; the line reports the mean over the repetitions "
-                         "(20 steps are 17 ms: one region alone moves with the clock state of the box); 0 = one region")
+                         "(20 steps are 17 ms: one region alone moves with the clock state of the box); 0 (the default) = one region, "
+                         "so that --steps is the number of timed steps; 200 = the method of the round-1 to round-6 records under profiles/")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: PMC passes, the one-GPU side legs (single pair, schedules, set-up, batching, "
+                         "reference start, chain), the whole-job legs of an N > 1 run and the CPU baseline; without it the run does only "
+                         "what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (poses, log-depths, costs) as DIR/<name>.npy, float32")
     ap.add_argument("--pairs", type=int, default=384, help="frame pairs resident per GPU (4.8 GB of tables and images)")
     ap.add_argument("--segments", type=int, default=64, help="segments per source keyframe (BASELINE config 5 uses 128)")
     ap.add_argument("--shape", choices=["grid", "blobs", "sam"], default="grid",
@@ -109,14 +127,14 @@ def parse(argv=None):
     ap.add_argument("--tile-points", type=int, default=8192, help="longest chunk (piece of one segment)")
     ap.add_argument("--span-points", type=int, default=None, help="points per workgroup (run of consecutive chunks); default: PairBatch's")
     ap.add_argument("--mode", choices=["gn", "adam"], default="gn")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-iters", type=int, default=10, help="timed CPU-baseline iterations per leg (after 3 warm-up)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-pair and full-schedule side measurements")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the single-pair and full-schedule side measurements")
     ap.add_argument("--sigma05-scenes", type=int, default=8,
                     help="distinct multi-octave scenes rendered for the reference-start leg (every resident pair gets its own "
                          "T_gt Exp(0.05 xi) start and its own depth seeds); 0 skips the leg")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not measure the HBM traffic of the dominant kernel in this run (by default, on one GPU, bench.py re-runs 10 "
+                    help="do not measure the HBM traffic of the dominant kernel in this run (with --full, on one GPU, bench.py re-runs 10 "
                          "steps of itself under `rocprofv3 --kernel-trace --pmc FETCH_SIZE` and `... --pmc WRITE_SIZE`, one counter per "
                          "pass as MI355X_MICROARCH.md prescribes, when rocprofv3 is on PATH)")
     ap.add_argument("--dry-run", action="store_true",
@@ -515,6 +533,24 @@ def sample_shader_clock(step, seconds=1.6):
     return float(np.mean(got)) if got else None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  Beyond DUMP_LIMIT_BYTES in all, every array is cut to the same
+    fixed, seeded sample of its elements (in order), so that two builds run with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = 0.9 * DUMP_LIMIT_BYTES / total
+        for k, a in arrays.items():
+            idx = np.random.default_rng(0).choice(a.size, max(1, int(keep * a.size)), replace=False)
+            arrays[k] = a.reshape(-1)[np.sort(idx)]
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 class _HostEvent:
     """Stand-in for torch.cuda.Event in --dry-run."""
 
@@ -568,6 +604,9 @@ def main(argv=None):
             for _ in range(8):
                 step()
             sync()
+        # (the settle runs as many steps as fit in its time: the counted steps start from the initial values again, so that what the
+        #  last timed step computes depends on the arguments alone)
+        batch.restore_initial()
     for _ in range(args.warmup):
         step()
     K = args.steps
@@ -626,7 +665,15 @@ def main(argv=None):
         klds_all = [torch.empty_like(batch.kld) for _ in range(world)]
         dist.all_gather(poses_all, batch.pose)
         dist.all_gather(klds_all, batch.kld)
+        if args.dump_outputs:
+            costs_all = [torch.empty_like(batch.costs()) for _ in range(world)]
+            dist.all_gather(costs_all, batch.costs())
         sync()
+    if args.dump_outputs and rank == 0:
+        if dist is None:
+            poses_all, klds_all, costs_all = [batch.pose], [batch.kld], [batch.costs()]
+        dump_outputs(args.dump_outputs, {"poses": torch.cat(poses_all).reshape(-1, 4, 4), "log_depths": torch.cat(klds_all),
+                                         "costs": torch.cat(costs_all)})
     elapsed = elapsed_max
     kern_ms = kern_max
 
@@ -649,12 +696,12 @@ def main(argv=None):
                      "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": alg_bytes / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                      "traffic": None, "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": kern_ms},
     }
-    # HBM traffic per launch is a PMC measurement (rocprofv3 --pmc, one counter per pass): taken in this run by profiling
-    # two short child runs of this very command; if that is not possible the figure of the committed summary is carried,
-    # labelled as such
+    # HBM traffic per launch is a PMC measurement (rocprofv3 --pmc, one counter per pass): taken with --full by profiling
+    # two short child runs of this very command; otherwise, or if that is not possible, the figure of the committed summary is
+    # carried, labelled as such
     pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
     line["roofline"]["traffic_source"] = None
-    if rank == 0 and world == 1 and not dry and not args.no_pmc:
+    if args.full and rank == 0 and world == 1 and not dry and not args.no_pmc:
         hbm, detail = measure_traffic(args, f"k_cost_pairs<{mode_id}, {0 if args.no_depth_table else 6}, 0, {'true' if args.granule == 64 else 'false'}>")
         if hbm is not None:
             line["roofline"]["traffic"] = hbm
@@ -698,9 +745,10 @@ def main(argv=None):
         line["rccl_world"] = rccl_world
     if dry:
         line["data"] = "DRY RUN (no measurement)"
-    # (SP_BENCH_REHEARSE_MULTI=1 under torch.distributed.run with ONE rank: the N > 1 legs below on the one GPU there is -- tests/test_gpu_rccl.py)
+    # (--full with SP_BENCH_REHEARSE_MULTI=1 under torch.distributed.run with ONE rank: the N > 1 legs below on the one GPU there is --
+    #  tests/test_gpu_rccl.py)
     multi = world > 1 or (dist is not None and os.environ.get("SP_BENCH_REHEARSE_MULTI") == "1")
-    if multi and args.mode == "gn" and not args.no_extras:
+    if args.full and multi and args.mode == "gn" and not args.no_extras:
         # whole-job frame pairs per second: every rank runs the quoted schedule on its own pairs at the same time (barrier, max
         # over ranks), from the initial values; one untimed pass first.  (On one GPU this is leg (c) of the extras below.)
         from super_primitive_amd.optim.pair_batch import FRAME_PAIR_SCHEDULE
@@ -730,7 +778,7 @@ def main(argv=None):
             line["frame_pairs_per_sec"] = world * rs["frame_pairs_per_sec"]
             line["roofline_schedule"] = rs.get("roofline_schedule")
             line["frame_pairs_per_sec_what"] = "reference start (sigma 0.05, depth seeds log(2 + 2 rand)), slot-level continuous batching, all ranks at once"
-    if rank == 0 and not multi and not args.no_extras and not dry:
+    if args.full and rank == 0 and not multi and not args.no_extras and not dry:
         # side measurements outside the timed region: (a) one pair alone (launch/latency bound, lives in the
         # Infinity Cache), (b) full coarse-to-fine schedule -> frame pairs per second.  ONE-GPU LINE ONLY: under torch.distributed.run
         # (N > 1) the other ranks would sit at the closing barrier for the half minute these take on rank 0; the
@@ -1078,7 +1126,7 @@ def main(argv=None):
         else:
             line["frame_pair_schedule"] = "3 levels (coarse to fine) x 500 Adam iterations (the reference's budget, two_frame_sfm.py:128)"
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not dry:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not dry:
         line["cpu_baseline"] = cpu_baseline(pairs[0], args.cpu_iters)
     if rank == 0:
         print(json.dumps(line))

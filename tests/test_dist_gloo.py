@@ -122,13 +122,21 @@ class _FakeBatch:
         self.M, self.Ps, self.max_N, self.span_points = M, [1000] * M, 4, 256
         self.pose = torch.eye(4).reshape(1, 16).repeat(M, 1).contiguous()
         self.kld = torch.zeros(M * 4)
+        self._costs = torch.zeros(M)
+        self._initial = (self.pose.clone(), self.kld.clone())
         self.calls = 0
 
     def cost_pass(self, level, mode, irls_eps=1e-3):
         self.calls += 1
 
     def solve_gn(self, level=0):
+        self._costs = self.pose[:, 0].clone()
         self.pose += 1.0
+        self.kld += 0.5
+        return self._costs
+
+    def costs(self):
+        return self._costs
 
     solve_adam = solve_gn
 
@@ -143,13 +151,15 @@ class _FakeBatch:
 
     def restore_initial(self):
         self.restored = getattr(self, "restored", 0) + 1
+        self.pose.copy_(self._initial[0])
+        self.kld.copy_(self._initial[1])
 
     def run_scheduled(self, **kw):
         self.scheduled = getattr(self, "scheduled", 0) + 1
         return 1
 
 
-def _bench_worker(rank, world, port, q):
+def _bench_worker(rank, world, port, q, extra=("--settle-ms", "0", "--full")):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world))
     import contextlib
     import io
@@ -162,9 +172,9 @@ def _bench_worker(rank, world, port, q):
     bench.build_batch = lambda args, rank, dev: (fake, [])
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "2", "--settle-ms", "0", "--dry-run"])
+        bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "2", "--dry-run", *extra])
     out = buf.getvalue().strip()
-    q.put((rank, json.loads(out) if out else None, fake.calls, fake.scheduled, fake.restored))
+    q.put((rank, json.loads(out) if out else None, fake.calls, getattr(fake, "scheduled", 0), getattr(fake, "restored", 0)))
 
 
 @pytest.mark.parametrize("world", [2, 8])
@@ -267,3 +277,52 @@ def test_segment_sharded_completion_control_flow_world8(n_segments):
         p.join(60)
         assert p.exitcode == 0
     assert [g[0] for g in got] == list(range(world)) and all(g[1] for g in got) and all(g[2] == 1 for g in got)
+
+
+def test_bench_plain_dry_run_times_the_steps_alone_and_dumps_the_last_outputs(tmp_path, monkeypatch):
+    """A run without --full: warm-up + exactly --steps cost passes and nothing else (no schedule, no CPU baseline), and
+    --dump-outputs writes the poses, log-depths and costs the last timed step left, as float32."""
+    import contextlib
+    import io
+    import json
+    import bench
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "TORCHELASTIC_RUN_ID"):
+        monkeypatch.delenv(k, raising=False)
+    fake = _FakeBatch(6)
+    monkeypatch.setattr(bench, "build_batch", lambda args, rank, dev: (fake, []))
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        bench.main(["--gpus", "1", "--steps", "7", "--warmup", "2", "--settle-ms", "0", "--dry-run", "--dump-outputs", str(tmp_path / "out")])
+    line = json.loads(buf.getvalue().strip())
+    assert fake.calls == 2 + 7 and line["steps"] == 7 and line["timed_regions"] == 1
+    assert not hasattr(fake, "scheduled") and "cpu_baseline" not in line and "frame_pairs_per_sec" not in line
+    np.testing.assert_allclose(line["value"], 6 * 7 / (line["ms_per_step"] * 7e-3), rtol=1e-6)
+    got = {k: np.load(tmp_path / "out" / (k + ".npy")) for k in ("poses", "log_depths", "costs")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["poses"], fake.pose.reshape(6, 4, 4).numpy())
+    assert got["poses"][0, 0, 0] == 1.0 + 9 and got["costs"].tolist() == [9.0] * 6 and got["log_depths"].tolist() == [4.5] * 24
+
+
+def test_bench_multi_rank_plain_dry_run_runs_nothing_after_the_gather_and_dumps_all_ranks(tmp_path):
+    """Without --full an N > 1 run does no whole-job schedule after its timed steps.  The time-based settle is followed by one
+    restore to the initial values, so what --dump-outputs writes (gathered over the ranks by rank 0) depends on --warmup and --steps
+    alone: 2 + 3 fake steps from the identity, whatever number of settle steps ran."""
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    extra = ("--settle-ms", "20", "--dump-outputs", str(tmp_path / "out"))
+    procs = [ctx.Process(target=_bench_worker, args=(r, world, port, q, extra)) for r in range(world)]
+    for p in procs:
+        p.start()
+    got = sorted([q.get(timeout=300) for _ in procs], key=lambda t: t[0])
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    line0 = got[0][1]
+    assert all(g[3] == 0 for g in got) and "frame_pairs_per_sec" not in line0 and "reference_start" not in line0
+    assert all(g[4] == 1 for g in got) and all(g[2] > 2 + 3 for g in got)            # one restore, after the settle steps
+    assert line0["rccl_world"] == world and line0["steps"] == 3 and line0["timed_regions"] == 1
+    out = {k: np.load(tmp_path / "out" / (k + ".npy")) for k in ("poses", "log_depths", "costs")}
+    assert out["poses"].shape == (world * 6, 4, 4) and out["log_depths"].shape == (world * 6 * 4,) and out["costs"].shape == (world * 6,)
+    assert (out["poses"][:, 0, 0] == 1.0 + 5).all() and (out["costs"] == 5.0).all() and (out["log_depths"] == 2.5).all()

@@ -57,7 +57,7 @@ def test_the_legs_of_an_n_gpu_bench_line_run_on_the_one_gpu_there_is():
     group -- rehearsed under torch.distributed.run with the one rank there is (``SP_BENCH_REHEARSE_MULTI=1``): hooks, collectives and the
     verdict counts of the line have executed on hardware before an 8-GPU node sees them; the one-GPU side measurements are skipped."""
     line = _torchrun(["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--pairs", "32", "--settle-ms", "20", "--sigma05-scenes", "2",
-                      "--no-cpu-baseline", "--no-pmc"], SP_BENCH_REHEARSE_MULTI="1")
+                      "--no-cpu-baseline", "--no-pmc", "--full"], SP_BENCH_REHEARSE_MULTI="1")
     print("\nN > 1 legs, 1 rank:", {k: line.get(k) for k in ("frame_pairs_per_sec", "frame_pairs_per_sec_near_start", "frame_pairs_status")})
     assert line["rccl_world"] == 1 and line["frame_pairs_per_sec"] > 0 and line["frame_pairs_per_sec_near_start"] > 0
     st = line["frame_pairs_status"]

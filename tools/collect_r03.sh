@@ -7,14 +7,14 @@ OUT=gpurun_out/r03
 mkdir -p $OUT
 (timeout 600 python -m pytest tests -m gpu -q 2>&1 | tail -6) > $OUT/pytest.txt
 (timeout 300 python -m pytest tests/test_gpu_sigma05.py tests/test_gpu_window_gn.py tests/test_gpu_sequence.py -m gpu -q -s 2>&1 | grep -v "^make\|amdgpu.ids\|^$") > $OUT/parity.txt
-timeout 600 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 600 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python bench.py --no-cpu-baseline --no-extras --no-pmc > $OUT/bench_under_rocprof.json 2>/dev/null
-timeout 300 python bench.py --mode adam --no-cpu-baseline --no-extras > $OUT/bench_n1_adam.json 2>/dev/null
-timeout 300 python bench.py --granule 64 --no-cpu-baseline --sigma05-scenes 0 > $OUT/bench_n1_g64.json 2>/dev/null
-timeout 400 python bench.py --segments 128 --no-cpu-baseline --sigma05-scenes 0 > $OUT/bench_n1_seg128.json 2>/dev/null
+timeout 300 python bench.py --full --mode adam --no-cpu-baseline --no-extras > $OUT/bench_n1_adam.json 2>/dev/null
+timeout 300 python bench.py --full --granule 64 --no-cpu-baseline --sigma05-scenes 0 > $OUT/bench_n1_g64.json 2>/dev/null
+timeout 400 python bench.py --full --segments 128 --no-cpu-baseline --sigma05-scenes 0 > $OUT/bench_n1_seg128.json 2>/dev/null
 for N in 64 300 1200; do
   for G in 256 64; do
-    timeout 400 python bench.py --shape blobs --segments $N --granule $G --no-cpu-baseline --sigma05-scenes 0 > $OUT/bench_blobs_${N}_g$G.json 2>/dev/null
+    timeout 400 python bench.py --full --shape blobs --segments $N --granule $G --no-cpu-baseline --sigma05-scenes 0 > $OUT/bench_blobs_${N}_g$G.json 2>/dev/null
   done
 done
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_blobs_1200_g64 -o bench -- python bench.py --shape blobs --segments 1200 --granule 64 --no-cpu-baseline --no-extras --no-pmc > /dev/null 2>&1

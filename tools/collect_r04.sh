@@ -9,12 +9,12 @@ mkdir -p $OUT
 (timeout 400 python -m pytest tests/test_gpu_sigma05.py tests/test_gpu_window_gn.py tests/test_gpu_sequence.py tests/test_gpu_rccl.py tests/test_gpu_drivers.py -m gpu -q -s 2>&1 \
    | grep -v "^make\|amdgpu.ids\|^$\|^   per-frame\|^   frame" | cut -c1-1500) > $OUT/parity.txt
 (timeout 200 python -m pytest tests/test_gpu_pairs.py tests/test_gpu_fullsize.py -m gpu -q -s -k "slot_level or config5_as_a_batch" 2>&1 | grep "pairs\|config 5\|passed" | cut -c1-600) >> $OUT/parity.txt
-timeout 900 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 900 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python bench.py --no-cpu-baseline --no-extras --no-pmc > $OUT/bench_under_rocprof.json 2>/dev/null
-timeout 300 python bench.py --no-depth-table --no-cpu-baseline --no-extras > $OUT/bench_n1_log_depth_tables.json 2>/dev/null
+timeout 300 python bench.py --full --no-depth-table --no-cpu-baseline --no-extras > $OUT/bench_n1_log_depth_tables.json 2>/dev/null
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_logtab -o bench -- python bench.py --no-depth-table --no-cpu-baseline --no-extras --no-pmc > /dev/null 2>&1
-timeout 300 python bench.py --mode adam --no-cpu-baseline --no-extras > $OUT/bench_n1_adam.json 2>/dev/null
-timeout 500 python bench.py --segments 128 --no-cpu-baseline > $OUT/bench_n1_seg128.json 2>/dev/null
+timeout 300 python bench.py --full --mode adam --no-cpu-baseline --no-extras > $OUT/bench_n1_adam.json 2>/dev/null
+timeout 500 python bench.py --full --segments 128 --no-cpu-baseline > $OUT/bench_n1_seg128.json 2>/dev/null
 # instruction counts of the dominant kernel, depth tables against log-depth tables (SQ counters, their own passes, --kernel-trace only)
 for tab in "" "--no-depth-table"; do
   tag=dt; [ -n "$tab" ] && tag=logtab

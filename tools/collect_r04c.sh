@@ -7,7 +7,7 @@ mkdir -p $OUT
 timeout 1200 python -m pytest tests -m gpu -q -s > /tmp/pytest_full.txt 2>&1
 tail -4 /tmp/pytest_full.txt > $OUT/pytest.txt
 grep -v "^make\|amdgpu.ids\|^$\|^   per-frame\|^   frame\|^hipcc" /tmp/pytest_full.txt | cut -c1-1500 > $OUT/parity.txt
-timeout 900 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 900 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python bench.py --no-cpu-baseline --no-extras --no-pmc > $OUT/bench_under_rocprof.json 2>/dev/null
 SP_GRANULE=64 timeout 200 python tools/setup_bench.py 2>/dev/null | grep "set-up\|timeline" > $OUT/setup.txt
 timeout 200 python tools/host_profile.py 384 2>/dev/null | grep -v "^$" | cut -c1-170 | head -34 > $OUT/host_profile.txt

@@ -9,14 +9,14 @@ mkdir -p $OUT
 (timeout 600 python -m pytest tests/test_gpu_sigma05.py tests/test_gpu_window_gn.py tests/test_gpu_sequence.py tests/test_gpu_rccl.py tests/test_gpu_drivers.py -m gpu -q -s 2>&1 \
    | grep -v "^make\|amdgpu.ids\|^$\|^   per-frame\|^   frame\|^   keyframe\|^   mapping" | cut -c1-1500) > $OUT/parity.txt
 (timeout 300 python -m pytest tests/test_gpu_pairs.py tests/test_gpu_fullsize.py -m gpu -q -s -k "slot_level or config5_as_a_batch or verdict or box" 2>&1 | grep "pairs\|config 5\|passed" | cut -c1-600) >> $OUT/parity.txt
-timeout 900 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 900 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python bench.py --no-cpu-baseline --no-extras --no-pmc > $OUT/bench_under_rocprof.json 2>/dev/null
 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-pmc > $OUT/bench_n1_driver_flags.json 2>/dev/null
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2>/dev/null      # the driver's own command (38 s)
-timeout 300 python bench.py --mode adam --no-cpu-baseline --no-extras > $OUT/bench_n1_adam.json 2>/dev/null
-timeout 500 python bench.py --segments 128 --no-cpu-baseline > $OUT/bench_n1_seg128.json 2>/dev/null
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2>/dev/null      # the headline step counts with every side leg (38 s)
+timeout 300 python bench.py --full --mode adam --no-cpu-baseline --no-extras > $OUT/bench_n1_adam.json 2>/dev/null
+timeout 500 python bench.py --full --segments 128 --no-cpu-baseline > $OUT/bench_n1_seg128.json 2>/dev/null
 for S in 64 300 1200; do
-  timeout 900 python bench.py --shape blobs --segments $S --no-cpu-baseline --no-pmc > $OUT/bench_blobs_${S}.json 2> /dev/null
+  timeout 900 python bench.py --full --shape blobs --segments $S --no-cpu-baseline --no-pmc > $OUT/bench_blobs_${S}.json 2> /dev/null
 done
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/stats_blobs64 -o bench -- python $GRAFT_REPO_ROOT/bench.py --shape blobs --segments 64 --no-cpu-baseline --no-extras --no-pmc > /dev/null 2>&1)
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/stats_blobs300 -o bench -- python $GRAFT_REPO_ROOT/bench.py --shape blobs --segments 300 --no-cpu-baseline --no-extras --no-pmc > /dev/null 2>&1)

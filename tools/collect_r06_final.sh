@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r06late; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2>/dev/null
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2>/dev/null
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2>/dev/null

@@ -1,7 +1,8 @@
 #!/bin/bash
 # One node, one process per GPU, RCCL over xGMI -- the exact commands of the multi-GPU configurations.
 #
-#   tools/launch_node.sh bench   [N] [extra bench.py args]    weak scaling of the headline workload (what the driver runs for N = 1, 2, 4, 8)
+#   tools/launch_node.sh bench   [N] [extra bench.py args]    weak scaling of the headline workload (what the driver runs for N = 1, 2, 4, 8);
+#                                                             with --full also the whole-job frame-pair legs (frame_pairs_per_sec)
 #   tools/launch_node.sh config5 [N]                          BASELINE configs[4]: 1024 frame pairs x 128 segments over N ranks
 #   tools/launch_node.sh config4 [N]                          BASELINE configs[3]: VOID-shaped depth completion, segments of one image over N ranks
 #   (the same control flow on CPU, gloo, world 2 and 8, batch mocked: tests/test_dist_gloo.py::test_bench_multi_rank_control_flow_dry_run)
