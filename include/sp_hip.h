@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 15
+#define SP_ABI_VERSION 16
 
 #define SP_EINVAL (-1)   /* bad argument (null pointer, non-positive size, ...) */
 #define SP_ELIMIT (-2)   /* size outside what the kernels support (H or W > 32767, N > 65535, ...) */
@@ -853,6 +853,26 @@ typedef struct SpChainStep {
     int32_t pad_;
 } SpChainStep;
 int sp_chain_step(SpChainStep* step, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
+ * (ABI 16) S odometry sequences in LOCKSTEP: sp_chain_step on n_steps records at once (reference: odometery/odometery.py:1018-1075, the
+ * driver loop of one sequence per record).  Every stage covers all records with the same launches -- the frames' pyramids one launch per
+ * level, node overwrites / edge composition / LM resets one launch each, the phase loop the round body of sp_window_gn_run_multi (cost pass
+ * over all work lists, per-edge reduce, Schur terms, update: window = blockIdx.z), the criterion's splat and select passes with the record
+ * on blockIdx.y -- so the launches per call do not grow with n_steps.  A phase ends once EVERY window froze (st[6]) or at its max_iters;
+ * the polls are run_phases' (the first after check_first iterations when conv_tol > 0, none after a phase's last iteration).  A frozen
+ * window is inert, so per record the result is BITWISE sp_chain_step's on that record alone: out_pose, out_aff, the supp window's
+ * log-depths and nodes, kld_dst, crit_host, track_iters, supp_iters, and the 16-float states left in each window's state_host.
+ * The call is HOMOGENEOUS: every record has the same stages, H, W, n_levels, valid_thresh, and per present stage the same phase list
+ * (level, max_iters, irls_eps, conv_tol), check_every, check_first, flags and LM constants (lam0, lm_up, lm_down, lm_min); otherwise
+ * -- or for n_steps outside 1 .. 65535 or a null pointer -- SP_EINVAL before anything is launched.
+ *   args_dev    : device scratch of n_steps * sp_chain_multi_bytes() bytes (the argument records, one host-to-device copy per call)
+ *   states_dev  : device scratch of 36 * n_steps floats; states_host: pinned host memory of the same size -- [16 n] the tracker windows'
+ *                 states, [16 n] the supp windows', [4 n] the criteria (one gathered device-to-host copy and one synchronisation at the end,
+ *                 plus the phase loop's polls)
+ * The records live in HOST memory as for sp_chain_step. */
+int sp_chain_multi_bytes(void);
+int sp_chain_step_multi(SpChainStep* steps, int n_steps, void* args_dev, float* states_dev, float* states_host, void* stream);
 
 #ifdef __cplusplus
 }

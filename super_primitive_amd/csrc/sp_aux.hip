@@ -52,13 +52,11 @@ __device__ __forceinline__ void table_point(const uint32_t* __restrict__ pix, co
 
 // core/ops.py:59-96 (mean=False): key = (point index + 1) << 32 | z bits, atomicMax => highest index wins,
 // i.e. the result of a sequential scatter_
-__global__ __launch_bounds__(SP_BLOCK) void k_splat_keys(const uint32_t* __restrict__ pix, const float* __restrict__ baseL,
-                                                         const int32_t* __restrict__ seg_off, const float* __restrict__ kp_L,
-                                                         const float* __restrict__ kld, int N, int P, int H, int W,
-                                                         const float* __restrict__ K9, const float* __restrict__ T16,
-                                                         unsigned long long* __restrict__ keys) {
-    const int i = blockIdx.x * SP_BLOCK + threadIdx.x;
-    if (i >= P) return;
+__device__ __forceinline__ void splat_key_at(const uint32_t* __restrict__ pix, const float* __restrict__ baseL,
+                                             const int32_t* __restrict__ seg_off, const float* __restrict__ kp_L,
+                                             const float* __restrict__ kld, int N, int H, int W,
+                                             const float* __restrict__ K9, const float* __restrict__ T16,
+                                             unsigned long long* __restrict__ keys, int i) {
     float x, y, d; int n;
     table_point(pix, baseL, seg_off, kp_L, kld, N, i, K9, x, y, d, n);
     const float qx = fmaf(T16[0], x, fmaf(T16[1], y, T16[2] * d)) + T16[3];
@@ -73,6 +71,16 @@ __global__ __launch_bounds__(SP_BLOCK) void k_splat_keys(const uint32_t* __restr
     if (r < 0 || r >= H || c < 0 || c >= W) return;
     const unsigned long long key = ((unsigned long long)(i + 1) << 32) | (unsigned long long)__float_as_uint(qz);
     atomicMax(&keys[(size_t)r * W + c], key);
+}
+
+__global__ __launch_bounds__(SP_BLOCK) void k_splat_keys(const uint32_t* __restrict__ pix, const float* __restrict__ baseL,
+                                                         const int32_t* __restrict__ seg_off, const float* __restrict__ kp_L,
+                                                         const float* __restrict__ kld, int N, int P, int H, int W,
+                                                         const float* __restrict__ K9, const float* __restrict__ T16,
+                                                         unsigned long long* __restrict__ keys) {
+    const int i = blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (i >= P) return;
+    splat_key_at(pix, baseL, seg_off, kp_L, kld, N, H, W, K9, T16, keys, i);
 }
 
 // core/ops.py:84-92 (mean=True): scatter_reduce_(0, index, depth, reduce='mean') with its default include_self=True -- the zero
@@ -329,9 +337,10 @@ __global__ __launch_bounds__(KF_BLOCK) void k_kf_criterion(const float* __restri
 // the four passes' tickets.  Exactly k_kf_criterion's selection -- the k-th smallest key -- so the same bits come out.
 constexpr int KF_WS_WORDS = 4 * 256 + 8;
 constexpr int KF_GRID_BLOCK = 256, KF_PER_THREAD = 16;
-__global__ __launch_bounds__(KF_GRID_BLOCK) void k_kf_select_pass(const float* __restrict__ depth, int n, float thresh, int pass, uint32_t* __restrict__ ws,
-                                                                  const float* __restrict__ pose_src, const float* __restrict__ pose_trg,
-                                                                  float* __restrict__ out) {
+// (the body of k_kf_select_pass; n_groups = the workgroups of ONE criterion -- the last of them to arrive finishes the pass)
+__device__ __forceinline__ void kf_select_pass_body(const float* __restrict__ depth, int n, float thresh, int pass, uint32_t* __restrict__ ws,
+                                                    const float* __restrict__ pose_src, const float* __restrict__ pose_trg,
+                                                    float* __restrict__ out, unsigned n_groups) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t last;
     uint32_t* g_hist = ws + pass * 256;
@@ -354,7 +363,7 @@ __global__ __launch_bounds__(KF_GRID_BLOCK) void k_kf_select_pass(const float* _
     if (hist[threadIdx.x]) atomicAdd(&g_hist[threadIdx.x], hist[threadIdx.x]);
     __threadfence();
     __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(&st[4 + pass], 1u) == gridDim.x - 1 ? 1u : 0u;
+    if (threadIdx.x == 0) last = atomicAdd(&st[4 + pass], 1u) == n_groups - 1 ? 1u : 0u;
     __syncthreads();
     if (!last) return;
     __threadfence();
@@ -388,6 +397,40 @@ __global__ __launch_bounds__(KF_GRID_BLOCK) void k_kf_select_pass(const float* _
     const double ax = D[7] - D[5], ay = D[2] - D[6], az = D[3] - D[1];
     const double sn = 0.5 * sqrt(ax * ax + ay * ay + az * az), cs = 0.5 * (D[0] + D[4] + D[8] - 1.0);
     out[3] = (float)(atan2(sn, cs) * 57.29577951308232);
+}
+
+__global__ __launch_bounds__(KF_GRID_BLOCK) void k_kf_select_pass(const float* __restrict__ depth, int n, float thresh, int pass, uint32_t* __restrict__ ws,
+                                                                  const float* __restrict__ pose_src, const float* __restrict__ pose_trg,
+                                                                  float* __restrict__ out) {
+    kf_select_pass_body(depth, n, thresh, pass, ws, pose_src, pose_trg, out, gridDim.x);
+}
+
+// ---- sp_chain_step_multi: the keyframe criterion of S sequences per launch (sequence = blockIdx.y; same bodies as above) --------------
+__global__ __launch_bounds__(SP_BLOCK) void k_chain_crit_zero(const ChainCritJob* __restrict__ jobs, int HW) {
+    const ChainCritJob& j = jobs[blockIdx.y];
+    for (int i = blockIdx.x * SP_BLOCK + threadIdx.x; i < HW; i += gridDim.x * SP_BLOCK) j.keys[i] = 0ull;
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < KF_WS_WORDS; i += SP_BLOCK) j.ws[i] = 0u;
+}
+
+__global__ __launch_bounds__(SP_BLOCK) void k_chain_splat_keys(const ChainCritJob* __restrict__ jobs, int H, int W) {
+    const ChainCritJob& j = jobs[blockIdx.y];
+    const int i = blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (i >= j.P) return;
+    splat_key_at(j.pix, j.baseL, j.seg_off, j.kp_L, j.kld, j.N, H, W, j.K, j.rel_pose, j.keys, i);
+}
+
+__global__ __launch_bounds__(SP_BLOCK) void k_chain_splat_decode(const ChainCritJob* __restrict__ jobs, int HW) {
+    const ChainCritJob& j = jobs[blockIdx.y];
+    const int i = blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (i >= HW) return;
+    const unsigned long long k = j.keys[i];
+    j.depth[i] = k ? __uint_as_float((uint32_t)(k & 0xffffffffull)) : 0.f;
+}
+
+__global__ __launch_bounds__(KF_GRID_BLOCK) void k_chain_select_pass(const ChainCritJob* __restrict__ jobs, int n, float thresh, int pass) {
+    const ChainCritJob& j = jobs[blockIdx.y];
+    kf_select_pass_body(j.depth, n, thresh, pass, j.ws, j.pose, j.kf_pose, j.crit, gridDim.x);
 }
 
 }  // namespace
@@ -500,6 +543,29 @@ int sp_kf_criterion(const float* depth, int n, float thresh, const float* pose_s
 }
 
 int sp_kf_criterion_ws_words(void) { return KF_WS_WORDS; }
+
+}  // extern "C"
+
+// (every job checked by the caller as sp_depth_splat / sp_kf_criterion_ws check their arguments; P <= max_P)
+int chain_criterion_multi(const ChainCritJob* jobs_dev, int n, int max_P, int H, int W, float thresh, void* stream) {
+    if (!jobs_dev || n <= 0 || n > 65535 || max_P <= 0 || H <= 0 || W <= 0 || !(thresh >= 0.f)) return SP_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int HW = H * W;
+    hipLaunchKernelGGL(k_chain_crit_zero, dim3((HW + SP_BLOCK - 1) / SP_BLOCK < 64 ? (HW + SP_BLOCK - 1) / SP_BLOCK : 64, n), dim3(SP_BLOCK), 0, s, jobs_dev, HW);
+    SP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_chain_splat_keys, dim3((max_P + SP_BLOCK - 1) / SP_BLOCK, n), dim3(SP_BLOCK), 0, s, jobs_dev, H, W);
+    SP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_chain_splat_decode, dim3((HW + SP_BLOCK - 1) / SP_BLOCK, n), dim3(SP_BLOCK), 0, s, jobs_dev, HW);
+    SP_CHECK_LAUNCH();
+    const int grid = (HW + KF_GRID_BLOCK * KF_PER_THREAD - 1) / (KF_GRID_BLOCK * KF_PER_THREAD);
+    for (int pass = 0; pass < 4; ++pass) {
+        hipLaunchKernelGGL(k_chain_select_pass, dim3(grid, n), dim3(KF_GRID_BLOCK), 0, s, jobs_dev, HW, thresh, pass);
+        SP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+extern "C" {
 
 int sp_kf_criterion_ws(const float* depth, int n, float thresh, const float* pose_src, const float* pose_trg, uint32_t* ws, float* out,
                        void* stream) {

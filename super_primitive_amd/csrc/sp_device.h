@@ -51,6 +51,35 @@ struct MultiList {
     int32_t first_block;      // its workgroups are blockIdx.x - first_block (a multiple of 8)
 };
 __attribute__((visibility("hidden"))) int cost_pairs_multi(const MultiList* lists_dev, int n_lists, int total_blocks, int mode, float irls_eps, void* stream);
+
+// ---- S sequences per launch (sp_chain_step_multi, sp_chain.hip): the per-sequence records its stages read from device memory --------
+// one level of a frame's pyramid: in = the planar (3, H_{l-1}, W_{l-1}) level above (level 0: the frame itself), out = the planar level
+// (NULL at level 0), packed = the tracker's packed target at this level or NULL; jobs_dev = [n_levels][n] records
+struct ChainImgJob { const float* in; float* out; float* packed; };
+__attribute__((visibility("hidden"))) int chain_pyramid_multi(const ChainImgJob* jobs_dev, int n, int n_levels, int H, int W, void* stream);
+// sp_window_compose of n windows (one workgroup each)
+struct ChainComposeJob { const SpPair* pairs; const SpWindowEdge* edges; SpWindowNode* nodes; int32_t n_edges, n_nodes; };
+__attribute__((visibility("hidden"))) int chain_compose_multi(const ChainComposeJob* jobs_dev, int n, void* stream);
+__attribute__((visibility("hidden"))) int chain_compose_max_edges(void);
+// the keyframe criterion of n sequences (sp_depth_splat + sp_kf_criterion_ws): keys / ws zeroed, splat, decode, four select passes
+struct ChainCritJob {
+    const uint32_t* pix; const float* baseL; const int32_t* seg_off; const float* kp_L; const float* kld; const float* K;
+    const float* rel_pose; const float* pose; const float* kf_pose;
+    unsigned long long* keys; float* depth; uint32_t* ws; float* crit;
+    int32_t N, P;
+};
+__attribute__((visibility("hidden"))) int chain_criterion_multi(const ChainCritJob* jobs_dev, int n, int max_P, int H, int W, float thresh, void* stream);
+// Gauss-Newton rounds of n windows side by side (the round body of sp_window_gn_run_multi).  wgn_multi_fill writes the n device-side
+// argument records (wgn_multi_args_bytes() each) and work lists (sizeof(MultiList) each) of one phase into host staging memory;
+// allow_inline: a depth-less window of a few edges reduces its edges inside the update kernel, as sp_window_gn_step does
+struct WgnMultiInfo { int total_blocks, max_edges, max_blocks, max_y, n_reduce; };
+__attribute__((visibility("hidden"))) int wgn_multi_args_bytes(void);
+__attribute__((visibility("hidden"))) int wgn_multi_fill(const SpWindowGn* const* windows, int n, int flags, float lm_up, float lm_down, float lm_min,
+                                                          float conv_tol, bool allow_inline, void* args_host, MultiList* lists_host, WgnMultiInfo* info);
+__attribute__((visibility("hidden"))) int wgn_multi_round(const void* args_dev, const MultiList* lists_dev, int n, const WgnMultiInfo& info, int flags,
+                                                           float irls_eps, void* stream);
+// the windows' 16-float LM states -> out[16 n]
+__attribute__((visibility("hidden"))) int wgn_multi_gather(const void* args_dev, int n, float* out, void* stream);
 __attribute__((visibility("hidden"))) int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stream, int first_phase, const SpQueue* queue, int n_slots,
                                                               const int32_t* active, int n_active, uint32_t idle_mask);
 

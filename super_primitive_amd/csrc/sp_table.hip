@@ -1363,6 +1363,29 @@ __global__ __launch_bounds__(SP_BLOCK) void k_prep_pack(const SpPrepImage* __res
     if (i < j.H * j.W) pack_texel(generic(j.in), j.H * j.W, i, generic(j.out));
 }
 
+// ---- sp_chain_step_multi: one level of S frames' pyramids per launch (sequence = blockIdx.y) ---------------------------------------
+// Level 0 packs the frame; level l > 0 blurs / decimates the planar level above (all three channels: one thread per output pixel) and
+// packs what it wrote -- the values of sp_blur_decimate + sp_pack_rgb, from the same blur_decimate_at / pack_texel.
+__global__ __launch_bounds__(SP_BLOCK) void k_chain_pyramid_multi(const ChainImgJob* __restrict__ jobs, int H, int W, int Ho, int Wo, int level0) {
+    const ChainImgJob j = jobs[blockIdx.y];
+    const int i = blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (i >= Ho * Wo) return;
+    if (level0) {
+        if (j.packed) pack_texel(j.in, Ho * Wo, i, j.packed);
+        return;
+    }
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        v[c] = blur_decimate_at(j.in + (size_t)c * H * W, H, W, Wo, i);
+        j.out[(size_t)c * Ho * Wo + i] = v[c];
+    }
+    if (j.packed) {
+        float* q = j.packed + (size_t)i * SP_TEXEL_FLOATS;
+        q[0] = v[0]; q[1] = v[1]; q[2] = v[2];
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1426,6 +1449,24 @@ int sp_blur_decimate(const float* in, int C, int H, int W, float* out, void* str
     return 0;
 }
 
+
+}  // extern "C"
+
+int chain_pyramid_multi(const ChainImgJob* jobs_dev, int n, int n_levels, int H, int W, void* stream) {
+    if (!jobs_dev || n <= 0 || n > 65535 || n_levels < 1 || H < 2 || W < 2) return SP_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int h = H, w = W;
+    for (int l = 0; l < n_levels; ++l) {
+        const int ho = l ? (h + 1) / 2 : h, wo = l ? (w + 1) / 2 : w;
+        hipLaunchKernelGGL(k_chain_pyramid_multi, dim3((ho * wo + SP_BLOCK - 1) / SP_BLOCK, n), dim3(SP_BLOCK), 0, s, jobs_dev + (size_t)l * n, h, w, ho, wo,
+                           l == 0 ? 1 : 0);
+        SP_CHECK_LAUNCH();
+        h = ho; w = wo;
+    }
+    return 0;
+}
+
+extern "C" {
 
 static_assert(sizeof(SpPrepTable) == 240 && sizeof(SpPrepSample) == 176 && sizeof(SpPrepImage) == 24, "preparation job records are part of the ABI");
 

@@ -359,7 +359,26 @@ __global__ __launch_bounds__(SP_BLOCK) void k_window_update(WinArgs w) {
     else window_update_body<false>(w);
 }
 
+// sp_window_compose of many windows: window = blockIdx.x (sp_chain_step_multi)
+__global__ __launch_bounds__(SP_BLOCK) void k_window_compose_multi(const ChainComposeJob* __restrict__ jobs) {
+    const ChainComposeJob j = jobs[blockIdx.x];
+    WinArgs w{};
+    w.pairs = j.pairs; w.edges = j.edges; w.n_edges = j.n_edges; w.nodes = j.nodes; w.n_nodes = j.n_nodes; w.compose_only = 1;
+    if (w.n_edges <= SP_WIN_LDS_EDGES && w.n_nodes <= SP_WIN_LDS_NODES) window_update_body<true>(w);
+    else window_update_body<false>(w);
+}
+
 }  // namespace
+
+// (the caller checked every job as sp_window_compose does: pointers set, 0 < n_edges <= SP_WIN_MAX_EDGES, n_nodes > 0)
+int chain_compose_multi(const ChainComposeJob* jobs_dev, int n, void* stream) {
+    if (!jobs_dev || n <= 0) return SP_EINVAL;
+    hipLaunchKernelGGL(k_window_compose_multi, dim3(n), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), jobs_dev);
+    SP_CHECK_LAUNCH();
+    return 0;
+}
+
+int chain_compose_max_edges(void) { return SP_WIN_MAX_EDGES; }
 
 extern "C" {
 

@@ -251,7 +251,7 @@ __device__ __forceinline__ int ltri_row(int t) {
 // for the largest window, workgroups beyond a window's own edges / blocks / tiles return at once.  wins == NULL: the one window passed by value.
 __global__ __launch_bounds__(SP_BLOCK) void k_window_gn_reduce_multi(const WGnArgs* __restrict__ wins) {
     const WGnArgs& w = wins[blockIdx.z];
-    if ((int)blockIdx.x >= w.n_edges) return;
+    if ((int)blockIdx.x >= w.n_edges || (w.flags & SP_WGN_INLINE_REDUCE)) return;      // (inline: the update kernel reduces the edges itself)
     wgn_reduce_edge(w.pairs, w.edges, w.span_partials, w.seg_partials, w.scratch, w.stride, w.Ad, w.loc, blockIdx.x, !(w.flags & 5));
 }
 
@@ -1153,48 +1153,22 @@ int sp_window_gn_run_multi(const SpWindowGn* windows, int n_windows, float irls_
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::vector<WGnArgs> host(n_windows);
     std::vector<MultiList> lists(n_windows);
-    int max_edges = 0, max_blocks = 0, max_y = 0, total_blocks = 0;
-    for (int i = 0; i < n_windows; ++i) {
-        const SpWindowGn& g = windows[i];
-        if (!g.chunks || !g.spans || g.n_spans <= 0) return SP_EINVAL;
-        if (int rc = wgn_fill_args(host[i], g.pairs, g.edges, g.n_edges, g.nodes, g.n_nodes, g.blocks, g.n_blocks, g.sum_N, g.max_N, g.n_unknowns,
-                                   g.span_partials, g.seg_partials, g.scratch, g.nodes_backup, g.kld_backup, flags, lm_up, lm_down, lm_min, conv_tol,
-                                   g.state, g.losses, g.max_losses))
-            return rc;
-        lists[i] = MultiList{g.pairs, g.chunks, g.spans, g.span_partials, g.seg_partials, g.n_spans, total_blocks};
-        total_blocks += (g.n_spans + 7) / 8 * 8;
-        max_edges = std::max(max_edges, g.n_edges); max_blocks = std::max(max_blocks, g.n_blocks); max_y = std::max(max_y, g.n_unknowns);
-    }
-    // the update kernel's instantiation is chosen for the LARGEST window; every window must fit the scratch it was sized for (cap_y): a window
-    // whose own scratch has no room for the global-memory triangle cannot ride in a batch that needs it
-    if (max_y > SP_WGN_LDS_Y)
-        for (int i = 0; i < n_windows; ++i) if (windows[i].n_unknowns <= SP_WGN_LDS_Y) return SP_EINVAL;
+    std::vector<const SpWindowGn*> ptrs(n_windows);
+    for (int i = 0; i < n_windows; ++i) ptrs[i] = windows + i;
+    WgnMultiInfo info;
+    if (int rc = wgn_multi_fill(ptrs.data(), n_windows, flags, lm_up, lm_down, lm_min, conv_tol, false, host.data(), lists.data(), &info)) return rc;
     WGnArgs* wins = static_cast<WGnArgs*>(args_dev);
     MultiList* lists_dev = reinterpret_cast<MultiList*>(static_cast<char*>(args_dev) + (sizeof(WGnArgs) * (size_t)n_windows + 15) / 16 * 16);
     hipError_t e = hipMemcpyAsync(wins, host.data(), sizeof(WGnArgs) * (size_t)n_windows, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(lists_dev, lists.data(), sizeof(MultiList) * (size_t)n_windows, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return -(1000 + (int)e);
-    const int lds = max_y * (max_y + 1) / 2;
-    const int tiles = std::max(1, (lds + SP_BLOCK * SP_WGN_PPT - 1) / (SP_BLOCK * SP_WGN_PPT));
-    const WGnArgs dummy{};
     int it = 0;
     while (it < max_iters) {
         const int n = (max_iters - it) < check_every ? (max_iters - it) : check_every;
-        for (int k = 0; k < n; ++k, ++it) {
-            int rc = cost_pairs_multi(lists_dev, n_windows, total_blocks, 2, irls_eps, stream);
-            if (rc != 0) return rc < 0 ? rc : -(1000 + rc);
-            hipLaunchKernelGGL(k_window_gn_reduce_multi, dim3(max_edges, 1, n_windows), dim3(SP_BLOCK), 0, s, (const WGnArgs*)wins);
-            if (!(flags & 5)) hipLaunchKernelGGL(k_window_gn_schur, dim3(max_blocks, tiles, n_windows), dim3(SP_BLOCK), 0, s, dummy, (const WGnArgs*)wins);
-            if (max_y <= 64) hipLaunchKernelGGL(k_window_gn_update<64>, dim3(1, 1, n_windows), dim3(wgn_update_threads(64)), 0, s, dummy, (const WGnArgs*)wins);
-            else if (max_y <= 128) hipLaunchKernelGGL(k_window_gn_update<128>, dim3(1, 1, n_windows), dim3(wgn_update_threads(128)), 0, s, dummy, (const WGnArgs*)wins);
-            else if (max_y <= SP_WGN_LDS_Y) hipLaunchKernelGGL(k_window_gn_update<SP_WGN_LDS_Y>, dim3(1, 1, n_windows), dim3(wgn_update_threads(SP_WGN_LDS_Y)), 0, s, dummy, (const WGnArgs*)wins);
-            else hipLaunchKernelGGL(k_window_gn_update<0>, dim3(1, 1, n_windows), dim3(wgn_update_threads(0)), 0, s, dummy, (const WGnArgs*)wins);
-            hipError_t el = hipGetLastError();
-            if (el != hipSuccess) return -(1000 + (int)el);
-        }
-        hipLaunchKernelGGL(k_wgn_gather_states, dim3((n_windows * SP_WGN_STATE + 255) / 256), dim3(256), 0, s, (const WGnArgs*)wins, n_windows, states_dev);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(states_host, states_dev, sizeof(float) * SP_WGN_STATE * (size_t)n_windows, hipMemcpyDeviceToHost, s);
+        for (int k = 0; k < n; ++k, ++it)
+            if (int rc = wgn_multi_round(wins, lists_dev, n_windows, info, flags, irls_eps, stream)) return rc;
+        if (int rc = wgn_multi_gather(wins, n_windows, states_dev, stream)) return rc;
+        e = hipMemcpyAsync(states_host, states_dev, sizeof(float) * SP_WGN_STATE * (size_t)n_windows, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return -(1000 + (int)e);
         if (conv_tol > 0.f) {
@@ -1207,3 +1181,61 @@ int sp_window_gn_run_multi(const SpWindowGn* windows, int n_windows, float irls_
 }
 
 }  // extern "C"
+
+// ---- the round body of sp_window_gn_run_multi, shared with sp_chain_step_multi (sp_device.h) --------------------------------------------
+int wgn_multi_args_bytes(void) { return (int)sizeof(WGnArgs); }
+
+int wgn_multi_fill(const SpWindowGn* const* windows, int n, int flags, float lm_up, float lm_down, float lm_min, float conv_tol, bool allow_inline,
+                   void* args_host, MultiList* lists_host, WgnMultiInfo* info) {
+    if (!windows || n <= 0 || n > 65535 || !args_host || !lists_host || !info) return SP_EINVAL;
+    WGnArgs* host = static_cast<WGnArgs*>(args_host);
+    int max_edges = 0, max_blocks = 0, max_y = 0, total_blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const SpWindowGn& g = *windows[i];
+        if (!g.chunks || !g.spans || g.n_spans <= 0) return SP_EINVAL;
+        if (int rc = wgn_fill_args(host[i], g.pairs, g.edges, g.n_edges, g.nodes, g.n_nodes, g.blocks, g.n_blocks, g.sum_N, g.max_N, g.n_unknowns,
+                                   g.span_partials, g.seg_partials, g.scratch, g.nodes_backup, g.kld_backup, flags, lm_up, lm_down, lm_min, conv_tol,
+                                   g.state, g.losses, g.max_losses))
+            return rc;
+        lists_host[i] = MultiList{g.pairs, g.chunks, g.spans, g.span_partials, g.seg_partials, g.n_spans, total_blocks};
+        total_blocks += (g.n_spans + 7) / 8 * 8;
+        max_edges = std::max(max_edges, g.n_edges); max_blocks = std::max(max_blocks, g.n_blocks); max_y = std::max(max_y, g.n_unknowns);
+    }
+    // the update kernel's instantiation is chosen for the LARGEST window; every window must fit the scratch it was sized for (cap_y): a window
+    // whose own scratch has no room for the global-memory triangle cannot ride in a batch that needs it
+    if (max_y > SP_WGN_LDS_Y)
+        for (int i = 0; i < n; ++i) if (windows[i]->n_unknowns <= SP_WGN_LDS_Y) return SP_EINVAL;
+    // the inline reduction of sp_window_gn_step, window by window under the same test (the 64-unknown instantiation is the only one that has it)
+    int n_reduce = n;
+    if (allow_inline && max_y <= 64 && (flags & 5) && !getenv("SP_WGN_NO_INLINE"))
+        for (int i = 0; i < n; ++i)
+            if (host[i].n_edges <= SP_WGN_INLINE_EDGES) { host[i].flags |= SP_WGN_INLINE_REDUCE; --n_reduce; }
+    *info = WgnMultiInfo{total_blocks, max_edges, max_blocks, max_y, n_reduce};
+    return 0;
+}
+
+int wgn_multi_round(const void* args_dev, const MultiList* lists_dev, int n, const WgnMultiInfo& info, int flags, float irls_eps, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const WGnArgs* wins = static_cast<const WGnArgs*>(args_dev);
+    const int max_y = info.max_y;
+    const int lds = max_y * (max_y + 1) / 2;
+    const int tiles = std::max(1, (lds + SP_BLOCK * SP_WGN_PPT - 1) / (SP_BLOCK * SP_WGN_PPT));
+    const WGnArgs dummy{};
+    int rc = cost_pairs_multi(lists_dev, n, info.total_blocks, 2, irls_eps, stream);
+    if (rc != 0) return rc < 0 ? rc : -(1000 + rc);
+    if (info.n_reduce > 0) hipLaunchKernelGGL(k_window_gn_reduce_multi, dim3(info.max_edges, 1, n), dim3(SP_BLOCK), 0, s, wins);
+    if (!(flags & 5)) hipLaunchKernelGGL(k_window_gn_schur, dim3(info.max_blocks, tiles, n), dim3(SP_BLOCK), 0, s, dummy, wins);
+    if (max_y <= 64) hipLaunchKernelGGL(k_window_gn_update<64>, dim3(1, 1, n), dim3(wgn_update_threads(64)), 0, s, dummy, wins);
+    else if (max_y <= 128) hipLaunchKernelGGL(k_window_gn_update<128>, dim3(1, 1, n), dim3(wgn_update_threads(128)), 0, s, dummy, wins);
+    else if (max_y <= SP_WGN_LDS_Y) hipLaunchKernelGGL(k_window_gn_update<SP_WGN_LDS_Y>, dim3(1, 1, n), dim3(wgn_update_threads(SP_WGN_LDS_Y)), 0, s, dummy, wins);
+    else hipLaunchKernelGGL(k_window_gn_update<0>, dim3(1, 1, n), dim3(wgn_update_threads(0)), 0, s, dummy, wins);
+    const hipError_t el = hipGetLastError();
+    return el == hipSuccess ? 0 : -(1000 + (int)el);
+}
+
+int wgn_multi_gather(const void* args_dev, int n, float* out, void* stream) {
+    hipLaunchKernelGGL(k_wgn_gather_states, dim3((n * SP_WGN_STATE + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const WGnArgs*>(args_dev), n, out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : -(1000 + (int)e);
+}

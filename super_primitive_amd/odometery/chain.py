@@ -124,6 +124,14 @@ class ChainStep:
         lands in ``hist_pose[i]`` / ``hist_aff[i]``.  SUPP: ``prev`` = history index of the older running supporting frame (the newer one
         is ``i``; ``supp_one``: there is only frame ``i`` -- ``prev`` = ``i``, the first slot's edge carries no weight).  CRITERION without TRACK: ``pose`` = the (4,4) device tensor to judge.  Returns (tracker iterations, mapper iterations,
         criterion [validity ratio, scale, translation difference, rotation degrees] | None)."""
+        keep = self._prepare(stages, i, image, start_pose, start_aff, prev, supp_images, supp_one, pose)
+        rc = self.lib.sp_chain_step(ctypes.byref(self.st), _lib.stream_ptr())
+        _lib.check(rc, "sp_chain_step")
+        del keep
+        return self._finish(stages)
+
+    def _prepare(self, stages, i=None, image=None, start_pose=None, start_aff=None, prev=None, supp_images=0, supp_one=False, pose=None):
+        """The argument record of one frame (``run``'s arguments); returns the tensors it points into that must outlive the call."""
         st = self.st
         keep = []
         st.stages = int(stages)
@@ -158,10 +166,58 @@ class ChainStep:
             edges = (self.mapper.edges_one if supp_one else self.mapper.edges_two).data_ptr()     # (one running frame: slot 0's edge off)
             for l in self.mapper.win.level_ids:
                 st.supp.gn[l].edges = edges
-        rc = self.lib.sp_chain_step(ctypes.byref(st), _lib.stream_ptr())
-        _lib.check(rc, "sp_chain_step")
+        return keep
+
+    def _finish(self, stages):
+        """After the call: the windows' pinned LM states are current; (tracker iterations, mapper iterations, criterion | None)."""
+        st = self.st
         for w in ((self.tracker.win,) if stages & TRACK else ()) + ((self.mapper.win,) if stages & SUPP else ()):
             w._gn.pop('host_stale', None)                # (the call left the pinned copy of the LM state current)
             w._gn['host_seen'] = True
         crit = self.crit_host.tolist() if stages & CRITERION else None
         return st.track_iters, st.supp_iters, crit
+
+
+class ChainStepBatch:
+    """``sp_chain_step_multi``: ONE call for the same stages of S sequences (one ``ChainStep`` each) -- every launch of the chain covers
+    all S, so the launches per frame index do not grow with S.  Per sequence the result is bitwise that of ``ChainStep.run`` on it alone
+    (tests/test_gpu_sequence_batch.py).  Owns the device argument area and the pinned states of the call, grown to the largest S seen."""
+
+    def __init__(self, device):
+        self.lib = _lib.load()
+        self.device = device
+        self.capacity = 0
+        self.n_calls = 0
+        self.sizes = []                  # sequences per call, in call order
+
+    def _grow(self, S):
+        if S <= self.capacity:
+            return
+        cap = max(S, 2 * self.capacity)
+        self.args_dev = torch.empty(cap * self.lib.sp_chain_multi_bytes(), dtype=torch.uint8, device=self.device)
+        self.states_dev = torch.zeros(36 * cap, dtype=torch.float32, device=self.device)
+        self.states_host = torch.zeros(36 * cap, dtype=torch.float32).pin_memory()
+        self.capacity = cap
+
+    def run(self, jobs):
+        """jobs: [(chain, dict of ``ChainStep.run`` keywords, ``stages`` included)], all with the same stages and frame size.  Returns
+        [(tracker iterations, mapper iterations, criterion | None)] in job order."""
+        S = len(jobs)
+        assert S >= 1
+        stages = int(jobs[0][1]['stages'])
+        assert all(int(kw['stages']) == stages for _, kw in jobs), "one call runs one stage mask"
+        self._grow(S)
+        keep = [ch._prepare(**kw) for ch, kw in jobs]
+        arr = (_lib.SpChainStep * S)()
+        for k, (ch, _) in enumerate(jobs):
+            arr[k] = ch.st
+        rc = self.lib.sp_chain_step_multi(arr, S, _lib.ptr(self.args_dev), _lib.ptr(self.states_dev), self.states_host.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "sp_chain_step_multi")
+        del keep
+        self.n_calls += 1
+        self.sizes.append(S)
+        out = []
+        for k, (ch, _) in enumerate(jobs):
+            ch.st.track_iters, ch.st.supp_iters = arr[k].track_iters, arr[k].supp_iters
+            out.append(ch._finish(stages))
+        return out

@@ -240,8 +240,12 @@ def map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose=1e-4, w
     affine = kf_affs is not None
     frozen0 = K == window_size
     if optimiser == "gn":
-        return _map_window_fused(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode,
-                                 gn=dict(MAP_GN_SCHEDULE, **(gn_schedule or {})))
+        ctx = map_window_gn_begin(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose=lr_pose, window_size=window_size,
+                                  initialised=initialised, rel_tol=rel_tol, gn_schedule=gn_schedule, mode=mode)
+        if ctx['win'] is not None:
+            for level, n, eps, tol in map_window_gn_phases(ctx):
+                ctx['n'] += ctx['win'].run_gn(level, n, irls_eps=eps, conv_tol=tol)
+        return map_window_gn_end(ctx)
     if fused:
         return _map_window_fused(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode)
     return _map_window_eager(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode)
@@ -357,26 +361,63 @@ def _build_map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose,
     return win, supp_node, src_ids
 
 
-def _map_window_fused(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode='map', gn=None):
+def map_window_gn_begin(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose=1e-4, window_size=5, initialised=True, rel_tol=1e-8,
+                        gn_schedule=None, mode='map'):
+    """``map_window(..., optimiser='gn')`` in three parts -- this one builds the window; ``map_window_gn_phases`` lists its Gauss-Newton
+    phases (run them with ``PoseWindow.run_gn`` or, for several windows side by side, ``PoseWindowBatch.run_gn``); ``map_window_gn_end``
+    reads the result.  Returns the context the other two take."""
     K = len(kfs)
-    win, supp_node, src_ids = _build_map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode, gn)
+    affine = kf_affs is not None
+    gn = dict(MAP_GN_SCHEDULE, **(gn_schedule or {}))
+    win, supp_node, src_ids = _build_map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, K == window_size, affine, initialised,
+                                                rel_tol, mode, gn)
+    return dict(win=win, supp_node=supp_node, src_ids=src_ids, K=K, affine=affine, gn=gn, num_iters=num_iters, kf_poses=kf_poses,
+                kf_klds=kf_klds, kf_affs=kf_affs, supp=supp, n=0)
+
+
+def map_window_gn_phases(ctx):
+    """[(level, max iterations, irls_eps, conv_tol)]: the main phase, then the polish (a short budget -- the supplementary mapping -- gets none)."""
+    gn, num_iters = ctx['gn'], ctx['num_iters']
+    out = [(0, min(num_iters, gn['max_iters']), gn['irls_eps'], gn['conv_tol'])]
+    if gn['polish_max'] > 0 and num_iters > gn['max_iters'] // 2:
+        out.append((0, gn['polish_max'], gn['polish_eps'], gn['polish_tol']))
+    return out
+
+
+def map_window_gn_end(ctx):
+    """``map_window``'s result once the phases ran (``ctx['n']``: the iterations they took)."""
+    K, affine, win, supp_node, src_ids, supp = ctx['K'], ctx['affine'], ctx['win'], ctx['supp_node'], ctx['src_ids'], ctx['supp']
+    kf_poses, kf_klds, kf_affs = ctx['kf_poses'], ctx['kf_klds'], ctx['kf_affs']
     det = lambda x: x.detach().clone()
     if win is None:                                                # a single keyframe without supporting frames: nothing to match
         return dict(kf_poses=torch.stack([det(p) for p in kf_poses]), klds=[det(k) for k in kf_klds],
                     affs=torch.stack([det(a) for a in kf_affs]) if affine else None, supp_poses=[[] for _ in range(K)],
                     supp_affs=[[] for _ in range(K)] if affine else None, losses=[torch.zeros((), device=kf_poses[0].device)], stopped=-1)
-    if gn:
-        n = win.run_gn(0, min(num_iters, gn['max_iters']), irls_eps=gn['irls_eps'], conv_tol=gn['conv_tol'])
-        if gn['polish_max'] > 0 and num_iters > gn['max_iters'] // 2:      # (a short budget -- the supplementary mapping -- gets no polish)
-            n += win.run_gn(0, gn['polish_max'], irls_eps=gn['polish_eps'], conv_tol=gn['polish_tol'])
-        poses, affs, losses = win.node_poses(), win.node_affines(), win.gn_losses()
-        stopped, extra = n, dict(gn=win.gn_stats())
-        if gn.get('profile', False):                               # (phase time stamps of the last update kernel: a read-back, diagnostics only)
-            extra['gn_profile'] = win.gn_profile()
-    else:
-        win.run(0, num_iters)
-        poses, affs, losses = win.node_poses(), win.node_affines(), win.losses()
-        stopped, extra = (win.iterations() - 1 if win.converged() else -1), {}
+    poses, affs, losses = win.node_poses(), win.node_affines(), win.gn_losses()
+    extra = dict(gn=win.gn_stats())
+    if ctx['gn'].get('profile', False):                            # (phase time stamps of the last update kernel: a read-back, diagnostics only)
+        extra['gn_profile'] = win.gn_profile()
+    wk = win.klds()
+    klds = [det(k) for k in kf_klds]
+    for b, s in enumerate(src_ids):
+        klds[s] = wk[b]
+    return dict(kf_poses=poses[:K], klds=klds, affs=affs[:K] if affine else None,
+                supp_poses=[[poses[supp_node[(k, j)]] for j in range(len(supp[k]))] for k in range(K)],
+                supp_affs=[[affs[supp_node[(k, j)]] for j in range(len(supp[k]))] for k in range(K)] if affine else None,
+                losses=list(losses.unbind(0)), stopped=ctx['n'], **extra)
+
+
+def _map_window_fused(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode='map'):
+    K = len(kfs)
+    win, supp_node, src_ids = _build_map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode, None)
+    det = lambda x: x.detach().clone()
+    if win is None:                                                # a single keyframe without supporting frames: nothing to match
+        return dict(kf_poses=torch.stack([det(p) for p in kf_poses]), klds=[det(k) for k in kf_klds],
+                    affs=torch.stack([det(a) for a in kf_affs]) if affine else None, supp_poses=[[] for _ in range(K)],
+                    supp_affs=[[] for _ in range(K)] if affine else None, losses=[torch.zeros((), device=kf_poses[0].device)], stopped=-1)
+    win.run(0, num_iters)
+    poses, affs, losses = win.node_poses(), win.node_affines(), win.losses()
+    stopped, extra = (win.iterations() - 1 if win.converged() else -1), {}
     wk = win.klds()
     klds = [det(k) for k in kf_klds]
     for b, s in enumerate(src_ids):

@@ -194,15 +194,31 @@ class MonoVO:
                 self.tracker.update_keyframe(self.kf_klds[-1])
             self.update_track_pose(mode)
             return
+        ctx = self._mapping_begin(num_iters, mode, K, rows, supp, lr_pose)
+        args, kw = self._map_args(ctx)
+        _sync(); t0 = time.perf_counter()
+        out = map_window(*args, optimiser="gn" if self.engine == "gn" else "adam", **kw)
+        _sync(); self.secs['supp_mapping' if mode == 'supp' else 'mapping'] += time.perf_counter() - t0
+        self._mapping_end(ctx, out)
+
+    def _mapping_begin(self, num_iters, mode, K, rows, supp, lr_pose):
+        """The part of ``mapping`` before the window is optimised (the window itself: ``map_window`` or, in parts,
+        ``loops.map_window_gn_begin`` / ``_phases`` / ``_end``)."""
         # (whatever follows moves poses / depths the persistent window holds: a scheduled mapping leaves its GRAPH as it is -- the window is
         #  refreshed with the mapped values below; anything else drops it)
-        keep_mapper = self.supp_mapper if mode == 'map' and c['persistent_supp'] else None
+        keep_mapper = self.supp_mapper if mode == 'map' and self.c['persistent_supp'] else None
         self.supp_mapper = None
-        _sync(); t0 = time.perf_counter()
-        out = map_window(self.kfs, self.kf_poses, self.kf_klds, self.kf_affs if self.affine else None, supp, num_iters, lr_pose=lr_pose,
-                         window_size=c['window_size'], initialised=self.initialised, optimiser="gn" if self.engine == "gn" else "adam", mode=mode,
-                         rel_tol=c['map_rel_tol'])
-        _sync(); self.secs['supp_mapping' if mode == 'supp' else 'mapping'] += time.perf_counter() - t0
+        return dict(mode=mode, K=K, rows=rows, supp=supp, lr_pose=lr_pose, num_iters=num_iters, keep_mapper=keep_mapper)
+
+    def _map_args(self, ctx):
+        """(positional, keyword) arguments of the mapping's window (``map_window`` / ``loops.map_window_gn_begin``)."""
+        c = self.c
+        return ((self.kfs, self.kf_poses, self.kf_klds, self.kf_affs if self.affine else None, ctx['supp'], ctx['num_iters']),
+                dict(lr_pose=ctx['lr_pose'], window_size=c['window_size'], initialised=self.initialised, mode=ctx['mode'], rel_tol=c['map_rel_tol']))
+
+    def _mapping_end(self, ctx, out):
+        """The write-back of ``mapping`` once the window ran (``out``: what ``map_window`` returns)."""
+        mode, K, rows, keep_mapper = ctx['mode'], ctx['K'], ctx['rows'], ctx['keep_mapper']
         self.kf_poses = [p.clone() for p in out['kf_poses']]
         self.kf_klds = [k.clone() for k in out['klds']]
         if self.affine:
@@ -287,10 +303,31 @@ class MonoVO:
     def _step_native(self, i):
         """``step`` with the per-frame stages in ONE foreign call (``sp_chain_step``): tracking, the supplementary mapping against the two
         running supporting frames and the keyframe criterion, all on the device.  What stays in Python is what happens once per keyframe:
-        building the windows, the scheduled mapping, the new keyframe."""
+        building the windows, the scheduled mapping, the new keyframe.  In parts (``sequence_batch.run_sequences`` drives S sequences
+        through them in lockstep): ``_native_begin`` -> the call -> ``_native_end``, then the scheduled mapping when ``_mapping_due``,
+        the criterion-only call (``_native_criterion_job``) when the first call had none, and ``_native_keyframe``."""
+        c = self.c
+        _sync(); t0 = time.perf_counter()
+        job = self._native_begin(i)
+        _, _, crit = self.chain.run(**job)
+        self.secs['track'] += time.perf_counter() - t0
+        self._native_end(i)
+        if self._mapping_due():
+            self.mapping(c['map_steps'], mode='map')
+            self._mapping_done()
+        assert self.current_ts == i
+        t0 = time.perf_counter()
+        if crit is None:
+            _, _, crit = self.chain.run(**self._native_criterion_job())
+        new_kf = self._native_keyframe(i, crit)
+        self.secs['keyframe'] += time.perf_counter() - t0
+        return new_kf, crit
+
+    def _native_begin(self, i):
+        """Everything of a native step before the call: windows built / bound, the running frames' slots.  Returns the ``ChainStep.run``
+        keywords (``stages`` included)."""
         from .chain import CRITERION, SUPP, TRACK, ChainStep
         c, f = self.c, self.frames[i]
-        _sync(); t0 = time.perf_counter()
         if self.chain is None:
             H, W = f.image.shape[-2:]
             self.chain = ChainStep(len(self.frames), H, W, c['track_levels'][1], self.dev)
@@ -328,45 +365,65 @@ class MonoVO:
                 m.frames = [prev.frame, f]
         map_now = self.mapping_scheduled                                  # (mapping(mode='map') may move the keyframe before the criterion looks at it)
         stages = TRACK | (SUPP if native_supp else 0) | (CRITERION if (native_supp or not want_supp) and not map_now else 0)
-        _, _, crit = ch.run(stages, i=i, image=f.image, start_pose=self.current_track, start_aff=self.current_aff if self.affine else None,
-                            prev=(prev.ts if prev is not None else i) if native_supp else None, supp_images=images, supp_one=prev is None)
-        self.secs['track'] += time.perf_counter() - t0
-        # ---- the bookkeeping of track_frame (:323-449) ...
+        return dict(stages=stages, i=i, image=f.image, start_pose=self.current_track, start_aff=self.current_aff if self.affine else None,
+                    prev=(prev.ts if prev is not None else i) if native_supp else None, supp_images=images, supp_one=prev is None)
+
+    def _native_end(self, i):
+        """The bookkeeping of a native step after the call: of track_frame (:323-449) and of mapping(mode='supp') (:1038-1042)."""
+        c, ch, f = self.c, self.chain, self.frames[i]
         self.current_track = ch.hist_pose[i]
         if self.affine:
             self.current_aff = ch.hist_aff[i]
         self.current_ts = i
         self.tracked.append(_Supp(f, self.current_track, self.current_aff, i))
         self.track.append(self.current_track)
-        # ---- ... and of mapping(mode='supp') (:1038-1042)
-        if native_supp:
+        want_supp = c['continual_steps'] > 0
+        if want_supp and c['persistent_supp']:
             self.tracked_poses_to_supp()
             self.kf_klds[-1] = self.supp_mapper.win.kld.clone()
             self.n_map['supp'] += 1
             self.update_track_pose('supp')
         elif want_supp:
             self.mapping(c['continual_steps'], mode='supp')
-        if self.mapping_scheduled and len(self.curr_supp) >= 2:
-            self.mapping(c['map_steps'], mode='map')
-            self.mapping_scheduled = False
-            self.reset_tracked_poses()
-            self.reset_running_supp_kfs()
-        assert self.current_ts == i
-        t0 = time.perf_counter()
-        if crit is None:
-            if ch.tracker is not self.tracker:                            # (cannot happen: mapping keeps the tracker; guards the binding)
-                ch.bind_tracker(self.tracker, self.kfs[-1], self.affine)
-            _, _, crit = ch.run(CRITERION, pose=self.current_track)
+
+    def _mapping_due(self):
+        return self.mapping_scheduled and len(self.curr_supp) >= 2
+
+    def _mapping_done(self):
+        self.mapping_scheduled = False
+        self.reset_tracked_poses()
+        self.reset_running_supp_kfs()
+
+    def _map_begin_scheduled(self):
+        """``mapping(map_steps, mode='map')`` up to its window: (mapping context, its (positional, keyword) window arguments)."""
+        c = self.c
+        self.tracked_poses_to_supp()
+        K = len(self.kfs)
+        rows = [(self.curr_supp if k == K - 1 else self.supp_opt[k]) if self.initialised else [] for k in range(K)]
+        supp = [[(s.frame, s.pose, s.aff) for s in row] for row in rows]
+        ctx = self._mapping_begin(c['map_steps'], 'map', K, rows, supp, c['map_lr_pose'])
+        return ctx, self._map_args(ctx)
+
+    def _native_criterion_job(self):
+        """The ``ChainStep.run`` keywords of the criterion-only call (the step's call had none: a scheduled mapping was due)."""
+        from .chain import CRITERION
+        ch = self.chain
+        if ch.tracker is not self.tracker:                            # (cannot happen: mapping keeps the tracker; guards the binding)
+            ch.bind_tracker(self.tracker, self.kfs[-1], self.affine)
+        return dict(stages=CRITERION, pose=self.current_track)
+
+    def _native_keyframe(self, i, crit):
+        """Keyframe decision on the criterion's values and, for a new keyframe, its creation.  Returns the decision."""
+        c = self.c
         new_kf = crit[0] < c['depth_validity_ratio'] or crit[2] > c['translation_thresh']
         if new_kf:
             self.flush_tracked_poses_to_supp()
-            self.init_keyframe(i, (ch.depth, crit))
+            self.init_keyframe(i, (self.chain.depth, crit))
             self.reset_tracked_poses()
             self.reset_running_supp_kfs()
             _sync()
             self.mapping_scheduled = True
-        self.secs['keyframe'] += time.perf_counter() - t0
-        return new_kf, crit
+        return new_kf
 
     def keyframe_stage(self, i):
         """The tail of one pass of the driver loop (odometery.py:1056-1075): keyframe decision, creation, what it schedules.  Returns
