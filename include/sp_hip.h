@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 16
+#define SP_ABI_VERSION 17
 
 #define SP_EINVAL (-1)   /* bad argument (null pointer, non-positive size, ...) */
 #define SP_ELIMIT (-2)   /* size outside what the kernels support (H or W > 32767, N > 65535, ...) */
@@ -776,24 +776,13 @@ int sp_kf_criterion_ws(const float* depth, int n, float thresh, const float* pos
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
- * ONE CALL PER FRAME of the monocular-odometry chain (ABI 14; BASELINE configs[2] as a sequence).  The reference's driver loop
- * (odometery/odometery.py:1018-1075) does, for every frame that is not a keyframe: track_frame against the latest keyframe (:323-449),
- * mapping(mode='supp') -- the latest keyframe's depths against its two running supporting frames (:1038-1042) -- and is_kf (:986-1016:
- * the keyframe's depth rendered in the tracked pose, validity ratio / scaled translation).  Behind Gauss-Newton windows that are built
- * once per keyframe (sp_window_gn_run) the interpreter between those steps -- three dozen small tensor operations, node arrays read back
- * and re-uploaded, a host synchronisation per step -- costs more than the kernels.  sp_chain_step runs the stages named in `stages` with
- * ALL state on the device -- poses, affine pairs and depths are read from and written to device buffers the caller names -- and the only
- * values that reach the host are the windows' 16-float LM states (the polls of sp_window_gn_run) and the 4 floats of the criterion.
- *   SP_CHAIN_TRACK     : pyramid of `image` (sp_blur_decimate) packed (sp_pack_rgb) into the tracker's target buffers; the target node's
- *                        pose / affine pair <- track_target.pose / .aff, tangents and moments cleared, edges recomposed; fresh LM state; the
- *                        phases of `track`; out_pose <- renormalise_se3(the node's pose) (lie/lie_algebra.py:41-47), out_aff <- its pair
- *   SP_CHAIN_SUPP      : (supp_images bit 0) the packed levels of supp_target[1] move to supp_target[0]; (bit 1) the tracker's packed levels
- *                        are copied into supp_target[1]; both nodes <- their pose / aff; fresh LM state; the phases of `supp`; then
- *                        kld_n floats kld_src -> kld_dst (the mapped depths into the tracker's block)
- *   SP_CHAIN_CRITERION : rel <- inv(out_pose) kf_pose; sp_depth_splat of the keyframe under rel into depth_out; sp_kf_criterion_ws(depth_out,
- *                        out_pose, kf_pose) -> crit (device) -> crit_host (pinned), and this stream is synchronised
- * Stages run in that order on `stream`.  The struct lives in HOST memory; iterations the phases took are written back to track_iters /
- * supp_iters.  Returns 0, SP_EINVAL, or what the stage's own entry point returned.
+ * ONE CALL PER FRAME INDEX of the monocular-odometry chain, for S sequences in lockstep (ABI 14; lockstep ABI 16; one path ABI 17; BASELINE
+ * configs[2] as a sequence).  The reference's driver loop (odometery/odometery.py:1018-1075) does, for every frame that is not a keyframe:
+ * track_frame against the latest keyframe (:323-449), mapping(mode='supp') -- the latest keyframe's depths against its two running
+ * supporting frames (:1038-1042) -- and is_kf (:986-1016: the keyframe's depth rendered in the tracked pose, validity ratio / scaled
+ * translation).  Behind Gauss-Newton windows that are built once per keyframe (sp_window_gn_run) the interpreter between those steps -- three
+ * dozen small tensor operations, node arrays read back and re-uploaded, a host synchronisation per step -- costs more than the kernels.
+ * sp_chain_step_multi (below) runs a frame's stages with ALL state on the device; its argument record, one SpChainStep per sequence:
  * ---------------------------------------------------------------------------------------------------- */
 #define SP_CHAIN_LEVELS 4
 #define SP_CHAIN_PHASES 6
@@ -815,7 +804,7 @@ typedef struct SpChainWindow {         /* a built window with its Gauss-Newton s
     float lm_up, lm_down, lm_min;
     int32_t check_first;               /* > 0: every phase looks at the state after this many iterations for the first time (a window that
                                         * usually converges at once -- the supplementary mapping -- should not run check_every iterations blind) */
-    float* state_host;                 /* host, pinned: 16 floats */
+    float* state_host;                 /* host: 16 floats, filled by the call */
 } SpChainWindow;                       /* 680 bytes */
 typedef struct SpChainTarget {         /* a target node whose frame the step replaces */
     float* packed[SP_CHAIN_LEVELS];    /* the node's packed (H_l, W_l, 3) image at pyramid level l, where the window has that level */
@@ -847,30 +836,43 @@ typedef struct SpChainStep {
     float* rel_pose;                   /* 16 floats scratch */
     float* crit;                       /* 4 floats */
     uint32_t* crit_ws;                 /* sp_kf_criterion_ws_words() uint32 of scratch */
-    float* crit_host;                  /* host, pinned: 4 floats */
+    float* crit_host;                  /* host: 4 floats, filled by the call */
     float valid_thresh;
     int32_t track_iters, supp_iters;   /* out (host) */
     int32_t pad_;
 } SpChainStep;
-int sp_chain_step(SpChainStep* step, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
- * (ABI 16) S odometry sequences in LOCKSTEP: sp_chain_step on n_steps records at once (reference: odometery/odometery.py:1018-1075, the
- * driver loop of one sequence per record).  Every stage covers all records with the same launches -- the frames' pyramids one launch per
+ * sp_chain_step_multi: the stages named in `stages` for n_steps records at once, one record per sequence (n_steps = 1: one sequence), with
+ * ALL state on the device -- poses, affine pairs and depths are read from and written to device buffers the records name -- and the only
+ * values that reach the host are the windows' 16-float LM states (the phase loop's polls and the final states) and the 4 criterion floats.
+ *   SP_CHAIN_TRACK     : pyramid of `image` packed into the tracker's target buffers (sp_blur_decimate / sp_pack_rgb's arithmetic); the
+ *                        target node's pose / affine pair <- track_target.pose / .aff, tangents and moments cleared, edges recomposed; fresh
+ *                        LM state; the phases of `track`; out_pose <- renormalise_se3(the node's pose) (lie/lie_algebra.py:41-47), out_aff
+ *                        <- its pair
+ *   SP_CHAIN_SUPP      : (supp_images bit 0) the packed levels of supp_target[1] move to supp_target[0]; (bit 1) the tracker's packed levels
+ *                        are copied into supp_target[1]; both nodes <- their pose / aff; fresh LM state; the phases of `supp`; then
+ *                        kld_n floats kld_src -> kld_dst (the mapped depths into the tracker's block)
+ *   SP_CHAIN_CRITERION : rel <- inv(out_pose) kf_pose; sp_depth_splat of the keyframe under rel into depth_out; sp_kf_criterion_ws(depth_out,
+ *                        out_pose, kf_pose) -> crit (device)
+ * Stages run in that order on `stream`.  Every stage covers all records with the same launches -- the frames' pyramids one launch per
  * level, node overwrites / edge composition / LM resets one launch each, the phase loop the round body of sp_window_gn_run_multi (cost pass
- * over all work lists, per-edge reduce, Schur terms, update: window = blockIdx.z), the criterion's splat and select passes with the record
- * on blockIdx.y -- so the launches per call do not grow with n_steps.  A phase ends once EVERY window froze (st[6]) or at its max_iters;
- * the polls are run_phases' (the first after check_first iterations when conv_tol > 0, none after a phase's last iteration).  A frozen
- * window is inert, so per record the result is BITWISE sp_chain_step's on that record alone: out_pose, out_aff, the supp window's
- * log-depths and nodes, kld_dst, crit_host, track_iters, supp_iters, and the 16-float states left in each window's state_host.
+ * over all work lists, per-edge reduce, Schur terms, update: window = blockIdx.z), the criterion's splat and select passes with the record on
+ * blockIdx.y -- so the launches per call do not grow with n_steps.  The polls are those of sp_window_gn_run with the ones that decide nothing
+ * left out: the first after check_first iterations when conv_tol > 0, then every check_every, none after a phase's last iteration; a phase
+ * ends once EVERY window froze (st[6]) or at its max_iters.  A frozen window is inert, so per record the result is BITWISE that of the call
+ * on that record alone: out_pose, out_aff, the supp window's log-depths and nodes, kld_dst, crit_host, track_iters, supp_iters, and the
+ * 16-float states left in each window's state_host.
  * The call is HOMOGENEOUS: every record has the same stages, H, W, n_levels, valid_thresh, and per present stage the same phase list
  * (level, max_iters, irls_eps, conv_tol), check_every, check_first, flags and LM constants (lam0, lm_up, lm_down, lm_min); otherwise
  * -- or for n_steps outside 1 .. 65535 or a null pointer -- SP_EINVAL before anything is launched.
  *   args_dev    : device scratch of n_steps * sp_chain_multi_bytes() bytes (the argument records, one host-to-device copy per call)
- *   states_dev  : device scratch of 36 * n_steps floats; states_host: pinned host memory of the same size -- [16 n] the tracker windows'
- *                 states, [16 n] the supp windows', [4 n] the criteria (one gathered device-to-host copy and one synchronisation at the end,
- *                 plus the phase loop's polls)
- * The records live in HOST memory as for sp_chain_step. */
+ *   states_dev  : device scratch of 36 * n_steps floats, what the device gathers the results into; states_host: pinned host memory of the
+ *                 same size that they are copied to -- [16 n] the tracker windows' states, [16 n] the supp windows', [4 n] the criteria
+ *                 (one device-to-host copy and one synchronisation of `stream` at the end, plus the phase loop's polls)
+ * The records stay in HOST memory.  After the call's one synchronisation the host fills each record's track.state_host / supp.state_host
+ * (16 floats each), crit_host (4 floats) and track_iters / supp_iters from states_host.  Returns 0, SP_EINVAL / SP_ELIMIT (before anything
+ * is launched), a hipError_t of a failed launch or copy, or the -(1000 + hipError_t) of a phase round (as sp_window_gn_run_multi). */
 int sp_chain_multi_bytes(void);
 int sp_chain_step_multi(SpChainStep* steps, int n_steps, void* args_dev, float* states_dev, float* states_host, void* stream);
 

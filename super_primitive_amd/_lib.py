@@ -69,7 +69,6 @@ SIGNATURES = {
     "sp_depth_accumulate": [P, P, P, P, P, P, I, I, I, I, P, P],
     "sp_depth_average_finish": [P, I, I, P, P, P],
     "sp_kf_criterion": [P, I, F, P, P, P, P],
-    "sp_chain_step": [P, P],
     "sp_chain_multi_bytes": [],
     "sp_chain_step_multi": [P, I, P, P, P, P],
     "sp_kf_criterion_ws_words": [],
@@ -83,7 +82,7 @@ SIGNATURES = {
     "sp_kth_mask_pixel": [P, P, I, I, I, P, P, P],
 }
 
-SP_ABI_VERSION = 16
+SP_ABI_VERSION = 17
 SP_GRAD_PARTIAL_FLOATS = 16
 SP_GN_PARTIAL_FLOATS = 32
 SP_GNA_PARTIAL_FLOATS = 48

@@ -1,14 +1,13 @@
-"""One foreign call per FRAME of the odometry chain (``sp_chain_step``, include/sp_hip.h): the host side that binds the per-keyframe
+"""One foreign call per FRAME of the odometry chain (``sp_chain_step_multi``, include/sp_hip.h): the host side that binds the per-keyframe
 Gauss-Newton windows of ``loops.GnTracker`` / ``loops.GnSuppMapper`` to the call's argument record.
 
 The reference's driver loop (``odometery/odometery.py:1018-1075``) runs, for a frame that is not a keyframe, ``track_frame`` (:323-449),
 ``mapping(mode='supp')`` (:1038-1042) and ``is_kf`` (:986-1016).  ``odometery/sequence.py`` mirrors that loop step by step in Python;
 with the windows built once per keyframe the interpreter BETWEEN the launches is most of a frame (0.76 ms of kernels
 in 2.7 ms).  ``ChainStep`` keeps poses, affine pairs and depths on the device and hands the three stages to the library in one call; the
-arithmetic is that of ``GnTracker.track`` / ``GnSuppMapper.__call__`` / ``MonoVO.is_kf`` (tests/test_gpu_sequence.py compares the two)."""
+arithmetic is that of ``GnTracker.track`` / ``GnSuppMapper.__call__`` / ``MonoVO.is_kf`` (tests/test_gpu_sequence.py compares the two).
+One sequence is a call on one record (``ChainStep.run``); ``ChainStepBatch`` makes the same call for the records of S sequences at once."""
 from __future__ import annotations
-
-import ctypes
 
 import torch
 
@@ -49,8 +48,9 @@ def _bind_window(cw, win, phases, check_first=0):
 
 
 class ChainStep:
-    """The argument record of ``sp_chain_step`` for one sequence: frame-sized scratch, the per-frame history of tracked poses and
-    affine pairs (device), and the windows of the latest keyframe once bound."""
+    """The argument record of ``sp_chain_step_multi`` for one sequence: frame-sized scratch, the per-frame history of tracked poses and
+    affine pairs (device), and the windows of the latest keyframe once bound.  ``run`` calls with this record alone, through a
+    ``ChainStepBatch`` of its own (sequences run in parallel host threads share no scratch)."""
 
     def __init__(self, n_frames, H, W, n_levels, device):
         self.lib = _lib.load()
@@ -76,6 +76,7 @@ class ChainStep:
         st.valid_thresh = 1e-6
         self.tracker = self.mapper = None
         self._keep = {}
+        self._batch = ChainStepBatch(device)
 
     # ---- the windows of the latest keyframe ---------------------------------------------------------------------------------------------
     def bind_tracker(self, tracker, kf, affine):
@@ -124,11 +125,9 @@ class ChainStep:
         lands in ``hist_pose[i]`` / ``hist_aff[i]``.  SUPP: ``prev`` = history index of the older running supporting frame (the newer one
         is ``i``; ``supp_one``: there is only frame ``i`` -- ``prev`` = ``i``, the first slot's edge carries no weight).  CRITERION without TRACK: ``pose`` = the (4,4) device tensor to judge.  Returns (tracker iterations, mapper iterations,
         criterion [validity ratio, scale, translation difference, rotation degrees] | None)."""
-        keep = self._prepare(stages, i, image, start_pose, start_aff, prev, supp_images, supp_one, pose)
-        rc = self.lib.sp_chain_step(ctypes.byref(self.st), _lib.stream_ptr())
-        _lib.check(rc, "sp_chain_step")
-        del keep
-        return self._finish(stages)
+        kw = dict(stages=stages, i=i, image=image, start_pose=start_pose, start_aff=start_aff, prev=prev, supp_images=supp_images,
+                  supp_one=supp_one, pose=pose)
+        return self._batch.run([(self, kw)])[0]
 
     def _prepare(self, stages, i=None, image=None, start_pose=None, start_aff=None, prev=None, supp_images=0, supp_one=False, pose=None):
         """The argument record of one frame (``run``'s arguments); returns the tensors it points into that must outlive the call."""
@@ -180,8 +179,9 @@ class ChainStep:
 
 class ChainStepBatch:
     """``sp_chain_step_multi``: ONE call for the same stages of S sequences (one ``ChainStep`` each) -- every launch of the chain covers
-    all S, so the launches per frame index do not grow with S.  Per sequence the result is bitwise that of ``ChainStep.run`` on it alone
-    (tests/test_gpu_sequence_batch.py).  Owns the device argument area and the pinned states of the call, grown to the largest S seen."""
+    all S, so the launches per frame index do not grow with S.  Per sequence the result is bitwise that of the call on it alone (S = 1,
+    ``ChainStep.run``; tests/test_gpu_sequence_batch.py).  Owns the device argument area and the pinned states of the call, grown to the
+    largest S seen."""
 
     def __init__(self, device):
         self.lib = _lib.load()

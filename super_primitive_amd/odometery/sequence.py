@@ -77,8 +77,8 @@ class MonoVO:
         self.tracker = None                   # (Gauss-Newton engine: one window per keyframe, re-used for every frame tracked against it)
         self.supp_mapper = None               # (... and one window per latest keyframe for the supplementary mapping after every frame)
         self.current_aff = torch.zeros(2, device=self.dev)
-        # engine 'gn': one foreign call per frame (sp_chain_step; odometery/chain.py) instead of the Python steps below -- same stages, same
-        # arithmetic, the state on the device.  ``native_step=False`` keeps the step-by-step path (the two are compared in tests/test_gpu_sequence.py)
+        # engine 'gn': one foreign call per frame (sp_chain_step_multi on this sequence's record; odometery/chain.py) instead of the Python
+        # steps below -- same stages, same arithmetic, the state on the device.  ``native_step=False`` keeps the step-by-step path (the two are compared in tests/test_gpu_sequence.py)
         self.chain = None
         self.native = bool(self.c['native_step']) and engine == "gn" and not self.c['motion_prior'] and self.dev.type == "cuda"
         self.add_kf(to_keyframe(0), pose0.clone(), kld0.clone(), 0, self.current_aff.clone())
@@ -301,8 +301,8 @@ class MonoVO:
         self.keyframe_stage(i)
 
     def _step_native(self, i):
-        """``step`` with the per-frame stages in ONE foreign call (``sp_chain_step``): tracking, the supplementary mapping against the two
-        running supporting frames and the keyframe criterion, all on the device.  What stays in Python is what happens once per keyframe:
+        """``step`` with the per-frame stages in ONE foreign call (``sp_chain_step_multi`` on this sequence's record): tracking, the
+        supplementary mapping against the two running supporting frames and the keyframe criterion, all on the device.  What stays in Python is what happens once per keyframe:
         building the windows, the scheduled mapping, the new keyframe.  In parts (``sequence_batch.run_sequences`` drives S sequences
         through them in lockstep): ``_native_begin`` -> the call -> ``_native_end``, then the scheduled mapping when ``_mapping_due``,
         the criterion-only call (``_native_criterion_job``) when the first call had none, and ``_native_keyframe``."""

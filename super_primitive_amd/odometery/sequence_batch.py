@@ -4,8 +4,8 @@ One sequence leaves the GPU nearly idle -- its frame is a chain of small depende
 walks the frame indices of S sequences together and, at every index, hands the per-frame stages of all sequences that can take them to
 ONE ``sp_chain_step_multi`` call per stage mask (``chain.ChainStepBatch``), and the scheduled mappings that fall on that index to
 ``PoseWindowBatch`` (one Gauss-Newton phase loop over all their windows).  Everything else -- sequences before their first mapping,
-window builds, keyframe creation -- runs per sequence exactly as ``MonoVO.step`` does.  Per sequence the results are bitwise those of
-``run_sequence`` on it alone (tests/test_gpu_sequence_batch.py)."""
+window builds, keyframe creation -- runs per sequence exactly as ``MonoVO.step`` does (whose native step is the same call on the sequence's
+one record).  Per sequence the results are bitwise those of ``run_sequence`` on it alone (tests/test_gpu_sequence_batch.py)."""
 from __future__ import annotations
 
 import time

@@ -53,7 +53,7 @@ class PoseWindow:
         edges:   list of (source index, target node, weight, zmin);
         levels:  (pyramid_min, pyramid_max) like ``config['aligment']`` (max exclusive);
         private_targets: target nodes whose images this window REPLACES in place (``set_target_image`` / ``copy_target_image`` / the slots of
-                 ``sp_chain_step``): they get buffers of their own.  None = all of them.  Every other target node at pyramid level 0 reads
+                 ``sp_chain_step_multi``): they get buffers of their own.  None = all of them.  Every other target node at pyramid level 0 reads
                  the packed image cached on the frame's tensor (``segment_table.packed_target``), shared by all windows the frame is part of;
         share_sources: keep / re-use the padded source samples of every source keyframe with its segment table (see below; the Gauss-Newton
                  windows of the odometry chain -- a keyframe is the source of a dozen windows while it lives).  Off, every window samples
@@ -371,7 +371,7 @@ class PoseWindow:
         return int(gn['state_host'][5]) - n0
 
     def _gn_host_state(self):
-        """The 16-float LM state on the host: the pinned copy ``run_gn`` / ``sp_chain_step`` left behind when nothing has moved the device's
+        """The 16-float LM state on the host: the pinned copy ``run_gn`` / ``sp_chain_step_multi`` left behind when nothing has moved the device's
         since (no read-back, no synchronisation), else a fresh copy."""
         gn = self._gn_state()
         if gn.get('host_stale', False) or not gn.get('host_seen', False):

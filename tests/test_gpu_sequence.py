@@ -430,9 +430,9 @@ def test_persistent_supplementary_mapping_window_equals_a_rebuilt_one():
 @pytest.mark.parametrize("cfg", [dict(), dict(affine_compensation=False), dict(continual_steps=0), dict(window_size=3, supp_every_n=2)],
                          ids=["reference extent", "no affine compensation", "no supplementary mapping", "window of 3"])
 def test_one_call_per_frame_gives_the_chain_of_the_python_steps(cfg):
-    """``sp_chain_step`` (include/sp_hip.h; odometery/chain.py) -- tracking, the supplementary mapping against the two
-    running supporting frames and the keyframe criterion of one frame as ONE foreign call with the state on the device -- against the
-    step-by-step Python driver (``native_step=False``: ``GnTracker.track`` -> ``GnSuppMapper`` -> ``is_kf``, odometery/odometery.py:1018-1075):
+    """``sp_chain_step_multi`` on one record (include/sp_hip.h; odometery/chain.py) -- tracking, the supplementary
+    mapping against the two running supporting frames and the keyframe criterion of one frame as ONE foreign call with the state on the
+    device -- against the step-by-step Python driver (``native_step=False``: ``GnTracker.track`` -> ``GnSuppMapper`` -> ``is_kf``, odometery/odometery.py:1018-1075):
     the same launches in the same order on the same data, so the same chain -- keyframe decisions, supporting frames, iteration for
     iteration -- with poses and depths equal to the round-off of inv(T) T' (one kernel here, three torch launches there)."""
     from super_primitive_amd.odometery.sequence import run_sequence

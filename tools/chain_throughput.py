@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""Config 3 as THROUGHPUT: S independent sequences through the one-call-per-frame chain (MonoVO, engine 'gn', sp_chain_step), each on its own
-HIP stream and host thread.  One chain is bound by the latency of its small dependent launches (~5 % of the chip is busy), and
-the foreign call releases the interpreter lock, so sequences side by side overlap; what does NOT overlap is the per-keyframe Python (window builds,
-the scheduled mapping's bookkeeping).   python tools/chain_throughput.py [n_frames] [S ...]
+"""Config 3 as THROUGHPUT: S independent sequences through the one-call-per-frame chain (MonoVO, engine 'gn', sp_chain_step_multi on the
+sequence's one record), each on its own HIP stream and host thread.  One chain is bound by the latency of its small dependent launches
+(~5 % of the chip is busy), and the foreign call releases the interpreter lock, so sequences side by side overlap; what
+does NOT overlap is the per-keyframe Python (window builds, the scheduled mapping's bookkeeping).   python tools/chain_throughput.py [n_frames] [S ...]
     python tools/chain_throughput.py --processes [n_frames] [S ...]     the same with one PROCESS per sequence (no interpreter lock between them)
     python tools/chain_throughput.py --lockstep [n_frames] [S ...]      the S sequences in LOCKSTEP in one thread (odometery.sequence_batch:
                                                                           one sp_chain_step_multi call per stage mask and frame index, the
