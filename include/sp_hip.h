@@ -348,6 +348,37 @@ int sp_pairs_gn_step(const SpPair* pairs, int n_pairs, int max_N, const float* s
  * by the caller (per pyramid level).  conv_tol <= 0 / done == NULL: exactly sp_pairs_gn_step / sp_pairs_cost. */
 int sp_pairs_cost_active(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
                          float* span_partials, float* seg_partials, const int32_t* done, void* stream);
+
+/* RUN DESCRIPTORS: the pixel words of a wave-span table (granule 64) rebuilt from one 32-byte record per 64-point group instead of
+ * read point by point (4 B per point of the cost pass's stream).  A group lies inside one chunk of one segment, its points in
+ * row-major order: its points form RUNS of consecutive pixels of one row, and with at most two runs (every segment at least 64
+ * pixels wide) lane l of the group decodes as
+ *     step = clamp(l + k, 0, 1)          (0 in run 0, 1 in run 1: k = 1 - s1, s1 = first lane of run 1, 64 without one)
+ *     col  = base[0] + l + step * d[0],   row = base[1] + step * d[1],   validity bit = bit l of valid
+ * (integer-valued floats, exact).  Lanes past the group's last nonzero word (the padding of a segment) continue the last run;
+ * they are invalid.  runs > 2: the formula does not hold for that group.  Record n_groups (one past the table) is written too, as
+ * that of an all-zero group: the cost pass prepares one trip past the end of a span. */
+typedef struct SpRunDesc {
+    uint32_t valid[2];           /* bit l of the 64-bit mask: bit 31 of the group's word l */
+    float d[2];                  /* run 1 relative to run 0: {c1 - s1 - c0, r1 - r0} ({0, 0} without run 1) */
+    float base[2];               /* {col, row} of lane 0 */
+    float k;                     /* 1 - s1 */
+    int32_t runs;                /* runs among the group's points (1 for an all-zero group) */
+} SpRunDesc;
+
+/* descriptors of the n_groups groups of pix[0 .. 64 n_groups) into desc[0 .. n_groups] (n_groups + 1 records); *n_general
+ * (device int32, zeroed by the caller) += number of groups with more than two runs.  Build it after the table's validity bits are
+ * final (sp_prepare_sample / sp_table_sample_source). */
+int sp_run_desc_build(const uint32_t* pix, int n_groups, SpRunDesc* desc, int32_t* n_general, void* stream);
+/* sp_pairs_cost / sp_pairs_cost_active on a wave-span depth table (mode 0 or 1 | SP_COST_WAVE_SPANS | SP_COST_DEPTH_TABLE) whose
+ * pixel words come from run descriptors instead of pix: pix_base = the flat pix array every pair's SpPair.pix points into (pair
+ * tables start at multiples of 64 points from it), desc = sp_run_desc_build of that array, without groups of more than two runs.
+ * Bitwise the same partials as sp_pairs_cost. */
+int sp_pairs_cost_rd(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
+                     float* span_partials, float* seg_partials, const uint32_t* pix_base, const SpRunDesc* desc, void* stream);
+int sp_pairs_cost_rd_active(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
+                            float* span_partials, float* seg_partials, const int32_t* done, const uint32_t* pix_base,
+                            const SpRunDesc* desc, void* stream);
 int sp_pairs_gn_step_conv(const SpPair* pairs, int n_pairs, int max_N, const float* span_partials, const float* seg_partials,
                           float lm_up, float lm_down, float lm_min, float* lm_state, float* backup, float* costs, float conv_tol,
                           int32_t* done, void* stream);

@@ -33,6 +33,9 @@ SIGNATURES = {
     "sp_pairs_adam_step": [P, I, I, P, P, F, F, F, P, P, P],
     "sp_pairs_gn_step": [P, I, I, P, P, F, F, F, P, P, P, P],
     "sp_pairs_cost_active": [P, P, P, I, I, F, P, P, P, P],
+    "sp_run_desc_build": [P, I, P, P, P],
+    "sp_pairs_cost_rd": [P, P, P, I, I, F, P, P, P, P, P],
+    "sp_pairs_cost_rd_active": [P, P, P, I, I, F, P, P, P, P, P, P],
     "sp_pairs_gn_step_conv": [P, I, I, P, P, F, F, F, P, P, P, F, P, P],
     "sp_prepare_count": [P, I, I, I, P],
     "sp_prepare_count_boxed": [P, I, I, I, P],

@@ -363,11 +363,59 @@ struct Pending2 {          // Pending, with the x/y quantities as register pairs
 };
 
 // prepare() on pairs: same operations in the same order per component (sp_device.h backproject / warp_point)
+__device__ __forceinline__ void prepare2_at(const PairConsts& k, f32x2 colrow, bool src_ok, float d, const f32x4 s, Pending2& p);
+
 template <bool DT = false>
 __device__ __forceinline__ void prepare2(const TileCtx& c, const PairConsts& k, float shift, uint32_t pw, const f32x4 s, Pending2& p) {
     const f32x2 colrow{(float)(pw & 0xffffu), (float)((pw >> 16) & 0x7fffu)};
     const bool src_ok = (int32_t)pw < 0;
     const float d = DT ? s.w * shift : fast_exp(s.w + shift);
+    prepare2_at(k, colrow, src_ok, d, s, p);
+}
+
+// RUN DESCRIPTORS (include/sp_hip.h SpRunDesc): the pixel of lane l of a 64-point group from the group's wave-uniform record (scalar
+// loads) instead of its pix word -- an add with clamp, a packed fma and a packed add, exact on these integer values, in place of
+// and / bfe / two conversions, and 4 B per point less of the stream
+typedef const SpRunDesc __attribute__((address_space(4)))* cptr_rd;
+__device__ __forceinline__ SpRunDesc rd_load(cptr_rd p) {         // (field by field: scalar loads, merged into one s_load_dwordx8)
+    SpRunDesc r;
+    r.valid[0] = p->valid[0]; r.valid[1] = p->valid[1];
+    r.d[0] = p->d[0]; r.d[1] = p->d[1];
+    r.base[0] = p->base[0]; r.base[1] = p->base[1];
+    r.k = p->k; r.runs = p->runs;
+    return r;
+}
+__device__ __forceinline__ f32x2 rd_colrow(const SpRunDesc& r, f32x2 lane2) {
+    const float step = __builtin_amdgcn_fmed3f(lane2.x + r.k, 0.f, 1.f);           // 0 in run 0, 1 in run 1
+    return pfma(step, f32x2{r.d[0], r.d[1]}, lane2) + f32x2{r.base[0], r.base[1]};
+}
+// ... and its validity bit: the depth of a point whose bit is clear becomes 0, which fails `d > 1e-7` -- one v_cndmask with the mask as
+// its scalar operand instead of the compare on the sign bit.  (An invalid point contributes exact zeros whatever its geometry: every
+// term it adds is multiplied by its zero mask / zinv.)
+__device__ __forceinline__ float rd_depth(const SpRunDesc& r, float d) {
+    const uint64_t m = ((uint64_t)r.valid[1] << 32) | r.valid[0];
+    float o;
+    asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(o) : "v"(d), "s"(m));
+    return o;
+}
+template <bool DT>
+__device__ __forceinline__ void prepare2_rd(const PairConsts& k, float shift, const SpRunDesc& r, f32x2 lane2, const f32x4 s, Pending2& p) {
+    const f32x2 colrow = rd_colrow(r, lane2);
+    const float d = rd_depth(r, DT ? s.w * shift : fast_exp(s.w + shift));
+    prepare2_at(k, colrow, true, d, s, p);
+}
+// mode 0's prepare() on a run descriptor
+template <bool DT>
+__device__ __forceinline__ void prepare_rd(const TileCtx& c, float shift, float ifx, float ify, const SpRunDesc& r, f32x2 lane2, const f32x4 s,
+                                           Pending& p) {
+    const f32x2 colrow = rd_colrow(r, lane2);
+    const float d = rd_depth(r, DT ? s.w * shift : fast_exp(s.w + shift));
+    float x, y;
+    backproject(colrow.x, colrow.y, d, c.Ks, ifx, ify, x, y);
+    prepare_xyz(c, x, y, d, true, s.x, s.y, s.z, p);
+}
+
+__device__ __forceinline__ void prepare2_at(const PairConsts& k, f32x2 colrow, bool src_ok, float d, const f32x4 s, Pending2& p) {
     const f32x2 xy = pfma(colrow, k.ifxy, k.nKc) * d;          // ((col, row) - (cx, cy)) / (fx, fy) * d, the subtraction folded into the multiply
     // (round 6: the translation rides in the innermost multiply-add -- R d + t as one fma -- instead of a trailing add: one packed and one
     //  scalar instruction less per point; the sum is rounded in another order, a last-bit difference of q)
@@ -628,10 +676,12 @@ __device__ __forceinline__ uint32_t pix_from_colour_bits(const f32x4 s) {
 // W64 ("wave spans"): the span belongs to ONE WAVE -- trips of 64 points, segment records one per chunk, pair-level sums reduced
 // over the wave only -- so that the padding granule of the tables is 64 points instead of 256 (small ragged segments: 1200
 // SAM-like masks of ~280 pixels pad 40 % at 256 and 11 % at 64); the four waves of a workgroup work on four consecutive spans.
-template <int ABL, bool WT, bool AFF = false, bool W64 = false>
+// RD (W64 depth tables only): pixel words from the run descriptors of the pair's table (rd = its group 0) instead of pix
+template <int ABL, bool WT, bool AFF = false, bool W64 = false, bool RD = false>
 __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, const int4* __restrict__ chunks, int q0,
                                             int n_chunks, int total, float irls_eps, float* __restrict__ span_rec,
-                                            float* __restrict__ seg_partials, float* lds) {
+                                            float* __restrict__ seg_partials, float* lds, const SpRunDesc* rd = nullptr) {
+    static_assert(!RD || (W64 && ABL == 6 && !AFF), "run descriptors: wave spans on depth tables");
     constexpr int TRIP = W64 ? 64 : SP_BLOCK;
     constexpr bool DT = ABL == 6;            // depth tables (cursor_shift)
     constexpr int NV = AFF ? SP_GNA_PARTIAL_FLOATS : SP_GN_PARTIAL_FLOATS, NS = AFF ? SP_GNA_SEG_FLOATS : SP_GN_SEG_FLOATS;
@@ -681,6 +731,11 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
     const int n_iter = total / TRIP;
     uint32_t op = (W64 ? (threadIdx.x & 63u) : threadIdx.x) * 4u;
     constexpr int NT = 2;
+    // RD: the record of the group being prepared (the span's groups are consecutive; the trip past the end reads the next record,
+    // which exists: sp_run_desc_build writes one past the table), and {lane, 0} as a loop-invariant register pair
+    cptr_rd rg = (cptr_rd)rd + (start >> 6);
+    f32x2 lane2{(float)(threadIdx.x & 63u), 0.f};
+    if (RD) asm volatile("" : "+v"(lane2));
     // Two point slots used alternately (the loop is unrolled by two with the roles swapped), so that nothing has to be
     // copied at the back edge: point j lives in slot j % 2 from its geometry (bottom of trip j - 1) through its taps and
     // channel mixing (trip j) to its fold (middle of trip j + 1), and the slot is overwritten by point j + 2 only after
@@ -689,8 +744,11 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
     Slot S0, S1;
     {
         const f32x4 s = buf_load4<NT>(r_src, op * 4u);
-        const uint32_t pw = ABL == 5 ? pix_from_colour_bits(s) : (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
-        prepare2<DT>(c, kc, k.shift, pw, s, S0.p);
+        if (RD) prepare2_rd<DT>(kc, k.shift, rd_load(rg), lane2, s, S0.p);
+        else {
+            const uint32_t pw = ABL == 5 ? pix_from_colour_bits(s) : (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
+            prepare2<DT>(c, kc, k.shift, pw, s, S0.p);
+        }
         S0.last = cursor_advance<TRIP, DT>(k, S0.q);
     }
     S1.p = S0.p;                         // "point -1": finite values, zinv = zi = 0 and a zero Mix2 -> contributes exact zeros
@@ -701,8 +759,10 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
     auto trip = [&](Slot& a, Slot& b) {
         op += 4u * TRIP;
         asm volatile("" : "+v"(op));        // one induction register; the src4 offset is a shift of it
-        const uint32_t pw = ABL == 5 ? 0u : (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
+        const uint32_t pw = (ABL == 5 || RD) ? 0u : (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
         const f32x4 s = buf_load4<NT>(r_src, op * 4u);
+        SpRunDesc rn;
+        if (RD) { ++rg; rn = rd_load(rg); }
         f32x3 ta, tb, tc, td;
         if (ABL == 1) { ta = tb = tc = td = f32x3{a.p.srg.x, a.p.srg.y, a.p.sb}; }
         else if (ABL == 3) {
@@ -738,9 +798,11 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
         else finish_gn2<AFF>(kc, a.p, ta, tb, tc, td, m, A.cost, A.n, &ma, &AA);
         uint32_t pw_ = pw;
         f32x4 s_ = s;
-        asm volatile("" : "+v"(pw_), "+v"(s_));
+        if (RD) asm volatile("" : "+v"(s_));
+        else asm volatile("" : "+v"(pw_), "+v"(s_));
         if (ABL == 5) pw_ = pix_from_colour_bits(s_);
-        prepare2<DT>(c, kc, k.shift, pw_, s_, b.p);       // (the trip past the end reads zeros and is never used)
+        if (RD) prepare2_rd<DT>(kc, k.shift, rn, lane2, s_, b.p);
+        else prepare2<DT>(c, kc, k.shift, pw_, s_, b.p);       // (the trip past the end reads zeros and is never used)
         b.last = cursor_advance<TRIP, DT>(k, b.q);
     };
     int j = 0;
@@ -787,10 +849,11 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
 }
 
 // mode 0: the segment column is 13 (d/dkld)
-template <int ABL, bool WT, bool W64 = false>
+template <int ABL, bool WT, bool W64 = false, bool RD = false>
 __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr, const int4* __restrict__ chunks, int q0,
                                               int n_chunks, int total, float* __restrict__ span_rec,
-                                              float* __restrict__ seg_partials, float* lds) {
+                                              float* __restrict__ seg_partials, float* lds, const SpRunDesc* rd = nullptr) {
+    static_assert(!RD || (W64 && ABL == 6), "run descriptors: wave spans on depth tables");
     constexpr int TRIP = W64 ? 64 : SP_BLOCK;
     constexpr bool DT = ABL == 6;            // depth tables (cursor_shift)
     constexpr int NV = SP_GRAD_PARTIAL_FLOATS;
@@ -808,13 +871,19 @@ __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr
     const int n_iter = total / TRIP;
     uint32_t op = (W64 ? (threadIdx.x & 63u) : threadIdx.x) * 4u;
     constexpr int NT = 2;
+    cptr_rd rg = (cptr_rd)rd + (start >> 6);          // RD: as in run_span_gn
+    f32x2 lane2{(float)(threadIdx.x & 63u), 0.f};
+    if (RD) asm volatile("" : "+v"(lane2));
     // two point slots used alternately, the loop unrolled by two (see run_span_gn): nothing is copied at the back edge
     struct Slot { Pending p; int q; bool last; };
     Slot S0, S1;
     {
-        const uint32_t pw = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
         const f32x4 s = buf_load4<NT>(r_src, op * 4u);
-        prepare<DT>(c, k.shift, ifx, ify, pw, s, S0.p);
+        if (RD) prepare_rd<DT>(c, k.shift, ifx, ify, rd_load(rg), lane2, s, S0.p);
+        else {
+            const uint32_t pw = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
+            prepare<DT>(c, k.shift, ifx, ify, pw, s, S0.p);
+        }
         S0.last = cursor_advance<TRIP, DT>(k, S0.q);
     }
     S1.p = S0.p;                         // "point -1": contributes exact zeros
@@ -829,8 +898,10 @@ __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr
     auto trip = [&](Slot& a, Slot& b) {
         op += 4u * TRIP;
         asm volatile("" : "+v"(op));
-        const uint32_t pw = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
+        const uint32_t pw = RD ? 0u : (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
         const f32x4 s = buf_load4<NT>(r_src, op * 4u);
+        SpRunDesc rn;
+        if (RD) { ++rg; rn = rd_load(rg); }
         f32x3 ta, tb, tc, td;
         if (ABL == 1) { ta = tb = tc = td = f32x3{a.p.sr, a.p.sg, a.p.sb}; }
         else {
@@ -851,8 +922,10 @@ __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr
         else finish_grad(c, a.p, ta, tb, tc, td, m0, acc[0]);
         uint32_t pw_ = pw;
         f32x4 s_ = s;
-        asm volatile("" : "+v"(pw_), "+v"(s_));
-        prepare<DT>(c, k.shift, ifx, ify, pw_, s_, b.p);
+        if (RD) asm volatile("" : "+v"(s_));
+        else asm volatile("" : "+v"(pw_), "+v"(s_));
+        if (RD) prepare_rd<DT>(c, k.shift, ifx, ify, rn, lane2, s_, b.p);
+        else prepare<DT>(c, k.shift, ifx, ify, pw_, s_, b.p);
         b.last = cursor_advance<TRIP, DT>(k, b.q);
     };
     int j = 0;
@@ -1033,9 +1106,11 @@ struct FuseArgs {
     const int32_t* active;    // queue runs, the tail: the launch covers only these slots (SpQueue.active), virtual span v belongs to active[v / vspans]
     const MultiList* multi;   // the launch covers n_multi work lists of DIFFERENT batches (the windows of sp_window_gn_run_multi), one after the other
     int32_t n_multi;
+    const uint32_t* rd_pix;   // run descriptors (k_cost_pairs<.., RD = true>): the flat pix array the pairs' tables lie in, and its records
+    const SpRunDesc* rd_desc;
 };
 
-template <int MODE, int ABL = 0, int FUSED = 0, bool W64 = false>
+template <int MODE, int ABL = 0, int FUSED = 0, bool W64 = false, bool RD = false>
 __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 4)) void k_cost_pairs(
         const SpPair* __restrict__ pairs, const int4* __restrict__ chunks, const int4* __restrict__ spans, int n_spans,
         float irls_eps, float* __restrict__ partials, float* __restrict__ seg_partials, FuseArgs f) {
@@ -1111,9 +1186,11 @@ __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 4)) voi
         c.bias = sgpr(pr.aff[3] - pr.aff[1]);
     }
     c.start = 0; c.count = 0;
+    // (RD: the pair's table starts a multiple of 64 points into the flat array: its group 0)
+    const SpRunDesc* rd = RD ? f.rd_desc + ((const uint32_t*)pr.pix - f.rd_pix) / 64 : nullptr;
     if (MODE == 2) run_span_gn<ABL, FUSED != 0, true>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds);
-    else if (MODE == 1) run_span_gn<ABL, FUSED != 0, false, W64>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds);
-    else run_span_grad<ABL, FUSED != 0, W64>(c, pr, chunks, span.x, span.y, span.z, partials + (size_t)w * NV, seg_partials, lds);
+    else if (MODE == 1) run_span_gn<ABL, FUSED != 0, false, W64, RD>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds, rd);
+    else run_span_grad<ABL, FUSED != 0, W64, RD>(c, pr, chunks, span.x, span.y, span.z, partials + (size_t)w * NV, seg_partials, lds, rd);
     if (FUSED != 0) {
         __shared__ int is_last;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1347,6 +1424,33 @@ int sp_pairs_cost_active(const SpPair* pairs, const int32_t* chunks, const int32
         hipLaunchKernelGGL((k_cost_pairs<1, 2>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
     SP_CHECK_LAUNCH();
     return 0;
+}
+
+int sp_pairs_cost_rd_active(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
+                            float* partials, float* seg_partials, const int32_t* done, const uint32_t* pix_base, const SpRunDesc* desc,
+                            void* stream) {
+    if (!pairs || !chunks || !spans || !partials || !seg_partials || !pix_base || !desc || n_spans <= 0) return SP_EINVAL;
+    const int base = mode & ~(SP_COST_WAVE_SPANS | SP_COST_DEPTH_TABLE);
+    if (!(mode & SP_COST_WAVE_SPANS) || !(mode & SP_COST_DEPTH_TABLE) || (base != 0 && base != 1)) return SP_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int gw = ((((n_spans + 3) / 4) + 7) / 8) * 8;
+    FuseArgs f{};
+    f.done = done;
+    f.rd_pix = pix_base;
+    f.rd_desc = desc;
+    const int4* c4 = reinterpret_cast<const int4*>(chunks);
+    const int4* s4 = reinterpret_cast<const int4*>(spans);
+    if (base == 0)
+        hipLaunchKernelGGL((k_cost_pairs<0, 6, 0, true, true>), dim3(gw), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, f);
+    else
+        hipLaunchKernelGGL((k_cost_pairs<1, 6, 0, true, true>), dim3(gw), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, f);
+    SP_CHECK_LAUNCH();
+    return 0;
+}
+
+int sp_pairs_cost_rd(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
+                     float* partials, float* seg_partials, const uint32_t* pix_base, const SpRunDesc* desc, void* stream) {
+    return sp_pairs_cost_rd_active(pairs, chunks, spans, n_spans, mode, irls_eps, partials, seg_partials, nullptr, pix_base, desc, stream);
 }
 
 }  // extern "C"

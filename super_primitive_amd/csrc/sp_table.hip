@@ -1563,3 +1563,45 @@ int sp_prepare_gather(const float* const* src, const long long* off, int n, floa
 }
 
 }  // extern "C"
+
+// Run descriptors (include/sp_hip.h SpRunDesc): one wave per 64-point group, lane l on word l.  Group n_groups (one past the
+// table) reads nothing and comes out all zero.
+__global__ __launch_bounds__(SP_BLOCK) void k_run_desc_build(const uint32_t* __restrict__ pix, int n_groups, SpRunDesc* __restrict__ desc,
+                                                             int32_t* __restrict__ n_general) {
+    const int g = blockIdx.x * SP_WAVES + (int)(threadIdx.x >> 6);
+    if (g > n_groups) return;
+    const int lane = (int)(threadIdx.x & 63u);
+    const uint32_t w = g < n_groups ? pix[(size_t)g * 64 + lane] : 0u;
+    const uint32_t v = w & 0x7fffffffu;
+    const uint64_t valid = __ballot((w >> 31) != 0u);
+    const uint64_t nz = __ballot(w != 0u);
+    const int last = nz ? 63 - __clzll((long long)nz) : 0;          // lanes past the last nonzero word: padding
+    const uint32_t prev = (uint32_t)__shfl_up((int)v, 1);
+    const uint64_t starts = __ballot(lane == 0 || (lane <= last && v != prev + 1u));
+    const int runs = __popcll(starts);
+    const uint64_t rest = starts & ~1ull;
+    const int s1 = rest ? __ffsll((long long)rest) - 1 : 64;
+    const uint32_t v0 = (uint32_t)__shfl((int)v, 0), v1 = (uint32_t)__shfl((int)v, s1 & 63);
+    const int c0 = (int)(v0 & 0xffffu), r0 = (int)(v0 >> 16);
+    const int c1 = s1 < 64 ? (int)(v1 & 0xffffu) : c0 + s1, r1 = s1 < 64 ? (int)(v1 >> 16) : r0;
+    // word `lane` of the record, stored by lanes 0..7
+    const int f = lane & 7;
+    const uint32_t word = f == 0 ? (uint32_t)valid : f == 1 ? (uint32_t)(valid >> 32)
+                        : f == 2 ? __float_as_uint((float)(c1 - s1 - c0)) : f == 3 ? __float_as_uint((float)(r1 - r0))
+                        : f == 4 ? __float_as_uint((float)c0) : f == 5 ? __float_as_uint((float)r0)
+                        : f == 6 ? __float_as_uint((float)(1 - s1)) : (uint32_t)runs;
+    if (lane < 8) reinterpret_cast<uint32_t*>(desc + g)[lane] = word;
+    if (lane == 0 && runs > 2 && g < n_groups) atomicAdd(n_general, 1);
+}
+
+extern "C" {
+
+int sp_run_desc_build(const uint32_t* pix, int n_groups, SpRunDesc* desc, int32_t* n_general, void* stream) {
+    if (!pix || !desc || !n_general || n_groups <= 0) return SP_EINVAL;
+    const int blocks = (n_groups + 1 + SP_WAVES - 1) / SP_WAVES;
+    hipLaunchKernelGGL(k_run_desc_build, dim3(blocks), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), pix, n_groups, desc, n_general);
+    SP_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // extern "C"

@@ -230,7 +230,7 @@ class _Lazy(dict):
 class PairBatch:
     def __init__(self, src_frames, trg_images, trg_Ks, poses, klds, levels=(0, 3), use_affine=False,
                  tile_points=DEFAULT_BATCH_TILE_POINTS, zmin=1e-7, replicate=1, span_points=None, point_stride=None,
-                 extra_tables=(), lazy_levels=True, timer=None, granule=GRANULE, depth_table=True):
+                 extra_tables=(), lazy_levels=True, timer=None, granule=GRANULE, depth_table=True, run_desc=True):
         """src_frames: keyframe-like objects (image, K, logdepth_perseg, keypoints, keypoint_regions) on one cuda
         device; trg_images: list of (3,H,W); trg_Ks: list of (3,3); poses: (M,4,4) initial target<-source;
         klds: list of (N_m,) initial keypoint log-depths; levels = (pyramid_min, pyramid_max) like
@@ -259,7 +259,11 @@ class PairBatch:
         ``depth_table`` (default): the batch's tables hold exp(L) in ``src4[..., 3]`` instead of L and the cost passes run in their
         depth-table form (include/sp_hip.h SP_COST_DEPTH_TABLE: one multiply per point instead of add + multiply + v_exp_f32, the
         exponential of the segment's shift taken once per chunk; -1.8 % kernel time).  ``False``: log-depth tables, as the per-keyframe
-        path (``segment_table``) keeps them; the single-launch forms (``fused=True``) need that."""
+        path (``segment_table``) keeps them; the single-launch forms (``fused=True``) need that.
+        ``run_desc`` (default; wave-span depth tables only): RUN DESCRIPTORS of the all-points table (include/sp_hip.h SpRunDesc, 0.5 B
+        per point) -- ``cost_pass`` / ``gn_step`` / ``adam_step`` rebuild every point's pixel word from its 64-point group's record instead
+        of reading pix (4 B per point), with bitwise the same results.  Only for tables none of whose groups has more than two runs
+        (every segment at least 64 pixels wide, e.g. the grid workload); ``self.run_desc`` is None otherwise and the passes read pix."""
         assert granule in (GRANULE, 64)
         self.granule = int(granule)
         self.rec_per_chunk = 4 if granule == GRANULE else 1
@@ -461,6 +465,15 @@ class PairBatch:
         self._flag = None
         self._verdict_arrays = None
         self.status = None
+        self.run_desc = None
+        if run_desc and self.granule == 64 and self.depth_table:
+            n_groups = self.pix.numel() // 64
+            rd = torch.empty((n_groups + 1) * 8, dtype=torch.int32, device=dev)          # (one record past the table: sp_run_desc_build)
+            n_general = torch.zeros(1, dtype=torch.int32, device=dev)
+            _lib.check(lib.sp_run_desc_build(_lib.ptr(self.pix), n_groups, _lib.ptr(rd), _lib.ptr(n_general), _lib.stream_ptr()), "sp_run_desc_build")
+            if int(n_general.item()) == 0:
+                self.run_desc = rd
+            mark('run descriptors')
         self._initial = (self.pose.clone(), self.kld.clone())
         mark('constructor returns')
 
@@ -508,6 +521,11 @@ class PairBatch:
     def cost_pass(self, level, mode, irls_eps=1e-3):
         if mode not in (0, 1) and self.table_flag:
             raise ValueError("cost mode 2 and the developer modes read log-depth tables: build the batch with depth_table=False")
+        if self.run_desc is not None and mode in (0, 1):
+            _lib.check(self.lib.sp_pairs_cost_rd(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, mode | self.wave_flag | self.table_flag,
+                                                 float(irls_eps), _lib.ptr(self.partials), _lib.ptr(self.seg_partials), _lib.ptr(self.pix),
+                                                 _lib.ptr(self.run_desc), _lib.stream_ptr()), "sp_pairs_cost_rd")
+            return
         _lib.check(self.lib.sp_pairs_cost(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, mode | self.wave_flag | (self.table_flag if mode in (0, 1) else 0),
                                           float(irls_eps), _lib.ptr(self.partials), _lib.ptr(self.seg_partials), _lib.stream_ptr()), "sp_pairs_cost")
 
@@ -527,9 +545,15 @@ class PairBatch:
             return self._costs
         if conv_tol > 0.0:
             # per-pair convergence on the device: pairs in self.done are skipped by both launches (``run(conv_tol=...)``)
-            _lib.check(self.lib.sp_pairs_cost_active(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, 1 | self.wave_flag | self.table_flag,
-                                                     float(irls_eps), _lib.ptr(self.partials), _lib.ptr(self.seg_partials),
-                                                     _lib.ptr(self.done), _lib.stream_ptr()), "sp_pairs_cost_active")
+            if self.run_desc is not None:
+                _lib.check(self.lib.sp_pairs_cost_rd_active(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans,
+                                                            1 | self.wave_flag | self.table_flag, float(irls_eps), _lib.ptr(self.partials),
+                                                            _lib.ptr(self.seg_partials), _lib.ptr(self.done), _lib.ptr(self.pix), _lib.ptr(self.run_desc),
+                                                            _lib.stream_ptr()), "sp_pairs_cost_rd_active")
+            else:
+                _lib.check(self.lib.sp_pairs_cost_active(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, 1 | self.wave_flag | self.table_flag,
+                                                         float(irls_eps), _lib.ptr(self.partials), _lib.ptr(self.seg_partials),
+                                                         _lib.ptr(self.done), _lib.stream_ptr()), "sp_pairs_cost_active")
             _lib.check(self.lib.sp_pairs_gn_step_conv(_lib.ptr(self.desc[level]), self.M, self.max_N, _lib.ptr(self.partials),
                                                       _lib.ptr(self.seg_partials), float(lm_up), float(lm_down), float(lm_min),
                                                       _lib.ptr(self.lm_state), _lib.ptr(self.backup), _lib.ptr(self._costs),

@@ -75,6 +75,7 @@ def main():
             for l in batch.src4:
                 batch.src4[l].view(-1, 4).copy_(batch.src4[l].view(-1, 4)[perm])
             del key, perm, w, col, row, real, run
+            batch.run_desc = None            # (the run descriptors describe the row-major order)
         print(f"--- table order: {order} x {order} pixel blocks inside every chunk" if order else "--- table order: row-major")
       for level in [int(x) for x in a.levels.split(",")]:
         for mode in [int(x) for x in a.modes.split(",")]:
