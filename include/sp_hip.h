@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 17
+#define SP_ABI_VERSION 18
 
 #define SP_EINVAL (-1)   /* bad argument (null pointer, non-positive size, ...) */
 #define SP_ELIMIT (-2)   /* size outside what the kernels support (H or W > 32767, N > 65535, ...) */
@@ -316,9 +316,22 @@ int sp_host_work_list(const long long* pc, const long long* seg_pos, const long 
 /* mode 0 / 1 as above.  mode 2 = mode 1 plus the affine brightness pair of the TARGET frame as two more unknowns (a_t, b_t; the
  * source frame's pair enters with the opposite sign): residual columns j_a = gain * I_trg(sample), j_b = -1.  Span record
  * (SP_GNA_PARTIAL_FLOATS): [0..28] as mode 1, [29..31] H_aa = {aa, ab, bb}, [32,33] b_a, [34..39] H_{a,pose}, [40..45] H_{b,pose};
- * segment record (SP_GNA_SEG_FLOATS): [0..7] as mode 1, [8] H_{a,depth}, [9] H_{b,depth}.  Consumed by sp_window_gn_step. */
+ * segment record (SP_GNA_SEG_FLOATS): [0..7] as mode 1, [8] H_{a,depth}, [9] H_{b,depth}.  Consumed by sp_window_gn_step.
+ * mode 2 takes neither flag; any other value of mode is SP_EINVAL (checked before any device work).
+ *
+ * sp_pairs_cost_opt is sp_pairs_cost with three optional arguments; sp_pairs_cost passes NULL for each.
+ *   done (n_pairs int32, see sp_pairs_gn_step_conv): workgroups return at once for spans of marked pairs, so that an iteration
+ *     costs time only for the pairs still moving.
+ *   pix_base, desc (both or neither; mode 0 or 1 | SP_COST_WAVE_SPANS | SP_COST_DEPTH_TABLE, anything else is SP_EINVAL): the pixel
+ *     words come from RUN DESCRIPTORS (SpRunDesc below) instead of pix.  pix_base = the flat pix array every pair's SpPair.pix
+ *     points into (pair tables start at multiples of 64 points from it), desc = sp_run_desc_build of that array, without groups of
+ *     more than two runs.  Bitwise the same partials as without them. */
 int sp_pairs_cost(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
                   float* span_partials, float* seg_partials, void* stream);
+struct SpRunDesc;
+int sp_pairs_cost_opt(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
+                      float* span_partials, float* seg_partials, const int32_t* done, const uint32_t* pix_base,
+                      const struct SpRunDesc* desc, void* stream);
 
 /* Adam step on {kld, left SE(3) tangent, affine} of every pair from the mode-0 partials: reduces the tile
  * partials (fixed order, fp64), loss = |residual| like odometery/two_frame_sfm.py:201-206, maps d/dpose to the
@@ -343,13 +356,13 @@ int sp_pairs_gn_step(const SpPair* pairs, int n_pairs, int max_N, const float* s
 /* Per-pair convergence on the device (the counterpart of the reference's relative-loss early stop, odometery/odometery.py:907-915,
  * for a batch whose pairs need different numbers of iterations).  sp_pairs_gn_step_conv marks done[pair] = 1 -- and leaves the pair
  * at its current point -- when the step that led to the evaluated point was accepted and lowered the cost by less than
- * conv_tol * cost; it returns immediately for pairs already marked.  sp_pairs_cost_active is sp_pairs_cost whose workgroups return
- * at once for spans of marked pairs: an iteration then costs time only for the pairs still moving.  done: n_pairs int32, zeroed
- * by the caller (per pyramid level).  conv_tol <= 0 / done == NULL: exactly sp_pairs_gn_step / sp_pairs_cost. */
-int sp_pairs_cost_active(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
-                         float* span_partials, float* seg_partials, const int32_t* done, void* stream);
+ * conv_tol * cost; it returns immediately for pairs already marked, and sp_pairs_cost_opt skips their spans.  done: n_pairs int32,
+ * zeroed by the caller (per pyramid level).  conv_tol <= 0 / done == NULL: exactly sp_pairs_gn_step / sp_pairs_cost. */
+int sp_pairs_gn_step_conv(const SpPair* pairs, int n_pairs, int max_N, const float* span_partials, const float* seg_partials,
+                          float lm_up, float lm_down, float lm_min, float* lm_state, float* backup, float* costs, float conv_tol,
+                          int32_t* done, void* stream);
 
-/* RUN DESCRIPTORS: the pixel words of a wave-span table (granule 64) rebuilt from one 32-byte record per 64-point group instead of
+/* RUN DESCRIPTORS (sp_pairs_cost_opt): the pixel words of a wave-span table (granule 64) rebuilt from one 32-byte record per 64-point group instead of
  * read point by point (4 B per point of the cost pass's stream).  A group lies inside one chunk of one segment, its points in
  * row-major order: its points form RUNS of consecutive pixels of one row, and with at most two runs (every segment at least 64
  * pixels wide) lane l of the group decodes as
@@ -370,18 +383,6 @@ typedef struct SpRunDesc {
  * (device int32, zeroed by the caller) += number of groups with more than two runs.  Build it after the table's validity bits are
  * final (sp_prepare_sample / sp_table_sample_source). */
 int sp_run_desc_build(const uint32_t* pix, int n_groups, SpRunDesc* desc, int32_t* n_general, void* stream);
-/* sp_pairs_cost / sp_pairs_cost_active on a wave-span depth table (mode 0 or 1 | SP_COST_WAVE_SPANS | SP_COST_DEPTH_TABLE) whose
- * pixel words come from run descriptors instead of pix: pix_base = the flat pix array every pair's SpPair.pix points into (pair
- * tables start at multiples of 64 points from it), desc = sp_run_desc_build of that array, without groups of more than two runs.
- * Bitwise the same partials as sp_pairs_cost. */
-int sp_pairs_cost_rd(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
-                     float* span_partials, float* seg_partials, const uint32_t* pix_base, const SpRunDesc* desc, void* stream);
-int sp_pairs_cost_rd_active(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
-                            float* span_partials, float* seg_partials, const int32_t* done, const uint32_t* pix_base,
-                            const SpRunDesc* desc, void* stream);
-int sp_pairs_gn_step_conv(const SpPair* pairs, int n_pairs, int max_N, const float* span_partials, const float* seg_partials,
-                          float lm_up, float lm_down, float lm_min, float* lm_state, float* backup, float* costs, float conv_tol,
-                          int32_t* done, void* stream);
 
 /* A whole coarse-to-fine schedule PER PAIR on the device.  Phase p of the schedule runs on the descriptors `pairs` of one pyramid
  * level (every phase describes the same n_pairs pairs) over the work list (chunks, spans) of that level's point set -- a coarse

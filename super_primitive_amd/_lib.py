@@ -32,10 +32,8 @@ SIGNATURES = {
     "sp_pairs_cost": [P, P, P, I, I, F, P, P, P],
     "sp_pairs_adam_step": [P, I, I, P, P, F, F, F, P, P, P],
     "sp_pairs_gn_step": [P, I, I, P, P, F, F, F, P, P, P, P],
-    "sp_pairs_cost_active": [P, P, P, I, I, F, P, P, P, P],
+    "sp_pairs_cost_opt": [P, P, P, I, I, F, P, P, P, P, P, P],
     "sp_run_desc_build": [P, I, P, P, P],
-    "sp_pairs_cost_rd": [P, P, P, I, I, F, P, P, P, P, P],
-    "sp_pairs_cost_rd_active": [P, P, P, I, I, F, P, P, P, P, P, P],
     "sp_pairs_gn_step_conv": [P, I, I, P, P, F, F, F, P, P, P, F, P, P],
     "sp_prepare_count": [P, I, I, I, P],
     "sp_prepare_count_boxed": [P, I, I, I, P],
@@ -85,7 +83,7 @@ SIGNATURES = {
     "sp_kth_mask_pixel": [P, P, I, I, I, P, P, P],
 }
 
-SP_ABI_VERSION = 17
+SP_ABI_VERSION = 18
 SP_GRAD_PARTIAL_FLOATS = 16
 SP_GN_PARTIAL_FLOATS = 32
 SP_GNA_PARTIAL_FLOATS = 48

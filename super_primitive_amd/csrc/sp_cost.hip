@@ -6,6 +6,8 @@
 //
 // Replaces core/dense_optim.py:265-403 and core/dense_optim_batch.py:50-147 of the reference (about 150 ATen
 // launches forward + the autograd backward) -- see include/sp_hip.h for the ABI and DESIGN.md for the layout.
+#include <type_traits>
+
 #include "sp_solve_device.h"
 
 namespace {
@@ -661,29 +663,17 @@ __device__ __forceinline__ void flush_segment_gn(GnAcc& A, float* __restrict__ r
     A.hd01 = z; A.hd[0] = z; A.hd[1] = z; A.D = z; A.bd = z;
 }
 
-// ABL (developer ablation, only reachable through mode >= 10 of sp_pairs_cost): 0 = product kernel,
-// 1 = no target gathers (taps replaced by the source colour), 2 = loads + geometry only (no accumulation),
-// 3 (mode 1 only) = the four tap loads made lane-consecutive (coalesced) instead of gathered,
-// 5 (mode 16) = NO pix stream: the pixel word of a point comes out of the low mantissa bits of its own src4 colours (tools/kbench.py
-//   packs it there for the run): the cheapest conceivable way of "deriving" the pixel -- 6 integer instructions, no load, 16 B per
-//   point instead of 20 -- i.e. the upper bound of what replacing pix[P] by run descriptors + a validity mask could gain
-__device__ __forceinline__ uint32_t pix_from_colour_bits(const f32x4 s) {
-    const uint32_t a = __builtin_bit_cast(uint32_t, s.x), b = __builtin_bit_cast(uint32_t, s.y), c = __builtin_bit_cast(uint32_t, s.z);
-    const uint32_t v = (a & 0x7fu) | ((b & 0x7fu) << 7) | ((c & 0x3fu) << 14);            // col (10) | row (9) << 10 | valid << 19
-    return (v & 0x3ffu) | (((v >> 10) & 0x1ffu) << 16) | ((v >> 19) << 31);
-}
-// 6 = DEPTH TABLES (a product form, not an ablation: SP_COST_DEPTH_TABLE / SP_PHASE_DEPTH_TABLE) -- src4.w holds exp(L), see cursor_shift
+// DT ("depth tables", SP_COST_DEPTH_TABLE / SP_PHASE_DEPTH_TABLE): src4.w holds exp(L) instead of L, see cursor_shift.
 // W64 ("wave spans"): the span belongs to ONE WAVE -- trips of 64 points, segment records one per chunk, pair-level sums reduced
 // over the wave only -- so that the padding granule of the tables is 64 points instead of 256 (small ragged segments: 1200
 // SAM-like masks of ~280 pixels pad 40 % at 256 and 11 % at 64); the four waves of a workgroup work on four consecutive spans.
 // RD (W64 depth tables only): pixel words from the run descriptors of the pair's table (rd = its group 0) instead of pix
-template <int ABL, bool WT, bool AFF = false, bool W64 = false, bool RD = false>
+template <bool DT, bool WT, bool AFF = false, bool W64 = false, bool RD = false>
 __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, const int4* __restrict__ chunks, int q0,
                                             int n_chunks, int total, float irls_eps, float* __restrict__ span_rec,
                                             float* __restrict__ seg_partials, float* lds, const SpRunDesc* rd = nullptr) {
-    static_assert(!RD || (W64 && ABL == 6 && !AFF), "run descriptors: wave spans on depth tables");
+    static_assert(!RD || (W64 && DT && !AFF), "run descriptors: wave spans on depth tables");
     constexpr int TRIP = W64 ? 64 : SP_BLOCK;
-    constexpr bool DT = ABL == 6;            // depth tables (cursor_shift)
     constexpr int NV = AFF ? SP_GNA_PARTIAL_FLOATS : SP_GN_PARTIAL_FLOATS, NS = AFF ? SP_GNA_SEG_FLOATS : SP_GN_SEG_FLOATS;
     GnAcc A;
     AffAcc AA;
@@ -746,7 +736,7 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
         const f32x4 s = buf_load4<NT>(r_src, op * 4u);
         if (RD) prepare2_rd<DT>(kc, k.shift, rd_load(rg), lane2, s, S0.p);
         else {
-            const uint32_t pw = ABL == 5 ? pix_from_colour_bits(s) : (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
+            const uint32_t pw = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
             prepare2<DT>(c, kc, k.shift, pw, s, S0.p);
         }
         S0.last = cursor_advance<TRIP, DT>(k, S0.q);
@@ -759,48 +749,26 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
     auto trip = [&](Slot& a, Slot& b) {
         op += 4u * TRIP;
         asm volatile("" : "+v"(op));        // one induction register; the src4 offset is a shift of it
-        const uint32_t pw = (ABL == 5 || RD) ? 0u : (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
+        const uint32_t pw = RD ? 0u : (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r_pix, (int)op, 0, NT);
         const f32x4 s = buf_load4<NT>(r_src, op * 4u);
         SpRunDesc rn;
         if (RD) { ++rg; rn = rd_load(rg); }
-        f32x3 ta, tb, tc, td;
-        if (ABL == 1) { ta = tb = tc = td = f32x3{a.p.srg.x, a.p.srg.y, a.p.sb}; }
-        else if (ABL == 3) {
-            // same four 12-byte loads per point, same data volume and real image values, but lane-consecutive texels
-            // (fully coalesced): what the bilinear footprint would cost if it were not a gather
-            const uint32_t lin = (op >> 2) * (4u * SP_TEXEL_FLOATS);
-            const uint32_t cap = (uint32_t)(c.Wl * (c.Hl - 2)) * (4u * SP_TEXEL_FLOATS);
-            const uint32_t o0 = lin < cap ? lin : lin - cap * (lin / cap);
-            ta = buf_load3(r_trg, o0);
-            tb = buf_load3(r_trg, o0 + 4u * SP_TEXEL_FLOATS);
-            tc = buf_load3(r_trg, o0, c.row_bytes);
-            td = buf_load3(r_trg, o0 + 4u * SP_TEXEL_FLOATS, c.row_bytes);
-        } else if (ABL == 4) {
-            // upper bound of sharing the right-hand texels with the neighbouring lane: only the left column is loaded
-            ta = buf_load3(r_trg, a.p.off0);
-            tc = buf_load3(r_trg, a.p.off0, c.row_bytes);
-            tb = ta; td = tc;
-        } else {
-            ta = buf_load3(r_trg, a.p.off0);
-            tb = buf_load3(r_trg, a.p.off0 + 4u * SP_TEXEL_FLOATS);
-            tc = buf_load3(r_trg, a.p.off0, c.row_bytes);
-            td = buf_load3(r_trg, a.p.off0 + 4u * SP_TEXEL_FLOATS, c.row_bytes);
-        }
+        f32x3 ta = buf_load3(r_trg, a.p.off0);
+        f32x3 tb = buf_load3(r_trg, a.p.off0 + 4u * SP_TEXEL_FLOATS);
+        f32x3 tc = buf_load3(r_trg, a.p.off0, c.row_bytes);
+        f32x3 td = buf_load3(r_trg, a.p.off0 + 4u * SP_TEXEL_FLOATS, c.row_bytes);
         __builtin_amdgcn_sched_barrier(0);
-        if (ABL != 2) fold_gn2<AFF>(kc, GeoGn{b.p.qxy, b.p.qz, b.p.zinv, b.p.zi}, m, A, &ma, &AA);
+        fold_gn2<AFF>(kc, GeoGn{b.p.qxy, b.p.qz, b.p.zinv, b.p.zi}, m, A, &ma, &AA);
         if (b.last) flush_segment_gn<WT, AFF>(A, seg_partials + (size_t)(W64 ? b.q : 4 * b.q + wave) * NS, &AA);
         __builtin_amdgcn_sched_barrier(0);
-        if (ABL != 1)
-            asm volatile("" : "+v"(ta), "+v"(tb), "+v"(tc), "+v"(td), "+v"(A.blk[0]), "+v"(A.blk[1]), "+v"(A.blk[2]),
-                         "+v"(A.blk[3]), "+v"(A.blk[4]), "+v"(A.blk[5]), "+v"(A.bp[0]), "+v"(A.bp[1]), "+v"(A.hd[0]),
-                         "+v"(A.hd[1]), "+v"(A.D), "+v"(A.bd), "+v"(A.h00), "+v"(A.h0[0]), "+v"(A.h0[1]), "+v"(A.h1[0]), "+v"(A.h1[1]), "+v"(A.h11), "+v"(A.bp01), "+v"(A.hd01));
-        if (ABL == 2) A.cost += ta.x + tb.y + tc.z + td.x + a.p.wxy.x + a.p.wxy.y + a.p.m;
-        else finish_gn2<AFF>(kc, a.p, ta, tb, tc, td, m, A.cost, A.n, &ma, &AA);
+        asm volatile("" : "+v"(ta), "+v"(tb), "+v"(tc), "+v"(td), "+v"(A.blk[0]), "+v"(A.blk[1]), "+v"(A.blk[2]),
+                     "+v"(A.blk[3]), "+v"(A.blk[4]), "+v"(A.blk[5]), "+v"(A.bp[0]), "+v"(A.bp[1]), "+v"(A.hd[0]),
+                     "+v"(A.hd[1]), "+v"(A.D), "+v"(A.bd), "+v"(A.h00), "+v"(A.h0[0]), "+v"(A.h0[1]), "+v"(A.h1[0]), "+v"(A.h1[1]), "+v"(A.h11), "+v"(A.bp01), "+v"(A.hd01));
+        finish_gn2<AFF>(kc, a.p, ta, tb, tc, td, m, A.cost, A.n, &ma, &AA);
         uint32_t pw_ = pw;
         f32x4 s_ = s;
         if (RD) asm volatile("" : "+v"(s_));
         else asm volatile("" : "+v"(pw_), "+v"(s_));
-        if (ABL == 5) pw_ = pix_from_colour_bits(s_);
         if (RD) prepare2_rd<DT>(kc, k.shift, rn, lane2, s_, b.p);
         else prepare2<DT>(c, kc, k.shift, pw_, s_, b.p);       // (the trip past the end reads zeros and is never used)
         b.last = cursor_advance<TRIP, DT>(k, b.q);
@@ -809,10 +777,10 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
     for (; j + 1 < n_iter; j += 2) { trip(S0, S1); trip(S1, S0); }
     if (j < n_iter) {                    // odd trip count: the last point sits in S0
         trip(S0, S1);
-        if (ABL != 2) fold_gn2<AFF>(kc, GeoGn{S0.p.qxy, S0.p.qz, S0.p.zinv, S0.p.zi}, m, A, &ma, &AA);
+        fold_gn2<AFF>(kc, GeoGn{S0.p.qxy, S0.p.qz, S0.p.zinv, S0.p.zi}, m, A, &ma, &AA);
         flush_segment_gn<WT, AFF>(A, seg_partials + (size_t)(W64 ? S0.q : 4 * S0.q + wave) * NS, &AA);
     } else {
-        if (ABL != 2) fold_gn2<AFF>(kc, GeoGn{S1.p.qxy, S1.p.qz, S1.p.zinv, S1.p.zi}, m, A, &ma, &AA);
+        fold_gn2<AFF>(kc, GeoGn{S1.p.qxy, S1.p.qz, S1.p.zinv, S1.p.zi}, m, A, &ma, &AA);
         flush_segment_gn<WT, AFF>(A, seg_partials + (size_t)(W64 ? S1.q : 4 * S1.q + wave) * NS, &AA);
     }
     float acc[NV];
@@ -849,13 +817,12 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
 }
 
 // mode 0: the segment column is 13 (d/dkld)
-template <int ABL, bool WT, bool W64 = false, bool RD = false>
+template <bool DT, bool WT, bool W64 = false, bool RD = false>
 __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr, const int4* __restrict__ chunks, int q0,
                                               int n_chunks, int total, float* __restrict__ span_rec,
                                               float* __restrict__ seg_partials, float* lds, const SpRunDesc* rd = nullptr) {
-    static_assert(!RD || (W64 && ABL == 6), "run descriptors: wave spans on depth tables");
+    static_assert(!RD || (W64 && DT), "run descriptors: wave spans on depth tables");
     constexpr int TRIP = W64 ? 64 : SP_BLOCK;
-    constexpr bool DT = ABL == 6;            // depth tables (cursor_shift)
     constexpr int NV = SP_GRAD_PARTIAL_FLOATS;
     float acc[NV];
 #pragma unroll
@@ -902,24 +869,18 @@ __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr
         const f32x4 s = buf_load4<NT>(r_src, op * 4u);
         SpRunDesc rn;
         if (RD) { ++rg; rn = rd_load(rg); }
-        f32x3 ta, tb, tc, td;
-        if (ABL == 1) { ta = tb = tc = td = f32x3{a.p.sr, a.p.sg, a.p.sb}; }
-        else {
-            ta = buf_load3(r_trg, a.p.off0);
-            tb = buf_load3(r_trg, a.p.off0 + 4u * SP_TEXEL_FLOATS);
-            tc = buf_load3(r_trg, a.p.off0, c.row_bytes);
-            td = buf_load3(r_trg, a.p.off0 + 4u * SP_TEXEL_FLOATS, c.row_bytes);
-        }
+        f32x3 ta = buf_load3(r_trg, a.p.off0);
+        f32x3 tb = buf_load3(r_trg, a.p.off0 + 4u * SP_TEXEL_FLOATS);
+        f32x3 tc = buf_load3(r_trg, a.p.off0, c.row_bytes);
+        f32x3 td = buf_load3(r_trg, a.p.off0 + 4u * SP_TEXEL_FLOATS, c.row_bytes);
         __builtin_amdgcn_sched_barrier(0);
-        if (ABL != 2) fold_grad(c, b.p.g, m0, acc);
+        fold_grad(c, b.p.g, m0, acc);
         if (b.last) flush(b.q);
         __builtin_amdgcn_sched_barrier(0);
-        if (ABL != 1)
-            asm volatile("" : "+v"(ta), "+v"(tb), "+v"(tc), "+v"(td), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]),
-                         "+v"(acc[6]), "+v"(acc[7]), "+v"(acc[8]), "+v"(acc[9]), "+v"(acc[10]), "+v"(acc[11]), "+v"(acc[12]),
-                         "+v"(acc[13]), "+v"(acc[14]), "+v"(acc[15]));
-        if (ABL == 2) acc[0] += ta.x + tb.y + tc.z + td.x + a.p.wx + a.p.wy + a.p.m;
-        else finish_grad(c, a.p, ta, tb, tc, td, m0, acc[0]);
+        asm volatile("" : "+v"(ta), "+v"(tb), "+v"(tc), "+v"(td), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]),
+                     "+v"(acc[6]), "+v"(acc[7]), "+v"(acc[8]), "+v"(acc[9]), "+v"(acc[10]), "+v"(acc[11]), "+v"(acc[12]),
+                     "+v"(acc[13]), "+v"(acc[14]), "+v"(acc[15]));
+        finish_grad(c, a.p, ta, tb, tc, td, m0, acc[0]);
         uint32_t pw_ = pw;
         f32x4 s_ = s;
         if (RD) asm volatile("" : "+v"(s_));
@@ -932,10 +893,10 @@ __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr
     for (; j + 1 < n_iter; j += 2) { trip(S0, S1); trip(S1, S0); }
     if (j < n_iter) {                    // odd trip count: the last point sits in S0
         trip(S0, S1);
-        if (ABL != 2) fold_grad(c, S0.p.g, m0, acc);
+        fold_grad(c, S0.p.g, m0, acc);
         flush(S0.q);
     } else {
-        if (ABL != 2) fold_grad(c, S1.p.g, m0, acc);
+        fold_grad(c, S1.p.g, m0, acc);
         flush(S1.q);
     }
     if (W64) {
@@ -1106,14 +1067,28 @@ struct FuseArgs {
     const int32_t* active;    // queue runs, the tail: the launch covers only these slots (SpQueue.active), virtual span v belongs to active[v / vspans]
     const MultiList* multi;   // the launch covers n_multi work lists of DIFFERENT batches (the windows of sp_window_gn_run_multi), one after the other
     int32_t n_multi;
-    const uint32_t* rd_pix;   // run descriptors (k_cost_pairs<.., RD = true>): the flat pix array the pairs' tables lie in, and its records
+    const uint32_t* rd_pix;   // run descriptors (CostFrom<RunDesc>): the flat pix array the pairs' tables lie in, and its records
     const SpRunDesc* rd_desc;
 };
 
-template <int MODE, int ABL = 0, int FUSED = 0, bool W64 = false, bool RD = false>
-__global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 4)) void k_cost_pairs(
+// FORM, the second template argument of k_cost_pairs: what src4.w of the tables holds.  Profiler output (and bench.py's filter on it)
+// prints it as a number, so the two values are fixed.
+constexpr int FORM_LOG_DEPTH = 0, FORM_DEPTH = 6;
+
+// Where the pixel word of a point comes from: the pix stream, or the run descriptors f.rd_pix / f.rd_desc (wave-span depth tables only).
+// The source is the argument of the CLASS the kernel is a member of, not one of the kernel's own template arguments: a kernel's
+// profiler-visible name is CostFrom<..>::k_cost_pairs<MODE, FORM, FUSED, W64>, and that tail is what bench.py looks for.
+struct Pix;
+struct RunDesc;
+template <class SRC>
+struct CostFrom {
+template <int MODE, int FORM = FORM_LOG_DEPTH, int FUSED = 0, bool W64 = false>
+static __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 4)) void k_cost_pairs(
         const SpPair* __restrict__ pairs, const int4* __restrict__ chunks, const int4* __restrict__ spans, int n_spans,
         float irls_eps, float* __restrict__ partials, float* __restrict__ seg_partials, FuseArgs f) {
+    static_assert(FORM == FORM_LOG_DEPTH || FORM == FORM_DEPTH, "FORM: log-depth tables (0) or depth tables (6)");
+    constexpr bool RD = std::is_same<SRC, RunDesc>::value;
+    constexpr bool DT = FORM == FORM_DEPTH;
     constexpr int NV = MODE == 0 ? SP_GRAD_PARTIAL_FLOATS : (MODE == 2 ? SP_GNA_PARTIAL_FLOATS : SP_GN_PARTIAL_FLOATS);
     __shared__ float lds[SP_WAVES * NV];
     int block = blockIdx.x;
@@ -1163,7 +1138,7 @@ __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 4)) voi
     } else {
         span = spans[w];
         owner = span.w;
-        if (f.done && f.done[owner]) return;    // converged pair (sp_pairs_cost_active): nothing to evaluate
+        if (f.done && f.done[owner]) return;    // converged pair (sp_pairs_cost_opt): nothing to evaluate
         if (f.phase) {
             const int ph = f.phase[owner];
             if (ph >= SP_MAX_PHASES || ph < 0 || !((phase_mask >> ph) & 1u)) return;
@@ -1188,9 +1163,9 @@ __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 4)) voi
     c.start = 0; c.count = 0;
     // (RD: the pair's table starts a multiple of 64 points into the flat array: its group 0)
     const SpRunDesc* rd = RD ? f.rd_desc + ((const uint32_t*)pr.pix - f.rd_pix) / 64 : nullptr;
-    if (MODE == 2) run_span_gn<ABL, FUSED != 0, true>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds);
-    else if (MODE == 1) run_span_gn<ABL, FUSED != 0, false, W64, RD>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds, rd);
-    else run_span_grad<ABL, FUSED != 0, W64, RD>(c, pr, chunks, span.x, span.y, span.z, partials + (size_t)w * NV, seg_partials, lds, rd);
+    if (MODE == 2) run_span_gn<DT, FUSED != 0, true>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds);
+    else if (MODE == 1) run_span_gn<DT, FUSED != 0, false, W64, RD>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds, rd);
+    else run_span_grad<DT, FUSED != 0, W64, RD>(c, pr, chunks, span.x, span.y, span.z, partials + (size_t)w * NV, seg_partials, lds, rd);
     if (FUSED != 0) {
         __shared__ int is_last;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1210,6 +1185,50 @@ __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 4)) voi
             else solve_gn(pairs, span.w, partials, seg_partials, f.gn);
         }
     }
+}
+};  // CostFrom
+
+// ---- the variants of k_cost_pairs that exist, and the one place that launches them ----
+struct CostVariant {
+    int mode;                  // 0 cost + gradient, 1 Gauss-Newton, 2 Gauss-Newton with the target's affine pair
+    bool dt, w64, rd;          // depth tables, wave spans, pixel words from run descriptors
+    int fused;                 // 0, or the solver the last workgroup of a pair runs: 1 Adam, 2 Gauss-Newton
+};
+using CostKernel = void (*)(const SpPair*, const int4*, const int4*, int, float, float*, float*, FuseArgs);
+CostKernel cost_kernel(const CostVariant& v) {             // nullptr: no such variant
+    enum { DT = 4, W64 = 8, RD = 16, ADAM = 32, GN = 2 * ADAM };       // (ADAM, GN: fused 1, 2)
+    if (v.mode < 0 || v.mode > 2 || v.fused < 0 || v.fused > 2) return nullptr;
+    switch (v.mode | (v.dt ? DT : 0) | (v.w64 ? W64 : 0) | (v.rd ? RD : 0) | v.fused * ADAM) {
+        case 0:                 return CostFrom<Pix>::k_cost_pairs<0>;
+        case 1:                 return CostFrom<Pix>::k_cost_pairs<1>;
+        case 2:                 return CostFrom<Pix>::k_cost_pairs<2>;
+        case 0 | DT:            return CostFrom<Pix>::k_cost_pairs<0, FORM_DEPTH>;
+        case 1 | DT:            return CostFrom<Pix>::k_cost_pairs<1, FORM_DEPTH>;
+        case 0 | W64:           return CostFrom<Pix>::k_cost_pairs<0, FORM_LOG_DEPTH, 0, true>;
+        case 1 | W64:           return CostFrom<Pix>::k_cost_pairs<1, FORM_LOG_DEPTH, 0, true>;
+        case 0 | DT | W64:      return CostFrom<Pix>::k_cost_pairs<0, FORM_DEPTH, 0, true>;
+        case 1 | DT | W64:      return CostFrom<Pix>::k_cost_pairs<1, FORM_DEPTH, 0, true>;
+        case 0 | DT | W64 | RD: return CostFrom<RunDesc>::k_cost_pairs<0, FORM_DEPTH, 0, true>;
+        case 1 | DT | W64 | RD: return CostFrom<RunDesc>::k_cost_pairs<1, FORM_DEPTH, 0, true>;
+        case 0 | ADAM:          return CostFrom<Pix>::k_cost_pairs<0, FORM_LOG_DEPTH, 1>;
+        case 1 | GN:            return CostFrom<Pix>::k_cost_pairs<1, FORM_LOG_DEPTH, 2>;
+        default:                return nullptr;
+    }
+}
+
+// workgroups of a launch over n_spans spans (a multiple of 8: the XCD of a block stays blockIdx.x % 8); four wave spans share one
+int cost_blocks(int n_spans, bool w64) { return (((w64 ? (n_spans + 3) / 4 : n_spans) + 7) / 8) * 8; }
+
+// SP_EINVAL (before any HIP call) if the variant does not exist
+int launch_cost(const CostVariant& v, int blocks, hipStream_t s, const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans,
+                float irls_eps, float* partials, float* seg_partials, const FuseArgs& f) {
+    const CostKernel k = cost_kernel(v);
+    if (!k) return SP_EINVAL;
+    const int4* c4 = reinterpret_cast<const int4*>(chunks);
+    const int4* s4 = reinterpret_cast<const int4*>(spans);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, f);
+    SP_CHECK_LAUNCH();
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1355,118 +1374,34 @@ int sp_photo_stats(const uint32_t* pix, const float* src4, const int32_t* seg_of
     return 0;
 }
 
-int sp_pairs_cost_active(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
-                         float* partials, float* seg_partials, const int32_t* done, void* stream);
-
-int sp_pairs_cost(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
-                  float* partials, float* seg_partials, void* stream) {
-    return sp_pairs_cost_active(pairs, chunks, spans, n_spans, mode, irls_eps, partials, seg_partials, nullptr, stream);
-}
-
-int sp_pairs_cost_active(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
-                         float* partials, float* seg_partials, const int32_t* done, void* stream) {
-    if (!pairs || !chunks || !spans || !partials || !seg_partials || n_spans <= 0) return SP_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (mode & SP_COST_WAVE_SPANS) {        // wave-granular work list (granule 64): modes 0 and 1
-        const int base = mode & ~(SP_COST_WAVE_SPANS | SP_COST_DEPTH_TABLE);
-        const bool dt = (mode & SP_COST_DEPTH_TABLE) != 0 || base == 17;
-        if (base != 0 && base != 1 && base != 17) return SP_EINVAL;
-        const int gw = ((((n_spans + 3) / 4) + 7) / 8) * 8;
-        FuseArgs nf{};
-        nf.done = done;
-        const int4* c4 = reinterpret_cast<const int4*>(chunks);
-        const int4* s4 = reinterpret_cast<const int4*>(spans);
-        if (base == 0 && dt)
-            hipLaunchKernelGGL((k_cost_pairs<0, 6, 0, true>), dim3(gw), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nf);
-        else if (base == 0)
-            hipLaunchKernelGGL((k_cost_pairs<0, 0, 0, true>), dim3(gw), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nf);
-        else if (dt)
-            hipLaunchKernelGGL((k_cost_pairs<1, 6, 0, true>), dim3(gw), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nf);
-        else
-            hipLaunchKernelGGL((k_cost_pairs<1, 0, 0, true>), dim3(gw), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nf);
-        SP_CHECK_LAUNCH();
-        return 0;
-    }
-    if (mode & SP_COST_DEPTH_TABLE) {
-        const int base = mode & ~SP_COST_DEPTH_TABLE;
-        if (base != 0 && base != 1) return SP_EINVAL;
-        mode = base == 0 ? 18 : 17;
-    }
-    if (mode != 0 && mode != 1 && mode != 2 && !(mode >= 10 && mode <= 18)) return SP_EINVAL;
-    const int gx = ((n_spans + 7) / 8) * 8;
-    const int4* c4 = reinterpret_cast<const int4*>(chunks);
-    const int4* s4 = reinterpret_cast<const int4*>(spans);
-    FuseArgs nofuse{};
-    nofuse.done = done;
-    if (mode == 0)
-        hipLaunchKernelGGL(k_cost_pairs<0>, dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 1)
-        hipLaunchKernelGGL(k_cost_pairs<1>, dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 2)
-        hipLaunchKernelGGL(k_cost_pairs<2>, dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 10)   /* developer ablations, see run_span_gn */
-        hipLaunchKernelGGL((k_cost_pairs<0, 1>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 11)
-        hipLaunchKernelGGL((k_cost_pairs<1, 1>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 14)
-        hipLaunchKernelGGL((k_cost_pairs<1, 3>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 17)
-        hipLaunchKernelGGL((k_cost_pairs<1, 6>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 18)
-        hipLaunchKernelGGL((k_cost_pairs<0, 6>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 16)
-        hipLaunchKernelGGL((k_cost_pairs<1, 5>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 15)
-        hipLaunchKernelGGL((k_cost_pairs<1, 4>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else if (mode == 12)
-        hipLaunchKernelGGL((k_cost_pairs<0, 2>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    else
-        hipLaunchKernelGGL((k_cost_pairs<1, 2>), dim3(gx), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, nofuse);
-    SP_CHECK_LAUNCH();
-    return 0;
-}
-
-int sp_pairs_cost_rd_active(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
-                            float* partials, float* seg_partials, const int32_t* done, const uint32_t* pix_base, const SpRunDesc* desc,
-                            void* stream) {
-    if (!pairs || !chunks || !spans || !partials || !seg_partials || !pix_base || !desc || n_spans <= 0) return SP_EINVAL;
-    const int base = mode & ~(SP_COST_WAVE_SPANS | SP_COST_DEPTH_TABLE);
-    if (!(mode & SP_COST_WAVE_SPANS) || !(mode & SP_COST_DEPTH_TABLE) || (base != 0 && base != 1)) return SP_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int gw = ((((n_spans + 3) / 4) + 7) / 8) * 8;
+int sp_pairs_cost_opt(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
+                      float* partials, float* seg_partials, const int32_t* done, const uint32_t* pix_base, const SpRunDesc* desc, void* stream) {
+    if (!pairs || !chunks || !spans || !partials || !seg_partials || n_spans <= 0 || (pix_base == nullptr) != (desc == nullptr)) return SP_EINVAL;
+    // (what remains of `mode` must be 0, 1 or 2; mode 2 has no flags, run descriptors are for wave-span depth tables: cost_kernel)
+    const CostVariant v{mode & ~(SP_COST_WAVE_SPANS | SP_COST_DEPTH_TABLE), (mode & SP_COST_DEPTH_TABLE) != 0, (mode & SP_COST_WAVE_SPANS) != 0,
+                        desc != nullptr, 0};
     FuseArgs f{};
     f.done = done;
     f.rd_pix = pix_base;
     f.rd_desc = desc;
-    const int4* c4 = reinterpret_cast<const int4*>(chunks);
-    const int4* s4 = reinterpret_cast<const int4*>(spans);
-    if (base == 0)
-        hipLaunchKernelGGL((k_cost_pairs<0, 6, 0, true, true>), dim3(gw), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, f);
-    else
-        hipLaunchKernelGGL((k_cost_pairs<1, 6, 0, true, true>), dim3(gw), dim3(SP_BLOCK), 0, s, pairs, c4, s4, n_spans, irls_eps, partials, seg_partials, f);
-    SP_CHECK_LAUNCH();
-    return 0;
+    return launch_cost(v, cost_blocks(n_spans, v.w64), static_cast<hipStream_t>(stream), pairs, chunks, spans, n_spans, irls_eps, partials,
+                       seg_partials, f);
 }
 
-int sp_pairs_cost_rd(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
-                     float* partials, float* seg_partials, const uint32_t* pix_base, const SpRunDesc* desc, void* stream) {
-    return sp_pairs_cost_rd_active(pairs, chunks, spans, n_spans, mode, irls_eps, partials, seg_partials, nullptr, pix_base, desc, stream);
+int sp_pairs_cost(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int mode, float irls_eps,
+                  float* partials, float* seg_partials, void* stream) {
+    return sp_pairs_cost_opt(pairs, chunks, spans, n_spans, mode, irls_eps, partials, seg_partials, nullptr, nullptr, nullptr, stream);
 }
 
 }  // extern "C"
 
 // the cost pass (mode 2: the window optimiser's, or 0 / 1) over n_lists work lists of different batches in ONE launch
 int cost_pairs_multi(const MultiList* lists_dev, int n_lists, int total_blocks, int mode, float irls_eps, void* stream) {
-    if (!lists_dev || n_lists <= 0 || total_blocks <= 0 || (mode != 0 && mode != 1 && mode != 2)) return SP_EINVAL;
+    if (!lists_dev || n_lists <= 0 || total_blocks <= 0) return SP_EINVAL;
     FuseArgs f{};
     f.multi = lists_dev; f.n_multi = n_lists;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const SpPair* np = nullptr; const int4* n4 = nullptr; float* nf = nullptr;
-    if (mode == 2) hipLaunchKernelGGL(k_cost_pairs<2>, dim3(total_blocks), dim3(SP_BLOCK), 0, s, np, n4, n4, 0, irls_eps, nf, nf, f);
-    else if (mode == 1) hipLaunchKernelGGL(k_cost_pairs<1>, dim3(total_blocks), dim3(SP_BLOCK), 0, s, np, n4, n4, 0, irls_eps, nf, nf, f);
-    else hipLaunchKernelGGL(k_cost_pairs<0>, dim3(total_blocks), dim3(SP_BLOCK), 0, s, np, n4, n4, 0, irls_eps, nf, nf, f);
-    SP_CHECK_LAUNCH();
-    return 0;
+    return launch_cost(CostVariant{mode, false, false, false, 0}, total_blocks, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, 0, irls_eps,
+                       nullptr, nullptr, f);
 }
 
 extern "C" {
@@ -1474,6 +1409,15 @@ extern "C" {
 int sp_pairs_schedule_cost(const SpSchedule* sched, const int32_t* phase, void* stream) { return schedule_cost_from(sched, phase, stream, 0, nullptr, 0, nullptr, 0, 0u); }
 
 }  // extern "C"
+
+namespace {
+// the Gauss-Newton pass of a schedule over the work list of phase `ph` (f.sched.n_lists > 0: over several lists of its kind -- wave
+// spans or workgroup spans, depth tables or log-depth tables)
+int launch_phase(const SpPhase& ph, int n_spans, int blocks, hipStream_t s, const FuseArgs& f) {
+    const CostVariant v{1, (ph.flags & SP_PHASE_DEPTH_TABLE) != 0, (ph.flags & SP_PHASE_WAVE_SPANS) != 0, false, 0};
+    return launch_cost(v, blocks, s, ph.pairs, ph.chunks, ph.spans, n_spans, ph.irls_eps, ph.span_partials, ph.seg_partials, f);
+}
+}  // namespace
 
 // first_phase: a phase every pair is known to have reached (pairs only move forward): work lists none of whose phases is at or
 // beyond it have no pair left and are not launched -- two of the three launches of a frame-pair schedule's iteration through
@@ -1525,17 +1469,6 @@ int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stre
     }
     if (n_leads == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto blocks_of = [&](const SpPhase& ph, int n_spans) { return (ph.flags & SP_PHASE_WAVE_SPANS) ? ((((n_spans + 3) / 4) + 7) / 8) * 8 : ((n_spans + 7) / 8) * 8; };
-    // the four kinds of a scheduled Gauss-Newton pass: wave spans or workgroup spans, depth tables or log-depth tables
-    const auto launch_sched = [&](const SpPhase& lead, int n_spans, int blocks) {
-        const int4* c4 = reinterpret_cast<const int4*>(lead.chunks);
-        const int4* s4 = reinterpret_cast<const int4*>(lead.spans);
-        const bool w64 = (lead.flags & SP_PHASE_WAVE_SPANS) != 0, dt = (lead.flags & SP_PHASE_DEPTH_TABLE) != 0;
-        if (w64 && dt) hipLaunchKernelGGL((k_cost_pairs<1, 6, 0, true>), dim3(blocks), dim3(SP_BLOCK), 0, s, lead.pairs, c4, s4, n_spans, lead.irls_eps, lead.span_partials, lead.seg_partials, f);
-        else if (w64) hipLaunchKernelGGL((k_cost_pairs<1, 0, 0, true>), dim3(blocks), dim3(SP_BLOCK), 0, s, lead.pairs, c4, s4, n_spans, lead.irls_eps, lead.span_partials, lead.seg_partials, f);
-        else if (dt) hipLaunchKernelGGL((k_cost_pairs<1, 6>), dim3(blocks), dim3(SP_BLOCK), 0, s, lead.pairs, c4, s4, n_spans, lead.irls_eps, lead.span_partials, lead.seg_partials, f);
-        else hipLaunchKernelGGL(k_cost_pairs<1>, dim3(blocks), dim3(SP_BLOCK), 0, s, lead.pairs, c4, s4, n_spans, lead.irls_eps, lead.span_partials, lead.seg_partials, f);
-    };
     bool same_kind = n_leads <= SP_SCHED_LISTS;
     for (int i = 1; i < n_leads; ++i) same_kind = same_kind && !((sched->phase[leads[i].p].flags ^ sched->phase[leads[0].p].flags) & (SP_PHASE_WAVE_SPANS | SP_PHASE_DEPTH_TABLE));
     if (n_leads > 1 && same_kind) {
@@ -1545,20 +1478,17 @@ int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stre
             const SpPhase& ph = sched->phase[leads[i].p];
             f.sched.list[i] = SchedList{reinterpret_cast<const int4*>(ph.chunks), reinterpret_cast<const int4*>(ph.spans), ph.span_partials, ph.seg_partials,
                                         leads[i].n_spans, total, leads[i].mask, leads[i].vspans};
-            total += blocks_of(ph, leads[i].n_spans);
+            total += cost_blocks(leads[i].n_spans, (ph.flags & SP_PHASE_WAVE_SPANS) != 0);
         }
         f.sched.n_lists = n_leads;
-        const SpPhase& lead = sched->phase[leads[0].p];
-        launch_sched(lead, leads[0].n_spans, total);
-        SP_CHECK_LAUNCH();
-        return 0;
+        return launch_phase(sched->phase[leads[0].p], leads[0].n_spans, total, s, f);
     }
     for (int i = 0; i < n_leads; ++i) {
         const SpPhase& lead = sched->phase[leads[i].p];
         f.sched.mask = leads[i].mask;
         f.sched.vspans = leads[i].vspans;
-        launch_sched(lead, leads[i].n_spans, blocks_of(lead, leads[i].n_spans));
-        SP_CHECK_LAUNCH();
+        const int rc = launch_phase(lead, leads[i].n_spans, cost_blocks(leads[i].n_spans, (lead.flags & SP_PHASE_WAVE_SPANS) != 0), s, f);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -1574,11 +1504,8 @@ int sp_pairs_adam_iterate(const SpPair* pairs, const int32_t* chunks, const int3
     FuseArgs f{};
     f.arrivals = arrivals;
     f.adam = AdamArgs{max_N, lr_kld, lr_pose, lr_aff, state, losses};
-    const int gx = ((n_spans + 7) / 8) * 8;
-    hipLaunchKernelGGL((k_cost_pairs<0, 0, 1>), dim3(gx), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), pairs,
-                       reinterpret_cast<const int4*>(chunks), reinterpret_cast<const int4*>(spans), n_spans, 0.f, partials, seg_partials, f);
-    SP_CHECK_LAUNCH();
-    return 0;
+    return launch_cost(CostVariant{0, false, false, false, 1}, cost_blocks(n_spans, false), static_cast<hipStream_t>(stream), pairs, chunks, spans, n_spans,
+                       0.f, partials, seg_partials, f);
 }
 
 int sp_pairs_gn_iterate(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int n_pairs, int max_N,
@@ -1590,11 +1517,8 @@ int sp_pairs_gn_iterate(const SpPair* pairs, const int32_t* chunks, const int32_
     FuseArgs f{};
     f.arrivals = arrivals;
     f.gn = GnArgs{max_N, lm_up, lm_down, lm_min, lm_state, backup, costs, 0.f, nullptr, nullptr, nullptr, 0, 0, 0};
-    const int gx = ((n_spans + 7) / 8) * 8;
-    hipLaunchKernelGGL((k_cost_pairs<1, 0, 2>), dim3(gx), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), pairs,
-                       reinterpret_cast<const int4*>(chunks), reinterpret_cast<const int4*>(spans), n_spans, irls_eps, partials, seg_partials, f);
-    SP_CHECK_LAUNCH();
-    return 0;
+    return launch_cost(CostVariant{1, false, false, false, 2}, cost_blocks(n_spans, false), static_cast<hipStream_t>(stream), pairs, chunks, spans, n_spans,
+                       irls_eps, partials, seg_partials, f);
 }
 
 }  // extern "C"

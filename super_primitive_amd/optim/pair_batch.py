@@ -518,16 +518,17 @@ class PairBatch:
         self.lm_state[:, 1] = -1.0
 
     # ------------------------------------------------------------------------------------------------
-    def cost_pass(self, level, mode, irls_eps=1e-3):
+    def cost_pass(self, level, mode, irls_eps=1e-3, done=None):
+        """The cost pass of every pair at pyramid ``level`` into self.partials / self.seg_partials (mode 0: cost + gradient, 1: Gauss-Newton
+        sums, 2: those with the affine pair).  ``done``: (M,) int32, spans of marked pairs are skipped.  Modes 0 and 1 read the pixel words
+        from the run descriptors where the batch has them."""
         if mode not in (0, 1) and self.table_flag:
-            raise ValueError("cost mode 2 and the developer modes read log-depth tables: build the batch with depth_table=False")
-        if self.run_desc is not None and mode in (0, 1):
-            _lib.check(self.lib.sp_pairs_cost_rd(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, mode | self.wave_flag | self.table_flag,
-                                                 float(irls_eps), _lib.ptr(self.partials), _lib.ptr(self.seg_partials), _lib.ptr(self.pix),
-                                                 _lib.ptr(self.run_desc), _lib.stream_ptr()), "sp_pairs_cost_rd")
-            return
-        _lib.check(self.lib.sp_pairs_cost(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, mode | self.wave_flag | (self.table_flag if mode in (0, 1) else 0),
-                                          float(irls_eps), _lib.ptr(self.partials), _lib.ptr(self.seg_partials), _lib.stream_ptr()), "sp_pairs_cost")
+            raise ValueError("cost mode 2 reads log-depth tables: build the batch with depth_table=False")
+        rd = self.run_desc is not None and mode in (0, 1)
+        _lib.check(self.lib.sp_pairs_cost_opt(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans,
+                                              mode | self.wave_flag | (self.table_flag if mode in (0, 1) else 0), float(irls_eps), _lib.ptr(self.partials),
+                                              _lib.ptr(self.seg_partials), _lib.ptr(done), _lib.ptr(self.pix if rd else None),
+                                              _lib.ptr(self.run_desc if rd else None), _lib.stream_ptr()), "sp_pairs_cost_opt")
 
     def gn_step(self, level=0, irls_eps=1e-3, lm_up=8.0, lm_down=0.5, lm_min=1e-7, fused=False, conv_tol=0.0):
         """One Gauss-Newton/LM iteration of every pair at pyramid ``level``.  Returns the (M,) device tensor of costs
@@ -545,15 +546,7 @@ class PairBatch:
             return self._costs
         if conv_tol > 0.0:
             # per-pair convergence on the device: pairs in self.done are skipped by both launches (``run(conv_tol=...)``)
-            if self.run_desc is not None:
-                _lib.check(self.lib.sp_pairs_cost_rd_active(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans,
-                                                            1 | self.wave_flag | self.table_flag, float(irls_eps), _lib.ptr(self.partials),
-                                                            _lib.ptr(self.seg_partials), _lib.ptr(self.done), _lib.ptr(self.pix), _lib.ptr(self.run_desc),
-                                                            _lib.stream_ptr()), "sp_pairs_cost_rd_active")
-            else:
-                _lib.check(self.lib.sp_pairs_cost_active(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, 1 | self.wave_flag | self.table_flag,
-                                                         float(irls_eps), _lib.ptr(self.partials), _lib.ptr(self.seg_partials),
-                                                         _lib.ptr(self.done), _lib.stream_ptr()), "sp_pairs_cost_active")
+            self.cost_pass(level, 1, irls_eps, done=self.done)
             _lib.check(self.lib.sp_pairs_gn_step_conv(_lib.ptr(self.desc[level]), self.M, self.max_N, _lib.ptr(self.partials),
                                                       _lib.ptr(self.seg_partials), float(lm_up), float(lm_down), float(lm_min),
                                                       _lib.ptr(self.lm_state), _lib.ptr(self.backup), _lib.ptr(self._costs),

@@ -34,9 +34,9 @@ def _call(arr, n):
 
 def test_multi_symbol_and_abi():
     L, lib = _lib()
-    assert L.SP_ABI_VERSION == 17 and lib.sp_abi_version() == 17
+    assert L.SP_ABI_VERSION == 18 and lib.sp_abi_version() == 18
     assert hasattr(ctypes.CDLL(L.LIB_PATH), "sp_chain_step_multi")
-    assert not hasattr(ctypes.CDLL(L.LIB_PATH), "sp_chain_step")             # (ABI 17: one sequence is the multi call at n_steps = 1)
+    assert not hasattr(ctypes.CDLL(L.LIB_PATH), "sp_chain_step")             # (since ABI 17: one sequence is the multi call at n_steps = 1)
     assert lib.sp_chain_multi_bytes() > 0
 
 

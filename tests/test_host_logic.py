@@ -21,7 +21,10 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION
+    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == 18
+    # (ABI 18: sp_pairs_cost_opt is the one extended cost entry point)
+    for retired in ("sp_pairs_cost_active", "sp_pairs_cost_rd", "sp_pairs_cost_rd_active"):
+        assert not hasattr(lib, retired), retired
     # argument counts of the ctypes table match the prototypes
     for name in declared:
         proto = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1).strip()
@@ -123,6 +126,17 @@ def test_entry_points_reject_bad_arguments_without_a_gpu():
     from super_primitive_amd import _lib
     lib = _lib.load()
     assert lib.sp_pairs_cost(None, None, None, 0, 0, 0.0, None, None, None) == -1
+    # the retired developer modes: refused on the mode alone (dummy non-null pointers are never dereferenced, nothing is launched)
+    dummy = ctypes.c_void_p(ctypes.addressof(ctypes.create_string_buffer(256)))
+    for mode in range(10, 19):
+        assert lib.sp_pairs_cost(dummy, dummy, dummy, 1, mode, 1e-3, dummy, dummy, None) == -1, mode
+        assert lib.sp_pairs_cost_opt(dummy, dummy, dummy, 1, mode, 1e-3, dummy, dummy, None, None, None, None) == -1, mode
+    # run descriptors: both pointers or neither, and only for modes 0 / 1 on wave-span depth tables
+    wd = _lib.SP_COST_WAVE_SPANS | _lib.SP_COST_DEPTH_TABLE
+    assert lib.sp_pairs_cost_opt(dummy, dummy, dummy, 1, 1 | wd, 1e-3, dummy, dummy, None, dummy, None, None) == -1
+    for mode in (1, 1 | _lib.SP_COST_WAVE_SPANS, 1 | _lib.SP_COST_DEPTH_TABLE, 2 | wd):
+        assert lib.sp_pairs_cost_opt(dummy, dummy, dummy, 1, mode, 1e-3, dummy, dummy, None, dummy, dummy, None) == -1, mode
+    assert lib.sp_pairs_cost(dummy, dummy, dummy, 1, 2 | _lib.SP_COST_DEPTH_TABLE, 1e-3, dummy, dummy, None) == -1
     assert lib.sp_blur_decimate(None, 3, 10, 10, None, None) == -1
     assert lib.sp_renormalise_se3(None, 1, None) == -1
     with pytest.raises(RuntimeError, match="SP_EINVAL"):

@@ -28,7 +28,7 @@ def main():
                                                      "blocks (developer experiment on the table order; 0 = restore row-major)")
     a = ap.parse_args()
     if any(int(x) >= 2 for x in a.modes.split(",")):
-        a.no_depth_table = True          # (mode 2 and the developer modes read log-depth tables)
+        a.no_depth_table = True          # (mode 2 reads log-depth tables)
     dev = torch.device("cuda:0")
     batch, _ = bench.build_batch(a, 0, dev)
     for _ in range(3):
@@ -79,18 +79,6 @@ def main():
         print(f"--- table order: {order} x {order} pixel blocks inside every chunk" if order else "--- table order: row-major")
       for level in [int(x) for x in a.levels.split(",")]:
         for mode in [int(x) for x in a.modes.split(",")]:
-              if mode == 16:
-                  # developer mode 16 (sp_cost.hip ABL 5): no pix stream -- the pixel word rides in the low mantissa bits of the
-                  # point's own colours (7 + 7 + 6 bits; colours change by < 2^-16 relative, irrelevant for a timing experiment)
-                  assert bench.W <= 1024 and bench.H <= 512
-                  keep = batch.src4[level].clone()
-                  w = batch.pix.view(torch.int32).long() & 0xffffffff
-                  v = (w & 0x3ff) | (((w >> 16) & 0x1ff) << 10) | ((w >> 31) << 19)
-                  q = batch.src4[level].view(-1, 4).view(torch.int32)
-                  q[:, 0] = ((q[:, 0].long() & ~0x7f) | (v & 0x7f)).int()
-                  q[:, 1] = ((q[:, 1].long() & ~0x7f) | ((v >> 7) & 0x7f)).int()
-                  q[:, 2] = ((q[:, 2].long() & ~0x3f) | ((v >> 14) & 0x3f)).int()
-                  del w, v
               for _ in range(3):
                   batch.cost_pass(level, mode)
               ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
@@ -100,9 +88,6 @@ def main():
               torch.cuda.synchronize()
               ms = np.array([e0.elapsed_time(e1) for e0, e1 in ev])
               by = batch.algorithmic_bytes(level)
-              if mode == 16:
-                  batch.src4[level].copy_(keep)
-                  del keep
               print(f"level {level} mode {mode} pairs {batch.M} spans {batch.n_spans}: median {np.median(ms)*1e3:.1f} us  min {ms.min()*1e3:.1f} us  "
                     f"alg {by/1e6:.1f} MB -> {by/np.median(ms)/1e6:.0f} GB/s ({by/np.median(ms)/1e6/8000*100:.1f}% of 8 TB/s)  "
                     f"{sum(batch.Ps)/np.median(ms)/1e6:.2f} Gpt/s")

@@ -1,14 +1,15 @@
 #!/usr/bin/env python
 """Developer tool: package power and shader clock (rocm-smi, 4 Hz) while sp_pairs_cost runs back to back in one mode.
-    python tools/power_by_mode.py --modes 1,11,13,0 [--seconds 6]
-modes: 1 = GN pass, 0 = gradient pass, 11 / 10 = the same without the target gathers, 13 / 12 = loads + geometry only."""
+    python tools/power_by_mode.py --modes 1,0 [--seconds 6]
+modes: 1 = GN pass, 0 = gradient pass.  (profiles/r02_power_by_mode.txt also lists the ablation modes 11, 13 and 14, which the library
+had then.)"""
 import argparse, os, subprocess, sys, threading, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--modes", default="1,14,11,13")
+ap.add_argument("--modes", default="1,0")
 ap.add_argument("--seconds", type=float, default=6.0)
 ap.add_argument("--pairs", type=int, default=384)
 a = ap.parse_args()
