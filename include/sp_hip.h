@@ -794,6 +794,36 @@ int sp_build_part_masks(const uint8_t* masks, const uint8_t* split, const int32_
 int sp_kth_mask_pixel(const uint8_t* masks, const int32_t* row_off, int K, int H, int W, const int32_t* kth,
                       int32_t* out_rc, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Normal integration (the stage in front of N2): frontend/normals/normals_integration.py:7-28
+ * run_tiled_normal_integration as frontend/process_frame.py:78-92 calls it -- per-segment log-depth, right up to one
+ * constant per connected component, from surface normals.  The reference's solver is an un-vendored cupy submodule, so
+ * the arithmetic is the definition in DESIGN.md §4: with ax = nx (c - cx) + ny (r - cy) fx / fy + nz fx and
+ * ay = nx (c - cx) fy / fx + ny (r - cy) + nz fy, every pair of horizontally (vertically) adjacent mask pixels p, q is an
+ * edge of weight w = (a_p^2 + a_q^2) / 2 with t = -(a_p n_p + a_q n_q) / 2 (a, n = ax, nx or ay, ny); (L u)_p = sum_e
+ * w_e (u_p - u_other), b_q += t, b_p -= t; plain conjugate gradients on L u = b from u = 0, stopped PER SEGMENT once the
+ * recursively updated residual has |r_k| <= cg_tol |b|, or after cg_max_iter iterations (|b| = 0: no iteration).
+ *
+ *   normals (H,W,3) float, camera frame x right / y down / z forward (the sign of a normal does not matter);
+ *   K row-major 3x3 (device); masks (N,H,W) u8; boxes_or_null (N,4) int32 {row0, col0, row1, col1} half open, a HINT
+ *   (KeyFrame.segment_boxes): no mask pixel lies outside it.  It only narrows the scan -- the solve always works on the
+ *   tight box, so results are bitwise the same with and without it, and a segment's result does not depend on the
+ *   other segments of the call.  flags: 0 (reserved).
+ *   depth (N,H,W) float: exp(u) on the mask (u clamped to +-15, so every mask pixel passes process_frame.py:234's
+ *   `> 1e-7`), 0 elsewhere -- every element is written.  info (N,2) float: {iterations used, final recursive |r| / |b|};
+ *   iterations = -1 marks a segment whose vectors did not fit the scratch (its depth is 0).
+ *   scratch: scratch_floats floats = sp_normal_integration_plan_words(N) + the vector area.  The vector area is at most
+ *   N * sp_normal_integration_segment_floats(H, W); the exact need (6 vectors over every segment's padded tight box) is
+ *   what sp_normal_integration_plan leaves in plan[0..1] as one int64 (plan: sp_normal_integration_plan_words(N) int32).
+ * One workgroup solves one segment (largest first); nothing synchronises the host.
+ * ---------------------------------------------------------------------------------------------------- */
+int sp_normal_integration_plan_words(int N);
+int sp_normal_integration_segment_floats(int H, int W);
+int sp_normal_integration_plan(const uint8_t* masks, const int32_t* boxes_or_null, int N, int H, int W, int32_t* plan, void* stream);
+int sp_normal_integration(const float* normals, const float* K, const uint8_t* masks, const int32_t* boxes_or_null, int N, int H,
+                          int W, int cg_max_iter, float cg_tol, int flags, float* scratch, long long scratch_floats, float* depth,
+                          float* info, void* stream);
+
 /* odometery/kf_criteria.py:7-21 translation_difference, :23-34 rotation_difference and the depth-validity ratio of
  * odometery/odometery.py:1003-1004, in one launch without a host sync.  depth: n floats (the rendered depth of the
  * latest keyframe); poses row-major 4x4.  out[4] = {#(depth > thresh)/n, scale = lower median of the valid depths

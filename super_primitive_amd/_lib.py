@@ -81,6 +81,10 @@ SIGNATURES = {
     "sp_collect_parts": [P, P, P, P, I, I, I, I, P, P, P, P],
     "sp_build_part_masks": [P, P, P, I, I, P, I, P, P],
     "sp_kth_mask_pixel": [P, P, I, I, I, P, P, P],
+    "sp_normal_integration_plan_words": [I],
+    "sp_normal_integration_segment_floats": [I, I],
+    "sp_normal_integration_plan": [P, P, I, I, I, P, P],
+    "sp_normal_integration": [P, P, P, P, I, I, I, I, F, I, P, ctypes.c_longlong, P, P, P],
 }
 
 SP_ABI_VERSION = 18

@@ -1,0 +1,43 @@
+"""A keyframe from masks and normals: the network-free part of the reference's ``FrontProcessorNew.process_to_kf``
+(``frontend/process_frame.py:78-92,231-250``).  SAM and the normals network stay out of scope; when their outputs come from
+elsewhere, this is what a ``to_keyframe`` callback of ``run_sequence`` or ``DepthCompletion``'s ``front_processor`` is built from.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
+
+from ..image.keyframe import KeyFrame, put_keypoints_back
+from ..optim.batch_prepare import segment_boxes_of
+from .normals.normals_integration import _device_K, integrate_normals
+from .segment.post_processer import kf_fix_disconnected_regions
+
+
+def keyframe_from_normals(image, K, normals, masks, keypoints, *, cg_max_iter=1000, cg_tol=1e-3, split_disconnected=True,
+                          depth_disc_params=None):
+    """``KeyFrame`` of ``image`` (C,H,W) with intrinsics ``K`` from ``normals`` (h,w,3), ``masks`` (N,h,w) and normalised (row, col)
+    ``keypoints`` (N,2).  (h,w) is the integration size; when it differs from (H,W) the intrinsics are scaled to it for the
+    integration and the integrated depth is brought to (H,W) by nearest resize, as process_frame.py:132-134,231-233 do.
+
+    process_frame.py:234-250: ``masks = depth > 1e-7``, ``put_keypoints_back``, ``log``, ``KeyFrame``, then -- with
+    ``split_disconnected`` -- ``kf_fix_disconnected_regions`` (``depth_disc_params``: its ``filter_size``, ``depth_threshold``,
+    ``area_keep_ratio``).  ``segment_boxes`` of the result is filled in."""
+    with torch.no_grad():
+        H, W = image.shape[-2:]
+        h, w = masks.shape[-2:]
+        dev = masks.device
+        K_kf = _device_K(K, dev)
+        K_geom = K_kf.clone()
+        K_geom[0] = K_geom[0] * (w / W)
+        K_geom[1] = K_geom[1] * (h / H)
+        depth = integrate_normals(normals, K_geom, masks, cg_max_iter=cg_max_iter, cg_tol=cg_tol)
+        if (h, w) != (H, W):
+            depth = F.interpolate(depth[:, None], size=(H, W), mode='nearest')[:, 0]
+        regions = depth > 1e-7
+        keypoints, regions, depth = put_keypoints_back(keypoints.to(dev), regions, depth)
+        logdepth = torch.where(regions, torch.log(depth.clamp_min(1e-30)), torch.zeros_like(depth))
+        kf = KeyFrame(image, K=K_kf, logdepth_perseg=logdepth, keypoints=keypoints, keypoint_regions=regions)
+        if split_disconnected:
+            kf = kf_fix_disconnected_regions(kf, **(depth_disc_params or {}))
+        kf.segment_boxes = segment_boxes_of(kf.keypoint_regions)
+    return kf

@@ -314,6 +314,14 @@ def observable_segments(p, min_points=16):
     return (p.keypoint_regions & ok[None]).reshape(p.N, -1).sum(1) >= min_points
 
 
+def plane_normals(pair):
+    """(H,W,3) f32 per-pixel surface normals of ``pair``'s scene in the source camera frame -- the plane's unit normal, the first
+    draw of ``make_pair``'s generator -- i.e. what a perfect normals network would hand to the normal integration."""
+    n = np.array([0.22, -0.12, 1.0]) + 0.05 * np.random.default_rng(pair.meta["seed"]).standard_normal(3)
+    n /= np.linalg.norm(n)
+    return np.broadcast_to(n.astype(np.float32), (pair.H, pair.W, 3)).copy()
+
+
 def stepped_logdepth(pair, seed=0, n_boxes=3, factor=(0.55, 0.75)):
     """Per-segment log-depths of ``pair`` after pulling a few axis-aligned boxes towards the camera: depth steps
     inside segments, the situation ``frontend/segment/post_processer.py`` exists for.  Returns (N,H,W) f32."""
