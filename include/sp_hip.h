@@ -824,6 +824,32 @@ int sp_normal_integration(const float* normals, const float* K, const uint8_t* m
                           int W, int cg_max_iter, float cg_tol, int flags, float* scratch, long long scratch_floats, float* depth,
                           float* info, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Depth completion, the stage after sp_depth_average (BASELINE config 4): depth_completion/fill_in_tools.py:5-7 fill_depth and
+ * depth_completion/void.py:7-65 ErrorMetrics / ErrorMetricsDeltas, as the evaluation loop evaluate_void.py:122-146 uses them.
+ *
+ * sp_depth_fill_nearest: depth (B,H,W) float, invalid (B,H,W) u8 (non-zero = to be filled).  Every invalid pixel (r, c) takes the
+ * value of the valid pixel (r', c') of the same image that minimises ((r - r')^2 + (c - c')^2, c', r') lexicographically -- the pixel
+ * scipy.ndimage.distance_transform_edt(invalid, return_indices=True) names, ties included; valid pixels keep theirs.  Distances are
+ * uint32 squared distances, never floats.  filled (B,H,W) float (not depth itself), index_or_null (B,H,W) int32 = r' W + c',
+ * counts (B,2) int32 = {valid pixels, pixels filled}.  An image with no valid pixel is copied through ({0, 0}, index = identity;
+ * scipy indexes row -1 there).  workspace: sp_depth_fill_workspace_bytes(B, H, W) bytes.  H, W <= 32767, B <= 65535,
+ * B H W < 2^30, else SP_ELIMIT.
+ *
+ * sp_depth_metrics: estimate, target (B,H,W) float, valid (B,H,W) u8.  out (B,12) double per image, over its valid pixels:
+ * {n, rmse, mae, absrel (1000 x the inputs: mm), inv_rmse, inv_mae, inv_absrel (of 1 / (0.001 x the inputs): 1/km), fractions of
+ * max(t / e, e / t) below 1.05, 1.10, 1.25, 1.25^2, 1.25^3}.  Per-pixel terms are fp32 with every operation rounded on its own, as
+ * numpy forms them; sums are fp64 in a fixed order (two runs agree bitwise); pixels outside valid are never read into a sum
+ * (their target may be inf); n = 0 gives NaN.  workspace: sp_depth_metrics_workspace_doubles(B, H, W) doubles.
+ * Null pointers and non-positive sizes are SP_EINVAL before any device work.
+ * ---------------------------------------------------------------------------------------------------- */
+int sp_depth_fill_workspace_bytes(int B, int H, int W);
+int sp_depth_fill_nearest(const float* depth, const uint8_t* invalid, int B, int H, int W, void* workspace, float* filled,
+                          int32_t* index_or_null, int32_t* counts, void* stream);
+int sp_depth_metrics_workspace_doubles(int B, int H, int W);
+int sp_depth_metrics(const float* estimate, const float* target, const uint8_t* valid, int B, int H, int W, double* workspace,
+                     double* out, void* stream);
+
 /* odometery/kf_criteria.py:7-21 translation_difference, :23-34 rotation_difference and the depth-validity ratio of
  * odometery/odometery.py:1003-1004, in one launch without a host sync.  depth: n floats (the rendered depth of the
  * latest keyframe); poses row-major 4x4.  out[4] = {#(depth > thresh)/n, scale = lower median of the valid depths

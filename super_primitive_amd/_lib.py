@@ -85,6 +85,10 @@ SIGNATURES = {
     "sp_normal_integration_segment_floats": [I, I],
     "sp_normal_integration_plan": [P, P, I, I, I, P, P],
     "sp_normal_integration": [P, P, P, P, I, I, I, I, F, I, P, ctypes.c_longlong, P, P, P],
+    "sp_depth_fill_workspace_bytes": [I, I, I],
+    "sp_depth_fill_nearest": [P, P, I, I, I, P, P, P, P, P],
+    "sp_depth_metrics_workspace_doubles": [I, I, I],
+    "sp_depth_metrics": [P, P, P, I, I, I, P, P, P],
 }
 
 SP_ABI_VERSION = 18

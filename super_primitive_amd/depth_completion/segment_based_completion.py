@@ -5,7 +5,8 @@ into a KeyFrame (SAM masks + integrated normals; OUT OF SCOPE here, any object w
 plugged in) -> per-segment median log-depth shift (``sp_segment_reinit``) -> per-pixel average over the
 covering visible segments (``sp_depth_average``, which fuses the dense ``unproject_kf_to_depths`` expansion, the
 ``depths[mask == 0] = -1`` masking, the visible-segment filter and ``render_depth_avg``) -> rerun with larger
-masks when more than 15 % of the pixels stay uncovered."""
+masks when more than 15 % of the pixels stay uncovered.  ``depth_completion_dense`` adds the stage the reference's evaluation
+loop runs next (evaluate_void.py:122-125): every pixel that is still uncovered takes its nearest covered pixel's depth."""
 from __future__ import annotations
 
 import copy
@@ -18,6 +19,7 @@ from ..odometery import depth_init
 from ..segment_table import table_of
 from ..tool import point_utils
 from ..tool.etc import to_np
+from .fill_in_tools import fill_depth
 
 
 def render_depth_avg(depths):
@@ -101,3 +103,18 @@ class DepthCompletion:
             depths[invalid] = depths_new[invalid]
             invalid = torch.logical_and(invalid, invalid_new)
         return to_np(depths), to_np(invalid)
+
+    def depth_completion_dense(self, image, K, partial_depth, device='cuda:0'):
+        """``(filled, depth, invalid)`` as device tensors: ``depth`` and ``invalid`` are what ``depth_completion`` returns (rerun merge
+        included), ``filled`` is ``fill_depth(depth, invalid)`` -- ``depth`` where it is valid, the nearest valid pixel's elsewhere."""
+        rows, cols = torch.where(partial_depth > 1e-6)
+        keypoints = torch.stack([rows, cols], dim=1).float()
+        H, W = partial_depth.shape
+        keypoints = point_utils.normalise_coordinates(keypoints, (H, W)).to(device)
+        depths, invalid = infer_depth(self.front_processor, image, keypoints, K, partial_depth)
+        ratio = invalid.sum().float() / (invalid.shape[0] * invalid.shape[1])
+        if ratio > 0.15:
+            depths_new, invalid_new = infer_depth(self.front_processor, image, keypoints, K, partial_depth, rerun=True)
+            depths[invalid] = depths_new[invalid]
+            invalid = torch.logical_and(invalid, invalid_new)
+        return fill_depth(depths, invalid), depths, invalid
