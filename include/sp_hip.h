@@ -348,7 +348,17 @@ int sp_pairs_adam_step(const SpPair* pairs, int n_pairs, int max_N, const float*
  * evaluation / P, and -- schedules only -- how the pair's last finished phase ended: +iterations = on its cap, -iterations = by
  * its convergence test};
  * lambda adapts on device (cost up -> step undone from the backup, lambda*=lm_up, re-evaluated next call;
- * cost down -> lambda = max(lambda*lm_down, lm_min)).  backup: per pair (16+max_N) floats.  costs: [n_pairs]. */
+ * cost down -> lambda = max(lambda*lm_down, lm_min)).  backup: per pair (16+max_N) floats.  costs: [n_pairs].
+ * One call, in full (tests/gn_step_ref.py restates it in float64; tests/test_gpu_gn_step.py holds the device to it):
+ *   cost = sum|r| / (3 P) is written to costs and lm_state[5] (valid points / P to [6]) by every call that looks at the pair.
+ *   REJECT iff a last accepted cost exists, cost > last * (1 + 1e-6) and the previous call did not reject: pose and log-depths come
+ *     back from the backup bit for bit, lambda *= lm_up, [3] += 1, [4] = 1; nothing else moves.
+ *   Otherwise a STEP: lambda = max(lambda * lm_down, lm_min) unless the previous call rejected (so the first call lowers it too); the
+ *     point is copied to the backup (pose, then the pair's N log-depths: the rest of the slot is never written); the system is damped as
+ *     H_pp + lambda diag(H_pp) + 1e-12 I and D (1 + lambda); a segment whose damped D is <= 1e-12 (no valid point) is no unknown: it
+ *     stays where it is and does not enter the pose block; every log-depth step is clamped to +-0.5; [1] = cost, [2] += 1, [4] = 0.
+ *     When the pose block is not positive definite after the elimination (a failed LDL^T pivot) the pose stays where it is, every
+ *     log-depth still takes its own clamped step -b_d / D', and the call counts as an accepted step like any other. */
 #define SP_LM_STATE_FLOATS 8
 int sp_pairs_gn_step(const SpPair* pairs, int n_pairs, int max_N, const float* span_partials, const float* seg_partials,
                      float lm_up, float lm_down, float lm_min, float* lm_state, float* backup, float* costs, void* stream);
