@@ -663,8 +663,13 @@ int sp_window_step(const SpPair* pairs, const SpWindowEdge* edges, int n_edges, 
  * Bit 2 (ABI 14): the caller's word that NO depth block moves (every SpWindowBlock.lr is 0: frame-to-keyframe tracking) -- like bit 0 the
  * Schur-term launch is then left out (its terms are all zero): three launches per iteration instead of four.
  * LM: lambda adapts on the device exactly like sp_pairs_gn_step (loss up -> previous step undone from nodes_backup / kld_backup,
- * lambda *= lm_up, re-evaluated next call; loss down -> lambda = max(lambda lm_down, lm_min); a failed factorisation counts as a
- * rejected step: lambda *= lm_up, the same point is evaluated and solved again); conv_tol > 0: an accepted step that
+ * lambda *= lm_up, re-evaluated next call; loss down -> lambda = max(lambda lm_down, lm_min)).  A FAILED FACTORISATION (a pivot of the
+ * reduced camera system <= 0 at this damping) moves no unknown, neither camera nor log-depth: lambda *= lm_up, state[8] += 1 and the
+ * rejected-last flag state[4] = 1, so that the next call solves the same point again without a convergence test and without lowering
+ * lambda; state[2] (accepted) and state[3] (rejected) both stay, state[1] takes this call's loss and the backups this point (which is the
+ * point the call leaves: a later reject restores it), the loss is recorded and the iteration counted, the edges' slots are re-composed;
+ * the predicted exit does not look at such a call.  One call in full: tests/window_gn_step_ref.py restates it in float64,
+ * tests/test_gpu_window_gn_step.py holds the device to it.  conv_tol > 0: an accepted step that
  * lowered the loss by less than conv_tol * loss freezes the window (later calls return at once), like the relative-loss break at
  * odometery.py:907-915.
  * n_unknowns: the camera unknowns of the window (6 per node with lr_pose > 0 + 2 per node with lr_aff > 0), which sizes the scratch

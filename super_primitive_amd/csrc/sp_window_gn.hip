@@ -9,15 +9,19 @@
 //                      window is full (:594-603); every pose folded in T <- T inv(Exp(D)) and renormalised after the step (:861-882)
 //
 // but the step is a damped Newton step on the IRLS-weighted normal equations instead of Adam: ~10 iterations where Adam takes 300-500.
-// One iteration = sp_pairs_cost(mode 2) over all edges  ->  sp_window_gn_step = two launches:
+// One iteration = sp_pairs_cost(mode 2) over all edges  ->  sp_window_gn_step = three launches (two when no depth may move, flags bits 0 / 2:
+// no Schur terms; one when such a window has at most SP_WGN_INLINE_EDGES edges and 64 unknowns: the update kernel reduces them itself):
 //
 //   k_window_gn_reduce (grid = edges)   fixed-order fp64 reduction of an edge's span / segment records into its local system over
 //                                       z_e = [xi_e (left tangent of the edge's relative pose), a_e, b_e] and its source keyframe's depths
-//   k_window_gn_update (one workgroup)  LM accept / undo against the previous point; chain rule z_e = G_t y_t + G_s y_s onto the node
-//                                       unknowns y = [d (6), a, b] (G_t = I; G_s = -blockdiag(Ad_P, I_2) since P = Exp(d_t) M Exp(-d_s) =
-//                                       Exp(d_t - Ad_M d_s) M); assembly of the reduced camera system in LDS (<= 128 unknowns, fp64);
-//                                       Schur complement of the per-segment depth unknowns; Cholesky; back-substitution; fold-in,
-//                                       renormalisation; relative poses and affine slots of every edge for the next cost pass.
+//                                       and, through the chain rule z_e = G_t y_t + G_s y_s onto the node unknowns y = [d (6), a, b] (G_t = I;
+//                                       G_s = -blockdiag(Ad_P, I_2) since P = Exp(d_t) M Exp(-d_s) = Exp(d_t - Ad_M d_s) M), its 16 x 16 block
+//   k_window_gn_schur (blocks x tiles)  per source keyframe: the coupling rows C of its depth unknowns over the camera unknowns it meets,
+//                                       D^-1 with the LM damping, and its Schur term C^T D^-1 C, 2 x 256 pairs per workgroup
+//   k_window_gn_update (one workgroup)  LM accept / undo against the previous point; assembly of the reduced camera system (fp64, packed
+//                                       triangle: in LDS in the 64 / 128 / 192-unknown instantiations, in global scratch up to 512);
+//                                       minus the Schur terms; blocked LDL^T; substitution by one wave; clamped depth back-substitution;
+//                                       fold-in, renormalisation; relative poses and affine slots of every edge for the next cost pass.
 // No host synchronisation; the loss history and the converged flag live on the device like in sp_window_step.
 #include "sp_solve_device.h"
 #include <algorithm>
