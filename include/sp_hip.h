@@ -524,13 +524,22 @@ int sp_pairs_schedule_gn_step(const SpSchedule* sched, int n_pairs, int max_N, f
                               void* stream);
 
 /* The host loop of a scheduled run, natively: issues (sp_pairs_schedule_cost, sp_pairs_schedule_gn_step) up to max_rounds times and,
- * every check_every iterations, reads min(phase) back (one tiny kernel, a 4-byte copy into flag_host -- PINNED host memory -- and a
- * synchronisation of `stream` only) to stop once every pair has finished; work lists whose phases all lie behind that minimum are
- * no longer launched (pairs only move forward).  One foreign call per scheduled run instead of ~100: a
+ * every check_every iterations, polls the pairs' phases (one tiny kernel, a copy of five int32 into flag_host -- PINNED host memory --
+ * and a synchronisation of `stream` only) to stop once every pair has finished; work lists whose phases all lie behind the minimum
+ * are no longer launched (pairs only move forward).  One foreign call per scheduled run instead of ~100: a
  * Python caller issues nothing per iteration, so several batches can run their schedules from several host threads without
  * contending for the interpreter lock (optim/pair_stream.py), and the launch-bound tail of a schedule runs at the rate of the
- * runtime's launch path.  flag_dev / flag_host: EIGHT int32 each (device scratch / pinned host memory; ABI 13: {min phase, queue head, attempts left, busy slots, occupied phases, ...}).  Returns the number of iterations launched (>= 0), SP_EINVAL, or
- * -(1000 + hipError_t) for a runtime error.  This is the one entry point that synchronises the host (with `stream` only). */
+ * runtime's launch path.
+ * flag_dev / flag_host: EIGHT int32 each (device scratch / pinned host memory).  THE POLL RECORD is the first five:
+ *   [0] min(phase) over the pairs (slots)        [1] the queue's head (queue runs; else 0)
+ *   [2] 1 when an unfinished pair has an attempt left (verdict runs with a second / third attempt)
+ *   [3] how many pairs (slots) are still in a phase       [4] bit p set: phase p holds a pair        [5..7] spare
+ * max_rounds: the run ends there whatever the pairs' state (SP_STATUS_UNFINISHED).  Until its first poll -- the first check_every
+ * rounds -- this run takes every phase for occupied (the caller set the phases), while sp_pairs_schedule_run_queue takes only the
+ * ENTRY phase for occupied (every slot starts there): a slot the caller put into an SP_PHASE_ADAM phase sits those rounds out, and
+ * they count towards max_rounds -- as do the rounds a pair that restarts into such a phase waits for the next poll to see it.
+ * Returns the number of iterations launched (>= 0), SP_EINVAL, or -(1000 + hipError_t) for a runtime error.  This and
+ * sp_pairs_schedule_run_queue (the same host loop) are the entry points that synchronise the host (with `stream` only). */
 int sp_pairs_schedule_run(const SpSchedule* sched, int n_pairs, int max_N, float lm_up, float lm_down, float lm_min,
                           float* lm_state, float* backup, float* costs, int32_t* phase, int32_t* iters, int check_every,
                           int max_rounds, int32_t* flag_dev, int32_t* flag_host, const SpVerdict* verdict /* or NULL */, void* stream);
@@ -550,8 +559,9 @@ int sp_pairs_schedule_run(const SpSchedule* sched, int n_pairs, int max_N, float
  * empty: no launch works on a thinning batch except the very last ones.  Which pair lands in which slot depends on timing; every
  * pair's result does not (pairs never interact; bitwise what the pair gives with all pairs resident).  slot_pair: device [n_slots],
  * initialised 0..n_slots-1.  phase[p].n_spans is ignored (n_slots * max_spans[p] virtual spans are launched).
- * flag_dev / flag_host: EIGHT int32 each (min phase, queue head, attempts left, busy slots, bit mask of the phases that hold a pair, spare).  Otherwise as sp_pairs_schedule_run; pairs still in a slot when the
- * run ends on max_rounds get SP_STATUS_UNFINISHED in verdict->status (when given) and their state as it is. */
+ * flag_dev / flag_host, max_rounds and everything else: as sp_pairs_schedule_run (the poll record is taken over the slots; before the
+ * first poll only the entry phase counts as occupied, see there); pairs still in a slot when the run ends on max_rounds get
+ * SP_STATUS_UNFINISHED in verdict->status (when given) and their state as it is. */
 typedef struct SpQueue {
     const SpPair* qpairs[SP_MAX_PHASES];
     SpPair* slot_pairs[SP_MAX_PHASES];

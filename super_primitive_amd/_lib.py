@@ -286,6 +286,13 @@ def check(rc, what):
         raise RuntimeError(f"{what} failed: {kind}")
 
 
+def check_run(rc, what):
+    """``rc`` of sp_pairs_schedule_run / sp_pairs_schedule_run_queue: the rounds launched, or an error (SP_E*, -(1000 + hipError_t)) to raise."""
+    if rc < 0:
+        check(rc if rc > -1000 else -(rc + 1000), what)
+    return rc
+
+
 def ptr(t):
     """Device pointer of a tensor (or None)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())

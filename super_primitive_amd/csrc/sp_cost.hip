@@ -1406,7 +1406,7 @@ int cost_pairs_multi(const MultiList* lists_dev, int n_lists, int total_blocks, 
 
 extern "C" {
 
-int sp_pairs_schedule_cost(const SpSchedule* sched, const int32_t* phase, void* stream) { return schedule_cost_from(sched, phase, stream, 0, nullptr, 0, nullptr, 0, 0u); }
+int sp_pairs_schedule_cost(const SpSchedule* sched, const int32_t* phase, void* stream) { return schedule_cost_from(sched, phase, stream, ScheduleCostFrom{}); }
 
 }  // extern "C"
 
@@ -1419,15 +1419,10 @@ int launch_phase(const SpPhase& ph, int n_spans, int blocks, hipStream_t s, cons
 }
 }  // namespace
 
-// first_phase: a phase every pair is known to have reached (pairs only move forward): work lists none of whose phases is at or
-// beyond it have no pair left and are not launched -- two of the three launches of a frame-pair schedule's iteration through
-// its long tail (sp_pairs_schedule_run).
-// queue / n_slots: a queue run (sp_pairs_schedule_run_queue) -- every list is launched over n_slots * max_spans virtual spans.
-// active / n_active: the tail of a queue run -- only the n_active slots listed in `active` are launched over (sp_pairs_schedule_run_queue)
-// idle_mask: phases whose pairs sit this round out (the solver skips them too): work lists ALL of whose phases idle are not launched -- the
-//   fine-grained lists of the third attempt's Adam phases while no pair is in one
-int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stream, int first_phase, const SpQueue* queue, int n_slots,
-                       const int32_t* active, int n_active, uint32_t idle_mask) {
+// the cost pass of one round of a scheduled run: one launch per kind of work list that still has pairs (ScheduleCostFrom, sp_device.h)
+int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stream, const ScheduleCostFrom& from) {
+    const SpQueue* queue = from.queue;
+    int n_slots = from.n_slots;
     if (!sched || !phase || sched->n_phases <= 0 || sched->n_phases > SP_MAX_PHASES) return SP_EINVAL;
     if (queue && n_slots <= 0) return SP_EINVAL;
     for (int p = 0; p < sched->n_phases; ++p) {
@@ -1442,7 +1437,7 @@ int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stre
     uint32_t seen = 0;
     FuseArgs f{};
     f.phase = phase;
-    if (queue && active && n_active > 0) { f.active = active; n_slots = n_active; }
+    if (queue && from.active && from.n_active > 0) { f.active = from.active; n_slots = from.n_active; }
     for (int p = 0; p < sched->n_phases; ++p) {
         f.sched.pairs[p] = sched->phase[p].pairs;
         f.sched.irls_eps[p] = sched->phase[p].irls_eps;
@@ -1461,8 +1456,8 @@ int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stre
             mask |= 1u << q;
         }
         seen |= mask;
-        if ((mask >> first_phase) == 0u) continue;      // (every phase of this work list lies behind all pairs)
-        if ((mask & ~idle_mask) == 0u) continue;        // (every phase of this work list idles this round)
+        if ((mask >> from.first_phase) == 0u) continue;      // (every phase of this work list lies behind all pairs)
+        if ((mask & ~from.idle_mask) == 0u) continue;        // (every phase of this work list idles this round)
         const int vspans = queue ? queue->max_spans[p] : 0;
         if (queue && vspans == 0) continue;
         leads[n_leads++] = Lead{p, mask, queue ? n_slots * vspans : lead.n_spans, vspans};
@@ -1516,7 +1511,7 @@ int sp_pairs_gn_iterate(const SpPair* pairs, const int32_t* chunks, const int32_
         return SP_EINVAL;
     FuseArgs f{};
     f.arrivals = arrivals;
-    f.gn = GnArgs{max_N, lm_up, lm_down, lm_min, lm_state, backup, costs, 0.f, nullptr, nullptr, nullptr, 0, 0, 0};
+    f.gn = gn_args(max_N, lm_up, lm_down, lm_min, lm_state, backup, costs);
     return launch_cost(CostVariant{1, false, false, false, 2}, cost_blocks(n_spans, false), static_cast<hipStream_t>(stream), pairs, chunks, spans, n_spans,
                        irls_eps, partials, seg_partials, f);
 }

@@ -36,6 +36,8 @@ __device__ __forceinline__ float fast_exp(float x) {
         hipError_t e__ = hipGetLastError();        \
         if (e__ != hipSuccess) return (int)e__;    \
     } while (0)
+// a runtime error as the entry points that return a count report it: 0, or -(1000 + hipError_t) (below every SP_E* code)
+static inline int sp_hip_rc(hipError_t e) { return e == hipSuccess ? 0 : -(1000 + (int)e); }
 
 // sp_pairs_schedule_cost() from a phase every pair is known to have reached (sp_cost.hip; used by sp_pairs_schedule_run in sp_solver.hip)
 struct SpSchedule;
@@ -80,8 +82,19 @@ __attribute__((visibility("hidden"))) int wgn_multi_round(const void* args_dev, 
                                                            float irls_eps, void* stream);
 // the windows' 16-float LM states -> out[16 n]
 __attribute__((visibility("hidden"))) int wgn_multi_gather(const void* args_dev, int n, float* out, void* stream);
-__attribute__((visibility("hidden"))) int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stream, int first_phase, const SpQueue* queue, int n_slots,
-                                                              const int32_t* active, int n_active, uint32_t idle_mask);
+// which work lists sp_pairs_schedule_cost() launches, and over what (all zero: every list, over the batch's own spans)
+struct ScheduleCostFrom {
+    int first_phase;          // a phase every pair is known to have reached (pairs only move forward): work lists none of whose phases is at or
+                              // beyond it have no pair left and are not launched -- two of the three launches of a frame-pair schedule's
+                              // iteration through its long tail
+    const SpQueue* queue;     // a queue run: every list is launched over n_slots * max_spans virtual spans
+    int n_slots;
+    const int32_t* active;    // the tail of a queue run: only the n_active slots listed here are launched over
+    int n_active;
+    uint32_t idle_mask;       // phases whose pairs sit this round out (the solver skips them too): work lists ALL of whose phases idle are not
+                              // launched -- the fine-grained lists of the third attempt's Adam phases while no pair is in one
+};
+__attribute__((visibility("hidden"))) int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stream, const ScheduleCostFrom& from);
 
 // ---------------------------------------------------------------------------------------------------
 // wave64 / block reductions (fixed order -> bitwise reproducible run to run)

@@ -263,6 +263,12 @@ struct GnArgs {
     int predicted_exit;      // SP_PHASE_PREDICTED_EXIT: leave the phase when the step just taken is PREDICTED to buy less than conv_tol of the cost
     uint32_t idle_mask;      // phases whose pairs sit this round out: their work list was not launched (schedule_cost_from)
 };
+// what every launch sets; the rest is zero until the caller names it (conv_tol / done, or phase / iters) or the scheduled kernel fills it in
+inline GnArgs gn_args(int max_N, float lm_up, float lm_down, float lm_min, float* lm_state, float* backup, float* costs) {
+    GnArgs h{};
+    h.max_N = max_N; h.lm_up = lm_up; h.lm_down = lm_down; h.lm_min = lm_min; h.lm_state = lm_state; h.backup = backup; h.costs = costs;
+    return h;
+}
 
 // a pair leaves its current phase (thread 0): the next one starts afresh; lm_state[7] records how this one ended
 // (+iterations = on its cap, -iterations = by its convergence test)

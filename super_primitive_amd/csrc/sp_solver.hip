@@ -299,8 +299,10 @@ int sp_pairs_gn_step_conv(const SpPair* pairs, int n_pairs, int max_N, const flo
                           int32_t* done, void* stream) {
     if (!pairs || !partials || !seg_partials || !lm_state || !backup || !costs || n_pairs <= 0 || max_N <= 0) return SP_EINVAL;
     if (conv_tol > 0.f && !done) return SP_EINVAL;
+    GnArgs ga = gn_args(max_N, lm_up, lm_down, lm_min, lm_state, backup, costs);
+    ga.conv_tol = conv_tol; ga.done = done;
     hipLaunchKernelGGL(k_pairs_gn, dim3(n_pairs), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), pairs, partials,
-                       seg_partials, GnArgs{max_N, lm_up, lm_down, lm_min, lm_state, backup, costs, conv_tol, done, nullptr, nullptr, 0, 0});
+                       seg_partials, ga);
     SP_CHECK_LAUNCH();
     return 0;
 }
@@ -331,13 +333,85 @@ static int check_schedule(const SpSchedule* sched, const SpVerdict* v) {
     return 0;
 }
 
+// the five words k_phase_min leaves in flag_dev, read once the poll's copy has landed (include/sp_hip.h sp_pairs_schedule_run)
+struct Poll { int min_phase, head, attempts_left, n_active; uint32_t occupied; };
+static Poll read_poll(const int32_t* flag_host) {
+    const volatile int32_t* f = flag_host;      // (pinned memory the copy has just written)
+    return Poll{f[0], f[1], f[2], f[3], (uint32_t)f[4]};
+}
+
+// THE HOST LOOP OF A SCHEDULED RUN, behind both run entry points: check_every rounds of (cost pass, solver), a poll, and from what the poll saw
+// the work lists the next rounds can leave out.  queue == nullptr: all n pairs are resident; else n slots.  Every line where the two differ tests `queue`.
+static int schedule_run(const SpSchedule* sched, const SpQueue* queue, int n, int max_N, float lm_up, float lm_down, float lm_min, float* lm_state,
+                        float* backup, float* costs, int32_t* phase, int32_t* iters, int check_every, int max_rounds, int32_t* flag_dev,
+                        int32_t* flag_host, const SpVerdict* verdict, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const SpVerdict vd = verdict ? *verdict : SpVerdict{};
+    const SpQueue q = queue ? *queue : SpQueue{};     // (no queue: no head, no slot_pair, no active list -- slot i is pair i)
+    // a second attempt restarts a pair at retry_entry at any time: no work list can be left out while a first attempt is still running
+    const bool may_retry = vd.status && vd.attempts && vd.retry_mask != 0 && (sched->retry_entry >= 0 || sched->retry2_entry >= 0);
+    const int last_attempt = sched->retry2_entry >= 0 ? 2 : 1;
+    const uint32_t adam_mask = adam_phases(sched);
+    GnArgs ga = gn_args(max_N, lm_up, lm_down, lm_min, lm_state, backup, costs);
+    ga.phase = phase; ga.iters = iters;
+    int it = 0;
+    int min_phase = 0;
+    int reached = 0;                  // a phase every pair has passed: pairs only move forward, so work lists behind it are not launched
+    // THE TAIL (round 6): once the queue is empty and few slots still work on a pair -- a third attempt runs 1500 rounds on its own --
+    // both launches of a round go over the slots k_phase_min listed at the last poll instead of over all of them (a slot that finishes
+    // between two polls returns at once, none can become active again): a round of one pair costs its own kernels' latency, not the
+    // dispatch of n_slots x max_spans workgroups that find nothing to do
+    int n_active = 0;
+    uint32_t seen = 0;                // the phases that held a pair at the last poll
+    // ... and those that may hold one until the next.  Before the first: every slot of a queue starts at the entry; else the caller set the phases
+    uint32_t occupied = queue ? 1u << sched->entry : 0xffffffffu;
+    // (Staying one group of iterations AHEAD of the poll being waited for -- events instead of a stream synchronisation, the GPU
+    //  never idle while the host wakes up -- measured no better than this loop, 30.1 k against 30.7 k frame pairs/s: the tail of a
+    //  schedule is bound by the latency of a few pairs' own iterations, ~50 us each, not by the launch path.)
+    while (it < max_rounds) {
+        // all pairs resident: never a tail (finished pairs' workgroups return at once; there is no list of the others)
+        const bool tail = queue && q.active && n_active > 0 && 8 * n_active <= n;
+        // a tail of third attempts only -- every busy slot in an SP_PHASE_ADAM phase, hundreds of rounds from leaving it: the host looks in
+        // four times less often (a poll is a fifth of such a round's 25 us; finishing is noticed at most a dozen empty rounds late)
+        const int every = (tail && seen != 0 && (seen & ~adam_mask) == 0) ? 4 * check_every : check_every;
+        const int rounds = (max_rounds - it) < every ? (max_rounds - it) : every;
+        ga.idle_mask = adam_mask & ~occupied;
+        const ScheduleCostFrom from{reached, queue, queue ? n : 0, tail ? q.active : nullptr, tail ? n_active : 0, ga.idle_mask};   // (a queue run's cost pass: over the slots' virtual spans)
+        for (int k = 0; k < rounds; ++k, ++it) {
+            if (int rc = schedule_cost_from(sched, phase, stream, from)) return rc < 0 ? rc : sp_hip_rc((hipError_t)rc);
+            hipLaunchKernelGGL(k_pairs_gn_sched, dim3(tail ? n_active : n), dim3(SP_BLOCK), 0, s, *sched, ga, q, vd, from.active);
+            if (int rc = sp_hip_rc(hipGetLastError())) return rc;
+        }
+        hipLaunchKernelGGL(k_phase_min, dim3(1), dim3(SP_BLOCK), 0, s, phase, n, flag_dev, q.head, may_retry ? vd.attempts : nullptr, q.slot_pair,
+                           sched->n_phases, last_attempt, q.active);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(flag_host, flag_dev, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return sp_hip_rc(e);
+        const Poll poll = read_poll(flag_host);
+        min_phase = poll.min_phase;
+        seen = poll.occupied;
+        occupied = queue ? seen | 1u << sched->entry : seen;          // a slot refilled between two polls starts at the entry
+        n_active = poll.head >= q.n_queue ? poll.n_active : 0;          // (while pairs wait, every slot is busy)
+        if (min_phase >= sched->n_phases) break;                        // (a slot only stays finished when the queue was empty)
+        const bool drained = !queue || poll.head >= q.n_queue;         // (min(phase) over the slots says nothing about the pairs still waiting)
+        reached = (drained && !(may_retry && poll.attempts_left) && min_phase > 0) ? min_phase : 0;
+    }
+    if (min_phase < sched->n_phases && vd.status) {       // the round limit ended the run: SP_STATUS_UNFINISHED for whoever is still at work
+        hipLaunchKernelGGL(k_mark_unfinished, dim3((n + 255) / 256), dim3(256), 0, s, phase, q.slot_pair, n, sched->n_phases, vd.status);
+        if (int rc = sp_hip_rc(hipGetLastError())) return rc;
+    }
+    return it;
+}
+
 int sp_pairs_schedule_gn_step(const SpSchedule* sched, int n_pairs, int max_N, float lm_up, float lm_down, float lm_min,
                               float* lm_state, float* backup, float* costs, int32_t* phase, int32_t* iters, const SpVerdict* verdict,
                               void* stream) {
     if (!sched || !lm_state || !backup || !costs || !phase || !iters || n_pairs <= 0 || max_N <= 0) return SP_EINVAL;
     if (int rc = check_schedule(sched, verdict)) return rc;
-    hipLaunchKernelGGL(k_pairs_gn_sched, dim3(n_pairs), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), *sched,
-                       GnArgs{max_N, lm_up, lm_down, lm_min, lm_state, backup, costs, 0.f, nullptr, phase, iters, 0, 0, 0}, SpQueue{},
+    GnArgs ga = gn_args(max_N, lm_up, lm_down, lm_min, lm_state, backup, costs);
+    ga.phase = phase; ga.iters = iters;
+    hipLaunchKernelGGL(k_pairs_gn_sched, dim3(n_pairs), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), *sched, ga, SpQueue{},
                        verdict ? *verdict : SpVerdict{}, (const int32_t*)nullptr);
     SP_CHECK_LAUNCH();
     return 0;
@@ -356,60 +430,8 @@ int sp_pairs_schedule_run_queue(const SpSchedule* sched, const SpQueue* queue, i
         if ((ph.flags & SP_PHASE_WAVE_SPANS) && (queue->max_spans[p] & 3)) return SP_EINVAL;
         if ((long long)queue->max_spans[p] * n_slots > 0x7fffffffLL) return SP_ELIMIT;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const SpVerdict vd = verdict ? *verdict : SpVerdict{};
-    // a second attempt restarts a pair at retry_entry at any time: no work list can be left out while a first attempt is still running
-    const bool may_retry = vd.status && vd.attempts && vd.retry_mask != 0 && (sched->retry_entry >= 0 || sched->retry2_entry >= 0);
-    const int last_attempt = sched->retry2_entry >= 0 ? 2 : 1;
-    int it = 0;
-    int reached = 0;                  // a phase every slot has passed -- only meaningful once the queue is empty (refilled slots restart at the entry)
-    int min_phase = 0;
-    // THE TAIL (round 6): once the queue is empty and few slots still work on a pair -- a third attempt runs 1500 rounds on its own --
-    // both launches of a round go over the slots k_phase_min listed at the last poll instead of over all of them (a slot that finishes
-    // between two polls returns at once, none can become active again): a round of one pair costs its own kernels' latency, not the
-    // dispatch of n_slots x max_spans workgroups that find nothing to do
-    int n_active = 0;
-    const uint32_t adam_mask = adam_phases(sched);
-    uint32_t occupied = 1u << sched->entry;           // (what the last poll saw; before the first one every slot is at the entry)
-    uint32_t seen = 0;                                // ... without the entry's bit: where the busy slots really are
-    while (it < max_rounds) {
-        const bool tail = queue->active && n_active > 0 && 8 * n_active <= n_slots;
-        // a tail of third attempts only -- every busy slot in an SP_PHASE_ADAM phase, hundreds of rounds from leaving it: the host looks in
-        // four times less often (a poll is a fifth of such a round's 25 us; finishing is noticed at most a dozen empty rounds late)
-        const int every = (tail && seen != 0 && (seen & ~adam_mask) == 0) ? 4 * check_every : check_every;
-        const int n = (max_rounds - it) < every ? (max_rounds - it) : every;
-        const uint32_t idle = adam_mask & ~occupied;
-        GnArgs ga{max_N, lm_up, lm_down, lm_min, lm_state, backup, costs, 0.f, nullptr, phase, iters, 0, 0, 0};
-        ga.idle_mask = idle;
-        for (int k = 0; k < n; ++k, ++it) {
-            int rc = schedule_cost_from(sched, phase, stream, reached, queue, n_slots, tail ? queue->active : nullptr, tail ? n_active : 0, idle);
-            if (rc != 0) return rc < 0 ? rc : -(1000 + rc);
-            hipLaunchKernelGGL(k_pairs_gn_sched, dim3(tail ? n_active : n_slots), dim3(SP_BLOCK), 0, s, *sched, ga, *queue, vd,
-                               tail ? (const int32_t*)queue->active : (const int32_t*)nullptr);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return -(1000 + (int)e);
-        }
-        hipLaunchKernelGGL(k_phase_min, dim3(1), dim3(SP_BLOCK), 0, s, phase, n_slots, flag_dev, queue->head, may_retry ? vd.attempts : nullptr,
-                           queue->slot_pair, sched->n_phases, last_attempt, queue->active);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(flag_host, flag_dev, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return -(1000 + (int)e);
-        min_phase = static_cast<volatile int32_t*>(flag_host)[0];
-        seen = (uint32_t)static_cast<volatile int32_t*>(flag_host)[4];
-        occupied = seen | (1u << sched->entry);           // (a refilled slot starts at the entry)
-        const int head = static_cast<volatile int32_t*>(flag_host)[1];
-        n_active = head >= queue->n_queue ? static_cast<volatile int32_t*>(flag_host)[3] : 0;       // (while pairs wait, every slot is busy)
-        const bool first_attempts_left = static_cast<volatile int32_t*>(flag_host)[2] != 0;
-        if (min_phase >= sched->n_phases) break;          // (a slot only stays finished when the queue was empty)
-        reached = (head >= queue->n_queue && !(may_retry && first_attempts_left)) ? (min_phase < 0 ? 0 : min_phase) : 0;
-    }
-    if (min_phase < sched->n_phases && vd.status) {
-        hipLaunchKernelGGL(k_mark_unfinished, dim3((n_slots + 255) / 256), dim3(256), 0, s, phase, queue->slot_pair, n_slots, sched->n_phases, vd.status);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(1000 + (int)e);
-    }
-    return it;
+    return schedule_run(sched, queue, n_slots, max_N, lm_up, lm_down, lm_min, lm_state, backup, costs, phase, iters, check_every, max_rounds,
+                        flag_dev, flag_host, verdict, stream);
 }
 
 int sp_pairs_schedule_run(const SpSchedule* sched, int n_pairs, int max_N, float lm_up, float lm_down, float lm_min,
@@ -418,49 +440,8 @@ int sp_pairs_schedule_run(const SpSchedule* sched, int n_pairs, int max_N, float
     if (!sched || !phase || !iters || !flag_dev || !flag_host || check_every <= 0 || max_rounds < 0) return SP_EINVAL;
     if (!lm_state || !backup || !costs || n_pairs <= 0 || max_N <= 0) return SP_EINVAL;
     if (int rc = check_schedule(sched, verdict)) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool may_retry = verdict && verdict->status && verdict->attempts && verdict->retry_mask != 0 && (sched->retry_entry >= 0 || sched->retry2_entry >= 0);
-    const int last_attempt = sched->retry2_entry >= 0 ? 2 : 1;
-    int it = 0;
-    int reached = 0;                  // min(phase) at the last poll: pairs only move forward, so work lists behind it are not launched
-    int min_phase = 0;
-    const uint32_t adam_mask = adam_phases(sched);
-    uint32_t occupied = 0xffffffffu;  // (the caller set the phases: nothing is known before the first poll)
-    // (Staying one group of iterations AHEAD of the poll being waited for -- events instead of a stream synchronisation, the GPU
-    //  never idle while the host wakes up -- measured no better than this loop, 30.1 k against 30.7 k frame pairs/s: the tail of a
-    //  schedule is bound by the latency of a few pairs' own iterations, ~50 us each, not by the launch path.)
-    while (it < max_rounds) {
-        const int n = (max_rounds - it) < check_every ? (max_rounds - it) : check_every;
-        const uint32_t idle = adam_mask & ~occupied;
-        for (int k = 0; k < n; ++k, ++it) {
-            int rc = schedule_cost_from(sched, phase, stream, reached, nullptr, 0, nullptr, 0, idle);
-            if (rc == 0) rc = check_schedule(sched, verdict);
-            if (rc != 0) return rc < 0 ? rc : -(1000 + rc);
-            GnArgs ga{max_N, lm_up, lm_down, lm_min, lm_state, backup, costs, 0.f, nullptr, phase, iters, 0, 0, 0};
-            ga.idle_mask = idle;
-            hipLaunchKernelGGL(k_pairs_gn_sched, dim3(n_pairs), dim3(SP_BLOCK), 0, s, *sched, ga, SpQueue{}, verdict ? *verdict : SpVerdict{}, (const int32_t*)nullptr);
-            hipError_t el = hipGetLastError();
-            if (el != hipSuccess) return -(1000 + (int)el);
-        }
-        hipLaunchKernelGGL(k_phase_min, dim3(1), dim3(SP_BLOCK), 0, s, phase, n_pairs, flag_dev, (const int32_t*)nullptr,
-                           may_retry ? (const int32_t*)verdict->attempts : (const int32_t*)nullptr, (const int32_t*)nullptr, sched->n_phases, last_attempt,
-                           (int32_t*)nullptr);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(flag_host, flag_dev, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return -(1000 + (int)e);
-        reached = min_phase = static_cast<volatile int32_t*>(flag_host)[0];
-        occupied = (uint32_t)static_cast<volatile int32_t*>(flag_host)[4];
-        if (reached >= sched->n_phases) break;
-        // (a second attempt restarts a pair at retry_entry at any time: no work list can be left out while a first attempt is still running)
-        if (reached < 0 || (may_retry && static_cast<volatile int32_t*>(flag_host)[2] != 0)) reached = 0;
-    }
-    if (verdict && verdict->status && min_phase < sched->n_phases) {
-        hipLaunchKernelGGL(k_mark_unfinished, dim3((n_pairs + 255) / 256), dim3(256), 0, s, phase, (const int32_t*)nullptr, n_pairs, sched->n_phases, verdict->status);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(1000 + (int)e);
-    }
-    return it;
+    return schedule_run(sched, nullptr, n_pairs, max_N, lm_up, lm_down, lm_min, lm_state, backup, costs, phase, iters, check_every, max_rounds,
+                        flag_dev, flag_host, verdict, stream);
 }
 
 int sp_pairs_gn_step(const SpPair* pairs, int n_pairs, int max_N, const float* partials, const float* seg_partials,

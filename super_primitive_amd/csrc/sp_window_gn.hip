@@ -1132,11 +1132,11 @@ int sp_window_gn_run(const SpPair* pairs, const int32_t* chunks, const int32_t* 
                 rc = sp_window_gn_step(pairs, edges, n_edges, nodes, n_nodes, blocks, n_blocks, sum_N, max_N, n_unknowns, span_partials,
                                        seg_partials, scratch, nodes_backup, kld_backup, flags, lm_up, lm_down, lm_min, conv_tol, state, losses,
                                        max_losses, stream);
-            if (rc != 0) return rc < 0 ? rc : -(1000 + rc);
+            if (rc != 0) return rc < 0 ? rc : sp_hip_rc((hipError_t)rc);
         }
         hipError_t e = hipMemcpyAsync(state_host, state, SP_WGN_STATE * sizeof(float), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return -(1000 + (int)e);
+        if (e != hipSuccess) return sp_hip_rc(e);
         if (conv_tol > 0.f && static_cast<volatile float*>(state_host)[6] != 0.f) break;
     }
     return it;
@@ -1165,7 +1165,7 @@ int sp_window_gn_run_multi(const SpWindowGn* windows, int n_windows, float irls_
     MultiList* lists_dev = reinterpret_cast<MultiList*>(static_cast<char*>(args_dev) + (sizeof(WGnArgs) * (size_t)n_windows + 15) / 16 * 16);
     hipError_t e = hipMemcpyAsync(wins, host.data(), sizeof(WGnArgs) * (size_t)n_windows, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(lists_dev, lists.data(), sizeof(MultiList) * (size_t)n_windows, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return -(1000 + (int)e);
+    if (e != hipSuccess) return sp_hip_rc(e);
     int it = 0;
     while (it < max_iters) {
         const int n = (max_iters - it) < check_every ? (max_iters - it) : check_every;
@@ -1174,7 +1174,7 @@ int sp_window_gn_run_multi(const SpWindowGn* windows, int n_windows, float irls_
         if (int rc = wgn_multi_gather(wins, n_windows, states_dev, stream)) return rc;
         e = hipMemcpyAsync(states_host, states_dev, sizeof(float) * SP_WGN_STATE * (size_t)n_windows, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return -(1000 + (int)e);
+        if (e != hipSuccess) return sp_hip_rc(e);
         if (conv_tol > 0.f) {
             bool all = true;
             for (int i = 0; i < n_windows && all; ++i) all = static_cast<volatile float*>(states_host)[i * SP_WGN_STATE + 6] != 0.f;
@@ -1226,20 +1226,18 @@ int wgn_multi_round(const void* args_dev, const MultiList* lists_dev, int n, con
     const int tiles = std::max(1, (lds + SP_BLOCK * SP_WGN_PPT - 1) / (SP_BLOCK * SP_WGN_PPT));
     const WGnArgs dummy{};
     int rc = cost_pairs_multi(lists_dev, n, info.total_blocks, 2, irls_eps, stream);
-    if (rc != 0) return rc < 0 ? rc : -(1000 + rc);
+    if (rc != 0) return rc < 0 ? rc : sp_hip_rc((hipError_t)rc);
     if (info.n_reduce > 0) hipLaunchKernelGGL(k_window_gn_reduce_multi, dim3(info.max_edges, 1, n), dim3(SP_BLOCK), 0, s, wins);
     if (!(flags & 5)) hipLaunchKernelGGL(k_window_gn_schur, dim3(info.max_blocks, tiles, n), dim3(SP_BLOCK), 0, s, dummy, wins);
     if (max_y <= 64) hipLaunchKernelGGL(k_window_gn_update<64>, dim3(1, 1, n), dim3(wgn_update_threads(64)), 0, s, dummy, wins);
     else if (max_y <= 128) hipLaunchKernelGGL(k_window_gn_update<128>, dim3(1, 1, n), dim3(wgn_update_threads(128)), 0, s, dummy, wins);
     else if (max_y <= SP_WGN_LDS_Y) hipLaunchKernelGGL(k_window_gn_update<SP_WGN_LDS_Y>, dim3(1, 1, n), dim3(wgn_update_threads(SP_WGN_LDS_Y)), 0, s, dummy, wins);
     else hipLaunchKernelGGL(k_window_gn_update<0>, dim3(1, 1, n), dim3(wgn_update_threads(0)), 0, s, dummy, wins);
-    const hipError_t el = hipGetLastError();
-    return el == hipSuccess ? 0 : -(1000 + (int)el);
+    return sp_hip_rc(hipGetLastError());
 }
 
 int wgn_multi_gather(const void* args_dev, int n, float* out, void* stream) {
     hipLaunchKernelGGL(k_wgn_gather_states, dim3((n * SP_WGN_STATE + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const WGnArgs*>(args_dev), n, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(1000 + (int)e);
+    return sp_hip_rc(hipGetLastError());
 }

@@ -863,24 +863,24 @@ class PairBatch:
             self.adam_state.zero_()
         if slots is not None and int(slots) < self.M:
             it = self._run_queue(sched, int(slots), bound, check_every, lm_up, lm_down, lm_min, v, v_addr, streams=streams, schedule_kw=schedule_kw)
-            if outlier > 0.0 and self.M >= COST_OUTLIER_MIN_PAIRS:
-                it += self._cost_outlier_pass(outlier, v, bound, check_every, lm_up, lm_down, lm_min, schedule_kw)
-            return (it, self.status) if return_status else it
-        self.phase.fill_(sched.entry)
-        self.phase_iters.zero_()
-        self.lm_state[:, 1] = -1.0
-        self.lm_state[:, 4:] = 0.0
-        # the whole host loop in ONE foreign call (sp_pairs_schedule_run): nothing is issued from Python per iteration, and the
-        # interpreter lock is free for the other host threads of a PairStream while this batch runs
-        it = self.lib.sp_pairs_schedule_run(ctypes.addressof(sched), self.M, self.max_N, float(lm_up), float(lm_down), float(lm_min),
-                                            _lib.ptr(self.lm_state), _lib.ptr(self.backup), _lib.ptr(self._costs), _lib.ptr(self.phase),
-                                            _lib.ptr(self.phase_iters), int(check_every), int(bound), _lib.ptr(self._flag[0]),
-                                            self._flag[1].data_ptr(), v_addr, _lib.stream_ptr())
-        if it < 0:
-            _lib.check(it if it > -1000 else -(it + 1000), "sp_pairs_schedule_run")
+        else:
+            self.phase.fill_(sched.entry)
+            self.phase_iters.zero_()
+            self.lm_state[:, 1] = -1.0
+            self.lm_state[:, 4:] = 0.0
+            it = self._schedule_run(sched, v_addr, bound, check_every, lm_up, lm_down, lm_min)
         if outlier > 0.0 and self.M >= COST_OUTLIER_MIN_PAIRS:
             it += self._cost_outlier_pass(outlier, v, bound, check_every, lm_up, lm_down, lm_min, schedule_kw)
         return (it, self.status) if return_status else it
+
+    def _schedule_run(self, sched, v_addr, bound, check_every, lm_up, lm_down, lm_min):
+        """sp_pairs_schedule_run over all pairs of the batch from the phases they are in; returns the rounds launched.  The whole host loop
+        is ONE foreign call: nothing is issued from Python per iteration, and the interpreter lock is free for the other host threads of
+        a PairStream while this batch runs."""
+        return _lib.check_run(self.lib.sp_pairs_schedule_run(
+            ctypes.addressof(sched), self.M, self.max_N, float(lm_up), float(lm_down), float(lm_min), _lib.ptr(self.lm_state), _lib.ptr(self.backup),
+            _lib.ptr(self._costs), _lib.ptr(self.phase), _lib.ptr(self.phase_iters), int(check_every), int(bound), _lib.ptr(self._flag[0]),
+            self._flag[1].data_ptr(), v_addr, _lib.stream_ptr()), "sp_pairs_schedule_run")
 
     def _cost_outlier_pass(self, factor, v, bound, check_every, lm_up, lm_down, lm_min, schedule_kw):
         """The batch-relative part of the verdict (VERDICT_DEFAULTS['cost_outlier']), after the scheduled run proper: pairs that passed
@@ -927,13 +927,7 @@ class PairBatch:
             self.diag[:, 5] = torch.where(again, 0.0, self.diag[:, 5])
             if sched.adam_state:
                 self.adam_state.zero_()
-            n = self.lib.sp_pairs_schedule_run(ctypes.addressof(sched), M, self.max_N, float(lm_up), float(lm_down), float(lm_min),
-                                               _lib.ptr(self.lm_state), _lib.ptr(self.backup), _lib.ptr(self._costs), _lib.ptr(self.phase),
-                                               _lib.ptr(self.phase_iters), int(check_every), int(bound), _lib.ptr(self._flag[0]),
-                                               self._flag[1].data_ptr(), ctypes.addressof(v), _lib.stream_ptr())
-            if n < 0:
-                _lib.check(n if n > -1000 else -(n + 1000), "sp_pairs_schedule_run")
-            it += n
+            it += self._schedule_run(sched, ctypes.addressof(v), bound, check_every, lm_up, lm_down, lm_min)
         out = (self.diag[:, 0] > bound_c) & ((self.status & F) == 0)
         self.status.bitwise_or_(out.to(torch.int32) * _lib.SP_STATUS_COST)
         return it
@@ -1034,10 +1028,7 @@ class PairBatch:
                 t.join()
             for st in side:
                 main.wait_stream(st)
-        for it in its:
-            if it < 0:
-                _lib.check(it if it > -1000 else -(it + 1000), "sp_pairs_schedule_run_queue")
-        it = max(its)
+        it = max(_lib.check_run(n, "sp_pairs_schedule_run_queue") for n in its)
         # results per PAIR (what the per-slot arrays hold is whichever pairs came last)
         min_phase = min(int(f[1][0]) for f in flags)
         taken = min(max(int(f[1][1]) for f in flags), M)

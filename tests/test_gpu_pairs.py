@@ -475,6 +475,15 @@ def test_device_side_schedule_walks_every_pair_through_its_own_levels():
         assert torch.equal(solo.poses()[0], batch.poses()[m]), m
         assert torch.equal(solo.klds()[0], batch.klds()[m]), m
     assert launched == max(solo_iters), (launched, solo_iters)
+    # polled every FOURTH round (a fresh batch): the same per-pair arithmetic, bitwise -- a finished pair's workgroup returns at once -- and the
+    # rounds run on to the poll that sees the last pair finished (no SP_PHASE_ADAM phase in this schedule: no work list idles in between)
+    every4 = make_batch(prs, levels=(0, 2), tile_points=512)
+    launched4 = every4.run_scheduled(check_every=4, **sch)
+    torch.cuda.synchronize()
+    print(f"\nrounds launched: {launched} polled every round, {launched4} polled every fourth")
+    assert torch.equal(every4.pose, batch.pose) and torch.equal(every4.kld, batch.kld)
+    assert torch.equal(every4.costs(), batch.costs()) and torch.equal(every4.lm_state[:, :4], batch.lm_state[:, :4])
+    assert launched4 == -(-launched // 4) * 4, (launched4, launched)
     # finished: further launches are no-ops
     import ctypes
     from super_primitive_amd import _lib
@@ -775,7 +784,10 @@ def test_slot_level_continuous_batching_gives_every_pair_its_own_result(granule)
     """run_scheduled(slots=S) (SpQueue, sp_pairs_schedule_run_queue): 14 resident pairs of one layout, 4 slots -- a
     finished pair's slot goes to the next waiting pair inside the solver launch.  Every pair's pose, log-depths, final cost and
     iteration counts are BITWISE those of the run with all 14 resident (pairs never interact),
-    whichever slot it happened to get; the queue is handed out completely; far fewer pair-slots are launched than slots x rounds."""
+    whichever slot it happened to get; the queue is handed out completely; far fewer pair-slots are launched than slots x rounds.
+    With 8 slots the last pair to finish iterates alone and 8 x (busy slots) <= slots holds: the one small case whose last rounds are
+    launched over the listed slots only (SpQueue.active).  Nothing on the host reports that this branch was taken -- what is asserted is
+    that the results are the same bits with it."""
     from super_primitive_amd import synth
     sch = dict(max_iters_per_level=12, conv_tol=2e-3, polish_max=6, polish_eps=1e-5, polish_tol=1e-4)
     sig = [0.002, 0.012, 0.004, 0.008, 0.001, 0.015, 0.003, 0.006, 0.010, 0.002, 0.007, 0.013, 0.005, 0.009]
@@ -786,7 +798,7 @@ def test_slot_level_continuous_batching_gives_every_pair_its_own_result(granule)
     torch.cuda.synchronize()
     its_ref = npy(ref.lm_state[:, 2] + ref.lm_state[:, 3])
     assert its_ref.max() > 1.3 * its_ref.min()                 # (the pairs really finish at different times)
-    for slots in (4, 5):
+    for slots in (4, 5, 8):
         q = make_batch(prs, **kw)
         n_q = q.run_scheduled(check_every=1, slots=slots, **sch)
         torch.cuda.synchronize()
@@ -940,6 +952,17 @@ def test_scheduled_run_reports_a_verdict_and_retries_what_fails_it():
                                      _lib.ptr(dd.phase), _lib.ptr(dd.phase_iters), 2, 4, _lib.ptr(flag[0]), flag[1].data_ptr(), ctypes.addressof(v), _lib.stream_ptr())
     torch.cuda.synchronize()
     assert n == 4 and all(s == _lib.SP_STATUS_UNFINISHED for s in npy(dd.status))
+    #     ... and through two slots, the queue driver's round budget cut to (bound = 1) x (3 pairs / 2 slots, rounded up, + 1) = 3: no pair can
+    #     finish; the two in a slot are marked by the library (under the pair's index, through slot_pair), the one still waiting by the host
+    dq = make_batch(prs, **kw)
+    sched = dq.schedule(**sch)
+    v = dq._verdict(sched, None)
+    dq._flag = flag
+    n = dq._run_queue(sched, 2, 1, 2, 8.0, 0.5, 1e-7, v, ctypes.addressof(v), schedule_kw=sch)
+    torch.cuda.synchronize()
+    print(f"\nqueue run on its round limit: {n} rounds, status {npy(dq.status).tolist()}, queue {dq._queue_stats}")
+    assert n == 3 and npy(dq.status).tolist() == [_lib.SP_STATUS_UNFINISHED] * 3
+    assert dq._queue_stats["head"] == 2 and not dq._queue_stats["finished"]
     # (e) a non-finite unknown (the one thing the reference asserts on, core/dense_optim.py:311,321,340-343) is reported for THAT pair only
     ee = make_batch(prs, **kw)
     ee.kld[ee.n_off[2] + 1] = float("nan")
