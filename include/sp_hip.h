@@ -875,6 +875,46 @@ int sp_depth_metrics_workspace_doubles(int B, int H, int W);
 int sp_depth_metrics(const float* estimate, const float* target, const uint8_t* valid, int B, int H, int W, double* workspace,
                      double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * From SAM's raw output to the masks of a keyframe: the tensor code of frontend/segment/mask_generation.py behind the network.
+ * Everything runs on the caller's stream without a synchronisation.  Null or aliased pointers and non-positive sizes are SP_EINVAL,
+ * sizes beyond the stated limits SP_ELIMIT, both before any device work.  H W < 2^31 and W <= 32767 throughout (the reference's
+ * int16 row sums).
+ *
+ * sp_sam_candidate_stats: logits (M,H,W) float (M = 3 n candidates, M <= 65535), read once.  stats (M,8) int32 per candidate:
+ * {#(x > thresh + offset), #(x > thresh - offset), #(x > thresh), left, top, right, bottom, 0} -- the two counts of
+ * calculate_stability_score (mask_generation.py:54-56; strict comparisons, NaN false), the size of :71 and the XYXY box of
+ * batched_mask_to_box (:93) over x > thresh, zeros for an empty mask.  Integer atomics: bitwise stable.
+ *
+ * sp_box_nms: batched_nms with one category (mask_generation.py:183-188, :217-222).  boxes (K,4) float XYXY, scores (K) float.
+ * Visits in falling score (equal scores: the lower index first; NaN first, as torch.sort), suppresses j when
+ * inter / (area_i + area_j - inter) > thr in float32 with area = (x2 - x1)(y2 - y1) and inter = max(x2' - x1', 0) max(y2' - y1', 0)
+ * (NaN: false).  keep (K) int64: the kept indices in visiting order, n_keep (1) int32 their number.  K <= 2048.
+ *
+ * sp_sam_build_masks: masks (K,H,W) u8 0/1 with masks[k] = logits[cand[k]] > thresh (mask_generation.py:67,76), cand (K) int32 in
+ * [0, M) (anything else gives an empty mask); coverage_or_null (H,W) u8 = their OR (:192).
+ *
+ * sp_mask_edges: masks_to_edges / infer_edge_probs (mask_generation.py:291-313) of K masks (K,H,W) u8, optionally seen through a
+ * nearest resize to (He,We) (:240-244): row_map (He) / col_map (We) int32 name the source row / column of every coarse one (null: the
+ * identity, He = H / We = W).  Scharr / 32 with reflect padding at the coarse border, magnitude, maximum over the masks, with pool a
+ * 3x3 maximum on top; edges, edge_probs (He,We) float, edge_probs = clip(1 - 2 edges, 0, 1).  Bitwise the reference's floats.
+ * 2 <= He, We <= 32767.
+ *
+ * sp_sam_cut_masks: cut_masks_by_edges and filter_edge_points (mask_generation.py:254-275).  valid = edge_probs > prob_thresh
+ * (null: everywhere); kp_rc_or_null (K,2) int32 (row, col) of every mask's keypoint: mask k is kept when masks[k] & valid is set
+ * there (null: every mask is kept; a keypoint outside the image drops its mask).  keep (K) int32: the position of mask k among
+ * the kept ones or -1; out_masks_or_null (K,H,W) u8: the kept masks & valid, compacted in order (the rows behind them are not
+ * written; null: only keep and the coverage are wanted); final_coverage (H,W) u8 their OR.
+ * ---------------------------------------------------------------------------------------------------- */
+int sp_sam_candidate_stats(const float* logits, int M, int H, int W, float thresh, float offset, int32_t* stats, void* stream);
+int sp_box_nms(const float* boxes, const float* scores, int K, float thr, int64_t* keep, int32_t* n_keep, void* stream);
+int sp_sam_build_masks(const float* logits, const int32_t* cand, int K, int M, int H, int W, float thresh, uint8_t* masks,
+                       uint8_t* coverage_or_null, void* stream);
+int sp_mask_edges(const uint8_t* masks, int K, int H, int W, const int32_t* row_map_or_null, const int32_t* col_map_or_null, int He, int We,
+                  float* edges, float* edge_probs, int pool, void* stream);
+int sp_sam_cut_masks(const uint8_t* masks, int K, int H, int W, const float* edge_probs_or_null, float prob_thresh, const int32_t* kp_rc_or_null,
+                     int32_t* keep, uint8_t* out_masks_or_null, uint8_t* final_coverage, void* stream);
+
 /* odometery/kf_criteria.py:7-21 translation_difference, :23-34 rotation_difference and the depth-validity ratio of
  * odometery/odometery.py:1003-1004, in one launch without a host sync.  depth: n floats (the rendered depth of the
  * latest keyframe); poses row-major 4x4.  out[4] = {#(depth > thresh)/n, scale = lower median of the valid depths

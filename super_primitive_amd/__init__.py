@@ -13,15 +13,16 @@ import sys
 __version__ = "0.1.0"
 
 _REFERENCE_PACKAGES = ("core", "image", "lie", "tool", "odometery", "depth_completion")
-# single modules of packages whose other modules stay the reference's own (SAM and the normals network: out of scope)
-_REFERENCE_LEAF_MODULES = ("frontend.segment.post_processer", "frontend.normals.normals_integration")
+# single modules of packages whose other modules stay the reference's own (the SAM network and the normals network: out of scope)
+_REFERENCE_LEAF_MODULES = ("frontend.segment.post_processer", "frontend.normals.normals_integration", "frontend.segment.mask_generation")
 
 
 def install_as_reference_modules():
     """Alias ``super_primitive_amd.<pkg>[.<module>]`` as ``<pkg>[.<module>]`` in ``sys.modules``.  ``frontend.segment.post_processer``
-    (the keyframe post-processing) and ``frontend.normals.normals_integration`` (the stage in front of it) are
+    (the keyframe post-processing), ``frontend.normals.normals_integration`` (the stage in front of it) and
+    ``frontend.segment.mask_generation`` (from SAM's raw output to masks and keypoints) are
     aliased as LEAVES: when the reference's ``frontend`` package is importable it keeps its other modules (``sam_tools``,
-    ``mask_generation``, the normals network) and only these two are replaced; otherwise
+    the normals network) and only these are replaced; otherwise
     the (otherwise empty) parent packages of this tree stand in."""
     import importlib.util
     import pkgutil

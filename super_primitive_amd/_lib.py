@@ -89,6 +89,11 @@ SIGNATURES = {
     "sp_depth_fill_nearest": [P, P, I, I, I, P, P, P, P, P],
     "sp_depth_metrics_workspace_doubles": [I, I, I],
     "sp_depth_metrics": [P, P, P, I, I, I, P, P, P],
+    "sp_sam_candidate_stats": [P, I, I, I, F, F, P, P],
+    "sp_box_nms": [P, P, I, F, P, P, P],
+    "sp_sam_build_masks": [P, P, I, I, I, I, F, P, P, P],
+    "sp_mask_edges": [P, I, I, I, P, P, I, I, P, P, I, P],
+    "sp_sam_cut_masks": [P, I, I, I, P, F, P, P, P, P, P],
 }
 
 SP_ABI_VERSION = 18
