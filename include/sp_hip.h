@@ -740,26 +740,44 @@ int sp_window_gn_run(const SpPair* pairs, const int32_t* chunks, const int32_t* 
  * ---------------------------------------------------------------------------------------------------- */
 
 /* Dense (N,H,W) seeded depths.  log_space = 1: (L + shift_n) * mask  (core/dense_optim.py:38-80
- * infer_depth_seeds);  log_space = 0: exp of that  (core/dense_optim.py:164-174 unproject_kf_to_depths). */
+ * infer_depth_seeds);  log_space = 0: exp of that  (core/dense_optim.py:164-174 unproject_kf_to_depths).
+ * shift_n = kld[n] - L[n] at the keypoint's pixel; that pixel is float32 0.5 (size - 1) (kp + 1) rounded half to even, per
+ * axis.  Outside the masks the product is 0, so the two forms hold exactly 0.0 and exactly 1.0 there.  Every pixel of
+ * every segment is written, whatever N*H*W (grid-stride loop over at most 1024 blocks per segment). */
 int sp_depth_expand(const uint8_t* masks, const float* logdepth, const float* keypoints, const float* kld, int N,
                     int H, int W, int log_space, float* out, void* stream);
 
 /* core/ops.py:59-96 estimate_depth_diff (mean=False) on table points moved by pose: last-writer-wins z splat
  * at truncated (v,u); ties resolved by highest point index (deterministic, one of the orders the reference's
- * scatter_ may produce).  out: (H,W) zero-initialised by this call.  keys: H*W uint64 scratch. */
+ * scatter_ may produce).  out: (H,W) zero-initialised by this call.  keys: H*W uint64 scratch.
+ * Pinned by tests/test_gpu_segment_depth.py against the float64 statement tests/segment_depth_ref.py:
+ *   - the pixel is (trunc v, trunc u), truncation toward ZERO like .long(): u in (-1, 0) lands in column 0 and v in (-1, 0) in
+ *     row 0 (floor would drop them); the last row and column are H - 1 and W - 1;
+ *   - a point is kept iff z > 1e-6, u and v are finite and the pixel is inside the image; a NaN depth fails z > 1e-6, so a
+ *     point with a NaN log-depth vanishes and changes nothing but the pixels it would have won;
+ *   - table order is segment by segment, row-major within a segment; the point with the highest table index wins a pixel;
+ *   - an untouched pixel is exactly 0; two calls give the same bits. */
 int sp_depth_splat(const uint32_t* pix, const float* baseL, const int32_t* seg_off, const float* kp_L,
                    const float* kld, int N, int P, int H, int W, const float* K, const float* pose,
                    unsigned long long* keys, float* out, void* stream);
 
 /* core/ops.py:84-92 estimate_depth_diff(mean=True): scatter_reduce_('mean') at the truncated pixel, WITH the reference's "initial
  * zero counted" semantics (include_self defaults to True): a pixel hit by c points holds sum(z) / (c + 1), an untouched one 0.
- * acc: 12*H*W bytes of scratch (32.32 fixed-point sums + counts: order independent).  No reference caller passes mean=True. */
+ * acc: 12*H*W bytes of scratch (32.32 fixed-point sums + counts: order independent).  No reference caller passes mean=True.
+ * Which points are kept and where they land: exactly as sp_depth_splat. */
 int sp_depth_splat_mean(const uint32_t* pix, const float* baseL, const int32_t* seg_off, const float* kp_L, const float* kld, int N,
                         int P, int H, int W, const float* K, const float* pose, void* acc, float* out, void* stream);
 
 /* odometery/depth_init.py:10-67 segment_based_depth_reinit.  mode 0 = mean, 1 = median (lower middle for
  * even counts, like torch.median).  est_depth (H,W).  scratch: P floats.  out_kld[N], out_visible[N] u8.
- * Invisible segments receive the (lower) median of the visible segments' values. */
+ * Invisible segments receive the (lower) median of the visible segments' values.
+ *   - a pixel's estimate is valid iff NOT (est < 1e-6): 5e-7 and 0 are invalid, 2e-6 is valid, and a NaN is VALID (the
+ *     reference's ~(est < eps)) -- it makes its segment's result NaN; est_depth is read only;
+ *   - a segment's result is the mean, or the LOWER median = the (cnt - 1) / 2-th smallest (0-based; for an even count the lower
+ *     of the two middle values, an element of the data, never their average), of log(est) - L over its valid pixels, plus kp_L[n];
+ *   - a segment without a valid pixel is flagged invisible and receives the lower median, rank (nvis - 1) / 2, of the nvis
+ *     visible segments' results (equal results are ordered by segment index; the value is one of them, bit for bit);
+ *   - NO segment visible: every out_kld is 0 and every flag 0 (the reference's torch.median raises on the empty selection). */
 int sp_segment_reinit(const uint32_t* pix, const float* baseL, const int32_t* seg_off, const float* kp_L, int N,
                       int P, int H, int W, const float* est_depth, int mode, float* scratch, float* out_kld,
                       uint8_t* out_visible, void* stream);
@@ -767,7 +785,11 @@ int sp_segment_reinit(const uint32_t* pix, const float* baseL, const int32_t* se
 /* depth_completion/segment_based_completion.py:21-27 render_depth_avg fused with the expansion and the
  * visible-segment filter: per-pixel mean over covering visible segments of exp(L + shift_n)
  * (visible may be NULL = all).  out_depth (H,W), out_invalid (H,W) u8.  acc: 12*H*W bytes of scratch
- * (32.32 fixed-point sums + counts: the accumulation is order-independent, hence reproducible). */
+ * (32.32 fixed-point sums + counts: the accumulation is order-independent, hence reproducible).
+ *   - a covering segment counts iff it is visible and its depth d > 1e-6 (a NaN or a vanishing depth is skipped);
+ *   - out_depth = sum / (count + 1e-6), the reference's divisor: about 1e-6 below the plain mean for count 1, and 0 / 1e-6 = 0
+ *     where nothing counts;
+ *   - out_invalid = (count == 0). */
 int sp_depth_average(const uint32_t* pix, const float* baseL, const int32_t* seg_off, const float* kp_L,
                      const float* kld, const uint8_t* visible, int N, int P, int H, int W, void* acc,
                      float* out_depth, uint8_t* out_invalid, void* stream);
