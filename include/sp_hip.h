@@ -937,6 +937,41 @@ int sp_mask_edges(const uint8_t* masks, int K, int H, int W, const int32_t* row_
 int sp_sam_cut_masks(const uint8_t* masks, int K, int H, int W, const float* edge_probs_or_null, float prob_thresh, const int32_t* kp_rc_or_null,
                      int32_t* keep, uint8_t* out_masks_or_null, uint8_t* final_coverage, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Frame ingest: raw camera frames already on the device -> KeyFrame-ready images and depth maps, one launch per batch of frames
+ * (additive, ABI 18).  The reference does this on the host for EVERY tracked frame (frontend/process_frame.py:257-270
+ * process_to_supp_kf; :207-255 process_to_kf for keyframes): cv2.undistort(image, K, d) on the 8-bit BGR frame
+ * (data/tum_undistort.py:113; the general form is data/image_transforms.py:36-60 initUndistortRectifyMap + remap), the margin
+ * crop [mh:-mh, mw:-mw] and BGR -> RGB (data/tum_undistort.py:86-90,127-130), tool/etc.py image_tt (uint8 / 255 -> float CHW), and
+ * frontend/process_frame.py:170-189 _downsample_to_target (bilinear F.interpolate; intrinsics by tool/camera.py:13-22).
+ *
+ * sp_frame_ingest: raw (B,H,W,3) u8 -> out (B,3,Ho,Wo) float.  With (u, v) a pixel of the full frame,
+ *   x = (u - cx) / fx, y = (v - cy) / fy, r2 = x^2 + y^2, kr = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3),
+ *   mx = fx (x kr + 2 p1 x y + p2 (r2 + 2 x^2)) + cx,   my = fy (y kr + p1 (r2 + 2 y^2) + 2 p2 x y) + cy
+ * (OpenCV's initUndistortRectifyMap with R = I and newCameraMatrix = K, which is what cv2.undistort uses), U(v, u, c) is the bilinear
+ * sample of raw at (mx, my) -- taps floor and floor + 1, a tap outside the frame contributes 0 (BORDER_CONSTANT 0; grid_sample's
+ * 'zeros') --, C(i, j) = U(i + top, j + left) for 0 <= i < Hc, 0 <= j < Wc, and out is F.interpolate(C, size=(Ho,Wo), mode='bilinear',
+ * align_corners=False): per axis s = max((a + 0.5) Hc / Ho - 0.5, 0), i0 = floor(s), i1 = min(i0 + 1, Hc - 1), weight s - i0.
+ * (Ho,Wo) == (Hc,Wc) is the identity.  Map and weights are float64; the value is the weighted sum of the integer taps, rounded to float
+ * once and DIVIDED by 255.0f, so zero distortion without crop or resize is image_tt bit for bit.  bgr != 0 reverses the channels.
+ * cv2.undistort itself returns uint8 from fixed-point coordinates; this keeps the float value (DESIGN.md §4 "Frame ingest").
+ *
+ * sp_depth_ingest: raw (B,H,W) u16 -> out (B,Ho,Wo) float: d = (float)v * scale in float32 and d > max_depth -> 0
+ * (data/tum_undistort.py:16-36 DepthScale, DepthFilter), the same crop (:128), then torch's nearest rule
+ * src = min((int)floorf(dst * ((float)in / out)), in - 1) per axis (odometery/odometery.py:152-156); (Ho,Wo) == (Hc,Wc): no resize.
+ *
+ * cam is read on the host.  A null pointer, out aliasing raw, a non-positive size or a crop that leaves the frame is SP_EINVAL;
+ * W > 32767, H W >= 2^31, B > 65535, Ho > 65535, or fx / fy not finite or <= 0 is SP_ELIMIT; both before any device work.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct SpCamera {
+    double fx, fy, cx, cy;
+    double k1, k2, p1, p2, k3, k4, k5, k6;   /* OpenCV's order; absent coefficients are 0 */
+} SpCamera;                                  /* 96 bytes */
+int sp_frame_ingest(const uint8_t* raw, int B, int H, int W, const SpCamera* cam, int top, int left, int Hc, int Wc, int Ho, int Wo,
+                    int bgr, float* out, void* stream);
+int sp_depth_ingest(const uint16_t* raw, int B, int H, int W, float scale, float max_depth, int top, int left, int Hc, int Wc, int Ho,
+                    int Wo, float* out, void* stream);
+
 /* odometery/kf_criteria.py:7-21 translation_difference, :23-34 rotation_difference and the depth-validity ratio of
  * odometery/odometery.py:1003-1004, in one launch without a host sync.  depth: n floats (the rendered depth of the
  * latest keyframe); poses row-major 4x4.  out[4] = {#(depth > thresh)/n, scale = lower median of the valid depths

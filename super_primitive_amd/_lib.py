@@ -94,6 +94,8 @@ SIGNATURES = {
     "sp_sam_build_masks": [P, P, I, I, I, I, F, P, P, P],
     "sp_mask_edges": [P, I, I, I, P, P, I, I, P, P, I, P],
     "sp_sam_cut_masks": [P, I, I, I, P, F, P, P, P, P, P],
+    "sp_frame_ingest": [P, I, I, I, P, I, I, I, I, I, I, I, P, P],
+    "sp_depth_ingest": [P, I, I, I, F, F, I, I, I, I, I, I, P, P],
 }
 
 SP_ABI_VERSION = 18
@@ -241,6 +243,11 @@ class SpChainStep(ctypes.Structure):
                 ("kf_pose", c_void_p), ("N", c_int), ("P", c_int), ("keys", c_void_p), ("depth_out", c_void_p), ("rel_pose", c_void_p),
                 ("crit", c_void_p), ("crit_ws", c_void_p), ("crit_host", c_void_p), ("valid_thresh", c_float), ("track_iters", c_int), ("supp_iters", c_int),
                 ("pad_", c_int)]
+
+
+class SpCamera(ctypes.Structure):
+    """Mirror of ``struct SpCamera`` (include/sp_hip.h): pinhole intrinsics and OpenCV's distortion coefficients; 96 bytes, host memory."""
+    _fields_ = [(name, ctypes.c_double) for name in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")]
 
 
 class SpWindowNode(ctypes.Structure):
