@@ -337,7 +337,12 @@ int sp_pairs_cost_opt(const SpPair* pairs, const int32_t* chunks, const int32_t*
  * partials (fixed order, fp64), loss = |residual| like odometery/two_frame_sfm.py:201-206, maps d/dpose to the
  * tangent of Exp(a)*T, applies torch.optim.Adam semantics (betas 0.9/0.999, eps 1e-8, bias correction) with
  * per-group learning rates, retracts pose <- Exp(step)*pose.  state: per pair (2*(N+6+2)+2) floats, zeroed
- * by the caller before the first step.  losses: [n_pairs] written every step. */
+ * by the caller before the first step.  losses: [n_pairs] written every step.
+ * Pinned call by call (pair_adam_step_ref in tests/window_adam_step_ref.py, tests/test_gpu_pairs_adam_step.py): the sign is taken of the
+ * FLOAT32 residual (0 -> every gradient is zero and the moments still decay); state per pair = {step count, unused, m_kld[max_N],
+ * v_kld[max_N], m_xi[6], v_xi[6], m_aff[2], v_aff[2]} with nothing written behind N in m_kld / v_kld; the tangent starts from zero in every
+ * call (xi = the Adam step itself); only aff[2, 3] (the target's pair) move, aff[0, 1] and -- when aff is NULL -- m_aff / v_aff stay; the
+ * pose is Exp(xi) pose in float64 rounded once, its last row set to 0 0 0 1; bias corrections by pow() from the step count. */
 int sp_pairs_adam_step(const SpPair* pairs, int n_pairs, int max_N, const float* span_partials, const float* seg_partials,
                        float lr_kld, float lr_pose, float lr_aff, float* state, float* losses, void* stream);
 
@@ -650,7 +655,23 @@ int sp_window_compose(const SpPair* pairs, const SpWindowEdge* edges, int n_edge
  * freezes (later calls return without touching anything), like the break at odometery.py:907-915.
  * state: 12 floats, zeroed by the caller {Adam step count, iterations done, previous loss, converged flag, last loss, -,
  *   beta1^t and beta2^t as two doubles in [6..9]}; setting [0] = 0 restarts Adam's bias correction;
- * losses[max_losses]: loss of iteration i (evaluated BEFORE its update) at index i. */
+ * losses[max_losses]: loss of iteration i (evaluated BEFORE its update) at index i.
+ * Pinned call by call (tests/window_adam_step_ref.py restates one call in float64; tests/test_gpu_window_adam_step.py holds the device to it):
+ *   gradient   edge e enters with c_e = weight_e (abs_loss: weight_e sign(r_e), sign(0) = 0).  g_left = [g_t ; (A12 - A21, A20 - A02, A01 - A10)],
+ *              A = R g_R^T + t g_t^T from the edge's pose slot; kind-0 target += c g_left, source += -c Ad_P^T g_left, kind-1 target += c
+ *              <d(Exp(a) X)/da, dr/dP> (float32 dual numbers), affine target += c (d/da, d/db), source -=, block += c (segment sums).
+ *   Adam       on the float32 gradient, torch's operation order; only for nodes / blocks that an edge names and whose lr is > 0; the bias
+ *              corrections are the running products in state[6..9], restarted (with the moments kept) when state[0] == 0.
+ *   poses      kind 0: T <- T Exp(-a) in float64 rounded once whenever a != 0, a <- 0, then renormalise_se3 where flags & 1 -- also for a
+ *              node that is fixed or that no edge names; kind 1 keeps X and its tangent.  Every edge's pose slot (and aff slot, unless
+ *              SpPair.aff is NULL) is re-composed by every call that is not frozen, the skipped iteration 0 included.
+ *   state      [0] += 1 per update, [1] += 1 per call, [4] = loss; [2] is written only when rel_tol > 0; the freeze is decided on this call's
+ *              loss AFTER its update went in ([3] = 1; the call itself still updates; iteration 0 never freezes); losses[it] only for it <
+ *              max_losses; state[5, 10, 11] are never written; a frozen call writes nothing at all.
+ *   Pinned as they are, and questionable: (1) a kind-0 node with a non-zero tangent is folded in even when no edge names it and lr_pose = 0;
+ *   (2) under abs_loss an edge with r == 0 gives a zero gradient and still decays the moments of everything it touches, which moves those
+ *   parameters; (3) a kind-1 node named as a SOURCE would get the kind-0 source gradient added to its persistent tangent -- it is only ever
+ *   a target (above), and nothing tests that case on the device. */
 int sp_window_step(const SpPair* pairs, const SpWindowEdge* edges, int n_edges, SpWindowNode* nodes, int n_nodes,
                    const SpWindowBlock* blocks, int n_blocks, int max_N, const float* span_partials, const float* seg_partials,
                    double* scratch, int abs_loss, int skip_first, float rel_tol, float* state, float* losses, int max_losses,
