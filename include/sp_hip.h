@@ -836,29 +836,47 @@ int sp_renormalise_se3(float* T, int n, void* stream);
  * ---------------------------------------------------------------------------------------------------- */
 
 /* post_processer.py:13-36 depth_discontinuity + mask_by_depth_discontinuity: depth = exp(logdepth) (-1 where
- * !valid), filter_size x filter_size max-pool (stride 1), Scharr/32 gradient magnitude (reflect padding) > threshold.
- * split = valid & !discontinuity (N,H,W) u8; disc (optional) = valid & discontinuity.  scratch: N*H*W floats. */
+ * !valid), filter_size x filter_size max-pool (stride 1, -inf outside the image; filter_size odd, else SP_EINVAL), reflect
+ * padding by 1 (index -1 -> 1, n -> n - 2, so H, W >= 2), Scharr/32 gradient magnitude g > threshold.
+ * split = valid & !discontinuity (N,H,W) u8; disc (optional) = valid & discontinuity: together they partition valid.
+ * scratch: N*H*W floats (the pooled depth).  N <= 65535 (SP_ELIMIT).
+ * Pinned: g is a float32 evaluation of the float64 definition and lies within 14 * 2^-24 * max(1, max |pooled| over the
+ * pixel's 3x3 window) of it (the count of roundings is derived in tests/post_process_ref.py; measured: 0.12 of that), so
+ * the decision equals the float64 one at every pixel whose float64 g is farther than that from the threshold.
+ * Non-finite log-depths at valid pixels decide like the reference's max_pool2d + conv2d: the max lets a NaN win (a NaN
+ * depth makes every pooled value whose window holds it NaN), and all nine taps of each Scharr filter are multiplied, the
+ * zero weights included (0 * inf = NaN); a NaN magnitude is not above the threshold, so such a pixel is no discontinuity
+ * and stays in split.  Only a window whose infinite products all carry one sign gives g = inf, a discontinuity.  Values
+ * at invalid pixels are never read into the arithmetic. */
 int sp_depth_discontinuity(const float* logdepth, const uint8_t* valid, int N, int H, int W, int filter_size,
                            float threshold, float* scratch, uint8_t* split, uint8_t* disc, void* stream);
 
 /* post_processer.py:57-64 connected_components_batch (ndimage.label with the per-slice 4-connectivity structure):
- * labels[i] = 1 + (smallest linear index of i's component), 0 for background -- sorting components by label gives
- * scipy's scan-order numbering.  parent: N*H*W int32 scratch; sizes (optional, N*H*W int32): sizes[root] = pixels. */
+ * labels[i] = 1 + (smallest linear index, over the whole (N,H,W) array, of i's component), 0 for background -- sorting
+ * components by label gives scipy's scan-order numbering.  Nothing connects across slices, row ends or slice ends.  The
+ * result is exact and the same on every call (the union-find is lock-free, its result is not order-dependent).
+ * parent: N*H*W int32 scratch; sizes (optional, N*H*W int32): sizes[root] = pixels of the component, 0 at every other
+ * index.  N*H*W <= INT_MAX (SP_ELIMIT). */
 int sp_label_components(const uint8_t* fg, int N, int H, int W, int32_t* parent, int32_t* labels, int32_t* sizes,
                         void* stream);
 
-/* Compact list of components {slice, root, size} (unordered, at most cap entries; *n_parts = how many exist) and
- * bg_sizes[n] = |mask_n & !split_n| (the label-0 part post_process_kf forms, post_processer.py:127-133). */
+/* Compact list of components {slice, root, size}, one row per root pixel (labels[i] == i + 1), in no particular order,
+ * and bg_sizes[n] = |mask_n & !split_n| (the label-0 part post_process_kf forms, post_processer.py:127-133; masks may
+ * strictly contain split, and a slice with an empty split is counted like any other).  *n_parts = how many components
+ * exist, also when that exceeds cap; then the first cap rows of parts are distinct components, nothing is written
+ * behind row cap, and the caller calls again with cap >= *n_parts.  N*H*W <= INT_MAX (SP_ELIMIT). */
 int sp_collect_parts(const int32_t* labels, const int32_t* sizes, const uint8_t* masks, const uint8_t* split, int N, int H,
                      int W, int cap, int32_t* parts, int32_t* n_parts, int32_t* bg_sizes, void* stream);
 
 /* Materialise K part masks (K,H,W) u8.  parts[k] = {slice, kind, root}: kind 0 = component `root` of that slice,
- * 1 = mask & !split, 2 = the original mask of the slice (post_processer.py:138-146). */
+ * 1 = mask & !split, 2 = the original mask of the slice (post_processer.py:138-146); kind 0 is ANDed with the mask too, and
+ * one root may appear in several parts.  K <= 65535 (SP_ELIMIT). */
 int sp_build_part_masks(const uint8_t* masks, const uint8_t* split, const int32_t* labels, int H, int W,
                         const int32_t* parts, int K, uint8_t* out, void* stream);
 
 /* (row, col) of the kth[k]-th set pixel of mask k in raster order, i.e. torch.where(mask)[kth] as used by
- * sample_pts_in_mask (post_processer.py:67-84).  row_off: the row_counts output of sp_mask_count for these masks. */
+ * sample_pts_in_mask (post_processer.py:67-84).  row_off: the row_counts output of sp_mask_count for these masks.
+ * 0 <= kth[k] < count of mask k; empty rows in front of, inside and behind the mask are passed over. */
 int sp_kth_mask_pixel(const uint8_t* masks, const int32_t* row_off, int K, int H, int W, const int32_t* kth,
                       int32_t* out_rc, void* stream);
 

@@ -36,12 +36,14 @@ def label_slices(split):
     return out, total
 
 
-def fix_disconnected(frame, keep_ratio=1e-3):
+def fix_disconnected(frame, keep_ratio=1e-3, split=None):
     """Returns (masks (K,H,W) bool, logdepth (K,H,W), keypoints (K,2)); consumes torch's global RNG like the
-    reference (one ``torch.randint`` per part of every segment that is split into more than one kept part)."""
+    reference (one ``torch.randint`` per part of every segment that is split into more than one kept part).
+    ``split``: label this mask instead of the depth-discontinuity one (post_process_kf's ``connectivity`` argument)."""
     L, masks, kps = frame.logdepth_perseg, frame.keypoint_regions, frame.keypoints
     N, H, W = masks.shape
-    _, split = discontinuity(L, masks)
+    if split is None:
+        _, split = discontinuity(L, masks)
     labels, _ = label_slices(split)
     dims = torch.tensor([H, W], dtype=torch.float32)
     new_m, new_L, new_k = [], [], []

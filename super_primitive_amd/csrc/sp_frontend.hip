@@ -8,7 +8,8 @@
 namespace {
 
 // frontend/segment/post_processer.py:17-21: depth = exp(logdepth), -1 where invalid, fs x fs max-pool, stride 1,
-// implicit -inf padding
+// implicit -inf padding.  The max propagates a NaN like max_pool2d does (fmaxf would drop it): once a window has met a
+// NaN depth at a valid pixel its result is NaN.
 __global__ __launch_bounds__(SP_BLOCK) void k_masked_depth_maxpool(const float* __restrict__ logdepth,
                                                                    const uint8_t* __restrict__ valid, int H, int W, int fs,
                                                                    float* __restrict__ out) {
@@ -24,7 +25,8 @@ __global__ __launch_bounds__(SP_BLOCK) void k_masked_depth_maxpool(const float* 
             const int x = c + dx;
             if (x < 0 || x >= W) continue;
             const size_t j = base + (size_t)y * W + x;
-            m = fmaxf(m, valid[j] ? expf(logdepth[j]) : -1.f);
+            const float d = valid[j] ? expf(logdepth[j]) : -1.f;
+            if (d > m || d != d) m = d;
         }
     }
     out[base + i] = m;
@@ -32,7 +34,9 @@ __global__ __launch_bounds__(SP_BLOCK) void k_masked_depth_maxpool(const float* 
 
 __device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
-// image/image_processing.py:4-30 (Scharr /32, reflect padding) + post_processer.py:26-27,31-36
+// image/image_processing.py:4-30 (Scharr /32, reflect padding) + post_processer.py:26-27,31-36.  The three zero weights of
+// each filter multiply their taps like conv2d's do: they add nothing to a finite window and turn an infinite or NaN tap into
+// a NaN gradient, which is no discontinuity.
 __global__ __launch_bounds__(SP_BLOCK) void k_scharr_split(const float* __restrict__ pooled, const uint8_t* __restrict__ valid,
                                                            int H, int W, float threshold, uint8_t* __restrict__ split,
                                                            uint8_t* __restrict__ disc) {
@@ -47,8 +51,10 @@ __global__ __launch_bounds__(SP_BLOCK) void k_scharr_split(const float* __restri
         for (int dx = 0; dx < 3; ++dx)
             v[dy][dx] = pooled[base + (size_t)reflect1(r + dy - 1, H) * W + reflect1(c + dx - 1, W)];
     const float k = 1.f / 32.f;
-    const float gx = k * (-3.f * v[0][0] + 3.f * v[0][2] - 10.f * v[1][0] + 10.f * v[1][2] - 3.f * v[2][0] + 3.f * v[2][2]);
-    const float gy = k * (-3.f * v[0][0] - 10.f * v[0][1] - 3.f * v[0][2] + 3.f * v[2][0] + 10.f * v[2][1] + 3.f * v[2][2]);
+    const float gx = k * (-3.f * v[0][0] + 3.f * v[0][2] - 10.f * v[1][0] + 10.f * v[1][2] - 3.f * v[2][0] + 3.f * v[2][2])
+                     + (0.f * v[0][1] + 0.f * v[1][1] + 0.f * v[2][1]);
+    const float gy = k * (-3.f * v[0][0] - 10.f * v[0][1] - 3.f * v[0][2] + 3.f * v[2][0] + 10.f * v[2][1] + 3.f * v[2][2])
+                     + (0.f * v[1][0] + 0.f * v[1][1] + 0.f * v[1][2]);
     const bool ok = valid[base + i] != 0;
     const bool d = ok && (sqrtf(gx * gx + gy * gy) > threshold);
     split[base + i] = ok && !d;
@@ -157,6 +163,7 @@ int sp_depth_discontinuity(const float* logdepth, const uint8_t* valid, int N, i
                            float threshold, float* scratch, uint8_t* split, uint8_t* disc, void* stream) {
     if (!logdepth || !valid || !scratch || !split || N <= 0 || H < 2 || W < 2) return SP_EINVAL;
     if (filter_size < 1 || !(filter_size & 1)) return SP_EINVAL;
+    if (N > 65535) return SP_ELIMIT;                             // grid.y
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((H * W + SP_BLOCK - 1) / SP_BLOCK, N);
     hipLaunchKernelGGL(k_masked_depth_maxpool, grid, dim3(SP_BLOCK), 0, s, logdepth, valid, H, W, filter_size, scratch);
@@ -190,6 +197,7 @@ int sp_collect_parts(const int32_t* labels, const int32_t* sizes, const uint8_t*
                      int W, int cap, int32_t* parts, int32_t* n_parts, int32_t* bg_sizes, void* stream) {
     if (!labels || !sizes || !masks || !split || !parts || !n_parts || !bg_sizes || N <= 0 || H <= 0 || W <= 0 || cap <= 0)
         return SP_EINVAL;
+    if ((long long)N * H * W > 0x7fffffffLL) return SP_ELIMIT;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(n_parts, 0, sizeof(int32_t), s);
     if (e != hipSuccess) return (int)e;
@@ -205,6 +213,7 @@ int sp_collect_parts(const int32_t* labels, const int32_t* sizes, const uint8_t*
 int sp_build_part_masks(const uint8_t* masks, const uint8_t* split, const int32_t* labels, int H, int W,
                         const int32_t* parts, int K, uint8_t* out, void* stream) {
     if (!masks || !split || !labels || !parts || !out || K <= 0 || H <= 0 || W <= 0) return SP_EINVAL;
+    if (K > 65535) return SP_ELIMIT;                             // grid.y
     hipLaunchKernelGGL(k_build_part_masks, dim3((H * W + SP_BLOCK - 1) / SP_BLOCK, K), dim3(SP_BLOCK), 0,
                        static_cast<hipStream_t>(stream), masks, split, labels, H * W, parts, out);
     SP_CHECK_LAUNCH();
