@@ -1125,6 +1125,61 @@ typedef struct SpChainStep {
 int sp_chain_multi_bytes(void);
 int sp_chain_step_multi(SpChainStep* steps, int n_steps, void* args_dev, float* states_dev, float* states_host, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Sequence results (sp_results.hip): the similarity alignment of trajectories and the world map of keyframes.
+ *
+ * sp_traj_align: S trajectories in ONE launch, one workgroup each -- what tool/pose_utils.py `align` (:71-133) and `transfer_scale`
+ * (:16-48) compute for the translations of pred (the model) against those of gt (the data), accumulated and decomposed in float64:
+ *   zero-centred cross-covariance W = sum mz dz^T; rot = U S Vh of svd(W^T) with S = diag(1, 1, -1) when det(U) det(Vh) < 0 (one-sided
+ *   Jacobi; the third left vector is taken as u1 x u2, so a rank-2 W -- an exactly planar trajectory -- has its unique answer);
+ *   s = dots / norms; trans_scaled = mean(d) - s rot mean(m); trans = mean(d) - rot mean(m); the per-pose errors |s rot m + trans_scaled - d|
+ *   and |rot m + trans - d| with their root mean squares (the absolute trajectory error with and without scale); with anchor_rotation
+ *   rot_reanchor = R_gt[0] R_pred[0]^T, else the identity.
+ *     pred, gt    : (S, n_max, 4, 4) float32, camera-to-world; rows at and beyond lengths[s] are never read
+ *     lengths     : (S,) int32 on the device, each 3 .. n_max (the CALLER checks: the entry point sees a device pointer; the kernel
+ *                   clamps to 0 .. n_max)
+ *     out         : S records
+ *     err_scaled, err : (S, n_max) float64 per-pose errors; entries at and beyond lengths[s] are written as 0
+ * S in 1 .. 65535, n_max >= 3 (SP_EINVAL), S * n_max * 16 <= INT_MAX (SP_ELIMIT). */
+typedef struct SpTrajAlign {
+    double rot[9];                     /* row major */
+    double trans_scaled[3];
+    double trans[3];
+    double s;
+    double rot_reanchor[9];            /* row major; the identity without anchor_rotation */
+    double ate_scaled, ate;            /* root mean square of the per-pose errors with / without scale */
+    double dots, norms;                /* s = dots / norms */
+    double sigma[3];                   /* singular values of W, descending */
+} SpTrajAlign;                         /* 256 bytes */
+int sp_traj_align(const float* pred, const float* gt, const int32_t* lengths, int S, int n_max, int anchor_rotation, SpTrajAlign* out,
+                  double* err_scaled, double* err, void* stream);
+
+/* sp_map_points: the coloured world points of n_kf keyframes in ONE launch (gui/odometery_gui.py:569-575,665-686 get_dense_pcd per window
+ * keyframe).  Keyframe k contributes Q_k = ceil(P_k / stride) rows from out_offset on: row o is table point o * stride (table order is the
+ * reference's nonzero order, so this is src_pts[::stride]), its camera-frame point p by sp_photo_stats' arithmetic (decode_pix,
+ * exp(baseL + (kld[n] - kp_L[n])), backproject).  Without an alignment record the world point is R p + t in float32 fma; with record a it is
+ * R' (s p) + t' with R' = a.rot_reanchor R and t' = a.s a.rot t + a.trans_scaled (apply_scale, tool/pose_utils.py:50-68), R' and t'
+ * formed in float64 and rounded once.  The colour is image[:, row, col] (a load, no interpolation).  Nothing is filtered.
+ *     kfs       : n_kf records on the device; out_offset and first_block are the prefix sums of Q_k and of ceil(Q_k / 256) (the caller's
+ *                 host arithmetic: no device value is needed to size the call)
+ *     total_blocks, total_rows : the two sums; rows at or beyond total_rows are never written
+ *     align     : n_align records on the device, or NULL with n_align 0
+ *     points, colours : (total_rows, 3) float32; kf_index, seg_ids : (total_rows,) int32
+ * n_kf in 1 .. 65535, stride >= 1, total_blocks >= 1, total_rows in 1 .. 256 * total_blocks (SP_EINVAL). */
+typedef struct SpMapKeyframe {
+    const uint32_t* pix; const float* baseL; const int32_t* seg_off; const float* kp_L;   /* the keyframe's SegmentTable */
+    const float* kld;                  /* N keypoint log-depths */
+    const float* image;                /* planar (3, H, W), level 0 */
+    const float* K;                    /* 9 floats */
+    const float* pose;                 /* 16 floats, camera-to-world */
+    int32_t N, P, H, W;
+    long long out_offset;              /* first output row */
+    int32_t align;                     /* index of an SpTrajAlign record, or -1 */
+    int32_t first_block;               /* first workgroup of the launch that works on this keyframe */
+} SpMapKeyframe;                       /* 96 bytes */
+int sp_map_points(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int stride, const SpTrajAlign* align, int n_align, float* points,
+                  float* colours, int32_t* kf_index, int32_t* seg_ids, long long total_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,8 @@ SIGNATURES = {
     "sp_sam_cut_masks": [P, I, I, I, P, F, P, P, P, P, P],
     "sp_frame_ingest": [P, I, I, I, P, I, I, I, I, I, I, I, P, P],
     "sp_depth_ingest": [P, I, I, I, F, F, I, I, I, I, I, I, P, P],
+    "sp_traj_align": [P, P, P, I, I, I, P, P, P, P],
+    "sp_map_points": [P, I, I, I, P, I, P, P, P, P, ctypes.c_longlong, P],
 }
 
 SP_ABI_VERSION = 18
@@ -248,6 +250,23 @@ class SpChainStep(ctypes.Structure):
 class SpCamera(ctypes.Structure):
     """Mirror of ``struct SpCamera`` (include/sp_hip.h): pinhole intrinsics and OpenCV's distortion coefficients; 96 bytes, host memory."""
     _fields_ = [(name, ctypes.c_double) for name in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")]
+
+
+SP_TRAJ_ALIGN_DOUBLES = 32
+
+
+class SpTrajAlign(ctypes.Structure):
+    """Mirror of ``struct SpTrajAlign`` (include/sp_hip.h): the similarity alignment of one trajectory; 256 bytes, device memory."""
+    _fields_ = [("rot", ctypes.c_double * 9), ("trans_scaled", ctypes.c_double * 3), ("trans", ctypes.c_double * 3), ("s", ctypes.c_double),
+                ("rot_reanchor", ctypes.c_double * 9), ("ate_scaled", ctypes.c_double), ("ate", ctypes.c_double), ("dots", ctypes.c_double),
+                ("norms", ctypes.c_double), ("sigma", ctypes.c_double * 3)]
+
+
+class SpMapKeyframe(ctypes.Structure):
+    """Mirror of ``struct SpMapKeyframe`` (include/sp_hip.h): one keyframe of a world-map launch; 96 bytes, device memory."""
+    _fields_ = [("pix", c_void_p), ("baseL", c_void_p), ("seg_off", c_void_p), ("kp_L", c_void_p), ("kld", c_void_p), ("image", c_void_p),
+                ("K", c_void_p), ("pose", c_void_p), ("N", c_int), ("P", c_int), ("H", c_int), ("W", c_int), ("out_offset", ctypes.c_longlong),
+                ("align", c_int), ("first_block", c_int)]
 
 
 class SpWindowNode(ctypes.Structure):

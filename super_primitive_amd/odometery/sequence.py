@@ -45,7 +45,7 @@ def _sync():
 DEFAULTS = dict(track_steps=(0, 0, 300), track_levels=(0, 3), track_lr=5e-3, map_steps=500, continual_steps=10, init_steps=1000,
                 map_lr_pose=1e-4, window_size=5, supp_every_n=3, depth_validity_ratio=0.60, translation_thresh=0.2,
                 affine_compensation=True, mono_init=False, init_frames=7, motion_prior=False, persistent_supp=True, map_rel_tol=1e-8,
-                native_step=True)
+                native_step=True, keep_keyframes=False)
 
 
 class _Supp:
@@ -67,6 +67,9 @@ class MonoVO:
         self.affine = bool(self.c['affine_compensation'])
         self.kfs, self.kf_ids, self.kf_poses, self.kf_klds, self.kf_affs, self.supp_opt = [], [], [], [], [], []
         self.all_kf_ids = []
+        # the results the reference reports: every keyframe's pose as of the last scheduled / init mapping that held it (the reference's
+        # ``global_kf_trajectory``, odometery.py:279,960-962) and what a keyframe held when it left the window (``result()['kf_archive']``)
+        self.kf_trajectory, self.retired = {}, {}
         self.reset_tracked_poses()
         self.reset_running_supp_kfs()
         self.initialised = not self.c['mono_init']
@@ -82,6 +85,7 @@ class MonoVO:
         self.chain = None
         self.native = bool(self.c['native_step']) and engine == "gn" and not self.c['motion_prior'] and self.dev.type == "cuda"
         self.add_kf(to_keyframe(0), pose0.clone(), kld0.clone(), 0, self.current_aff.clone())
+        self.kf_trajectory[0] = self.kf_poses[0]
         self.update_track_pose('init')
         self.track = [pose0.clone()]
 
@@ -95,8 +99,14 @@ class MonoVO:
 
     def pop_kf(self, i):
         self.supp_mapper = None
+        self.retired[self.kf_ids[i]] = self._archive_entry(i)
         for lst in (self.kfs, self.kf_ids, self.kf_poses, self.kf_klds, self.kf_affs, self.supp_opt):
             lst.pop(i)
+
+    def _archive_entry(self, i):
+        """What window keyframe ``i`` holds now (references: these tensors are replaced, never written in place).  The ``KeyFrame`` itself --
+        masks and log-depth planes, megabytes -- only with ``keep_keyframes``: by default a long sequence keeps its device memory flat."""
+        return dict(pose=self.kf_poses[i], kld=self.kf_klds[i], aff=self.kf_affs[i], kf=self.kfs[i] if self.c['keep_keyframes'] else None)
 
     def reset_tracked_poses(self):
         self.tracked = []
@@ -245,6 +255,10 @@ class MonoVO:
                                                                kf_poses=[p.clone() for p in self.kf_poses], n_supp=[len(r) for r in rows],
                                                                losses=[float(out['losses'][0]), float(out['losses'][-1])], n=len(out['losses']),
                                                                gn=out.get('gn'))))
+        if mode != 'supp':
+            # (the supplementary mapping moves no pose, and with the Gauss-Newton engine it does not come through here: the trajectory
+            #  records the poses a scheduled or init mapping left, on every path alike -- references, no launch)
+            self.kf_trajectory.update(zip(self.kf_ids, self.kf_poses))
         self.update_track_pose(mode)
         self.initialised = True
 
@@ -452,7 +466,9 @@ class MonoVO:
     def result(self):
         return dict(track_poses=torch.stack(self.track), kf_ids=list(self.kf_ids), all_kf_ids=list(self.all_kf_ids), kf_poses=torch.stack(self.kf_poses),
                     kf_klds=self.kf_klds, kf_affs=self.kf_affs, supp_ids=[[s.ts for s in row] for row in self.supp_opt],
-                    n_mappings=self.n_map['map'], n_supp_mappings=self.n_map['supp'], n_init_mappings=self.n_map['init'], seconds=self.secs, frontend_seconds=self.frontend_secs)
+                    n_mappings=self.n_map['map'], n_supp_mappings=self.n_map['supp'], n_init_mappings=self.n_map['init'], seconds=self.secs, frontend_seconds=self.frontend_secs,
+                    kf_trajectory=dict(self.kf_trajectory),
+                    kf_archive={**self.retired, **{ts: self._archive_entry(i) for i, ts in enumerate(self.kf_ids)}})
 
 
 def run_sequence(frames, to_keyframe, pose0, kld0, engine="gn", **cfg):
@@ -460,5 +476,8 @@ def run_sequence(frames, to_keyframe, pose0, kld0, engine="gn", **cfg):
     to_keyframe(i) -> KeyFrame of frame i (the frontend's job in the reference: segments + per-segment log-depth shapes);
     pose0: camera-to-world of frame 0; kld0: keypoint log-depths of the first keyframe; ``depth_of(i)``: optional keypoint log-depths
     for the second keyframe (the reference's ground-truth-depth initialisation); other keywords override ``DEFAULTS``.
-    Returns dict(track_poses (n,4,4) camera-to-world as tracked, kf_ids, kf_poses, kf_klds, n_mappings, seconds dict, ...)."""
+    Returns dict(track_poses (n,4,4) camera-to-world as tracked, kf_ids, kf_poses, kf_klds, n_mappings, seconds dict, ...,
+    kf_trajectory {frame id: (4,4) pose as of the last scheduled / init mapping that held the keyframe; the start pose for frame 0},
+    kf_archive {frame id: dict(pose, kld, aff, kf)} of every keyframe ever added: frozen when it left the window, current while in it;
+    ``kf`` is the KeyFrame with ``keep_keyframes=True`` (what ``odometery.results.sequence_map`` needs), else None)."""
     return MonoVO(frames, to_keyframe, pose0, kld0, engine=engine, **cfg).run()
