@@ -73,7 +73,13 @@ int sp_table_fill(const uint8_t* masks, const float* logdepth, const float* keyp
 /* Sample one source pyramid level at every table point and pack {rgb, L}.  set_validity != 0: also compute the
  * source validity bit of pix with the reference's formula (core/dense_optim.py:143-162 applied to the source
  * frame, :315-317); it depends on the geometry grid only (not on the level), so it is set by the first sampling
- * after the table is built and pix is read-only afterwards.  img: planar (3,Hl,Wl) f32.  K: 9 floats row-major. */
+ * after the table is built and pix is read-only afterwards.  img: planar (3,Hl,Wl) f32.  K: 9 floats row-major.
+ * The formula, per point, in this operation order: d = exp(L + (kld[n] - kp_L[n])); x = (col - cx) d / fx;
+ * zinv = 1 / d where |d| > 1e-6, else the CONSTANT 1e-6 (core/ops.py:19-40: such a point re-projects onto the
+ * principal point, not onto its own pixel); u = x fx zinv + cx; xn = 2 u (1 / (W - 1)) - 1 (rows alike with H);
+ * valid = |xn| <= 0.99 and |yn| <= 0.99 and d > 1e-7 (false for a NaN log-depth).  The colour is the bilinear
+ * sample (align-corners: ix = (xn + 1) 0.5 (Wl - 1)) at that position for EVERY point, valid or not -- the points
+ * of the border band and of the zinv branch included; taps outside the level read as zero.  src4.w is L itself. */
 int sp_table_sample_source(uint32_t* pix, const float* baseL, const int32_t* seg_off, const float* kp_L,
                            const float* kld, int N, int P, int H, int W, const float* img, int Hl, int Wl,
                            const float* K, float* src4, int set_validity, void* stream);
@@ -82,7 +88,9 @@ int sp_table_sample_source(uint32_t* pix, const float* baseL, const int32_t* seg
 int sp_pack_rgb(const float* chw, int B, int H, int W, float* hwc3, void* stream);
 
 /* One pyramid step of image/gaussian_pyramid.py:53-85: reflect-pad 1, 3x3 binomial /16, keep even rows and
- * columns.  in: planar (C,H,W); out: planar (C,ceil(H/2),ceil(W/2)). */
+ * columns.  in: planar (C,H,W); out: planar (C,ceil(H/2),ceil(W/2)).  A dimension of ONE pixel has nothing to
+ * reflect onto (torch refuses that padding): the pixel itself is taken, so a 1 x 1 level blurs to itself --
+ * here and in the batched passes (sp_prepare_blur, sp_prepare_blur_pack). */
 int sp_blur_decimate(const float* in, int C, int H, int W, float* out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------

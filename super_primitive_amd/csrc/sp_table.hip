@@ -247,7 +247,9 @@ __global__ __launch_bounds__(SP_BLOCK) void k_pack_rgb(const float* __restrict__
     pack_texel(chw + (size_t)blockIdx.y * 3 * HW, HW, i, out + (size_t)blockIdx.y * HW * SP_TEXEL_FLOATS);
 }
 
-__device__ __forceinline__ int reflect1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+// (a dimension of ONE pixel has nothing to reflect onto: indices -1 and 1 would land outside it -- the pixel itself is taken,
+//  so a 1-pixel level blurs to itself; torch's reflect padding refuses that size)
+__device__ __forceinline__ int reflect1(int i, int n) { return n == 1 ? 0 : (i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i)); }
 
 // image/gaussian_pyramid.py:53-85: reflect pad 1, depthwise [1 2 1;2 4 2;1 2 1]/16, keep [::2, ::2]
 __device__ __forceinline__ float blur_decimate_at(const float* __restrict__ p, int H, int W, int Wo, int i) {
@@ -1441,7 +1443,7 @@ int sp_pack_rgb(const float* chw, int B, int H, int W, float* hwc3, void* stream
 }
 
 int sp_blur_decimate(const float* in, int C, int H, int W, float* out, void* stream) {
-    if (!in || !out || C <= 0 || H < 2 || W < 2) return SP_EINVAL;
+    if (!in || !out || C <= 0 || H < 1 || W < 1) return SP_EINVAL;
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
     hipLaunchKernelGGL(k_blur_decimate, dim3((Ho * Wo + SP_BLOCK - 1) / SP_BLOCK, C), dim3(SP_BLOCK), 0,
                        static_cast<hipStream_t>(stream), in, H, W, Ho, Wo, out);

@@ -602,11 +602,14 @@ def _check_against_per_keyframe_tables(batch, prs, granule=256):
             Hl, Wl = batch.level_hw[l][m]
             off = sum(3 * h * w for h, w in batch.level_hw[l][:m])
             assert np.array_equal(npy(batch.trg4[l][off: off + 3 * Hl * Wl]), npy(packed_target(lv_t[l]).reshape(-1)))
-    _check_decimated_tables(batch)
+    _check_decimated_tables(batch, prs, granule)
 
 
-def _check_decimated_tables(batch):
-    """decimated tables: lattice points of the full table, in order, same validity bits, same source samples"""
+def _check_decimated_tables(batch, prs, granule=256):
+    """decimated tables: lattice points of the full table, in order, same validity bits, same source samples -- and, against the
+    independent reference (tests/point_table_ref.py), EVERY lattice pixel of the masks in torch.where order at its place in the padded
+    layout, the points whose validity bit is clear included, with zeros in the padding"""
+    import point_table_ref as ref
     for (level, stride), lay in batch.coarse.items():
         chunks = npy(lay.chunks)
         for m in range(batch.M):
@@ -625,6 +628,16 @@ def _check_decimated_tables(batch):
             keep_valid = on & ((full_pix >> 31) == 1)
             assert np.array_equal(mpix[(mpix >> 31) == 1], full_pix[keep_valid]), (level, stride, m)
             assert np.array_equal(msrc[(mpix >> 31) == 1], full_src[keep_valid]), (level, stride, m)
+            pr = prs[m]
+            t = ref.table_ref(pr.keypoint_regions, pr.logdepth_perseg, pr.keypoints, stride)
+            pos, pad, total = ref.padded_layout(t["counts"], granule)
+            assert len(mine) == total and lay.points[m] == len(t["pix"]), (level, stride, m)
+            ref.check_table(t["counts"], mpix[pos], None, None, t, f"level {level} stride {stride} pair {m}")
+            assert not mpix[pad].any() and not msrc[pad].view(np.uint32).any(), (level, stride, m)
+            t1 = ref.table_ref(pr.keypoint_regions, pr.logdepth_perseg, pr.keypoints, 1)
+            pos1 = ref.padded_layout(t1["counts"], granule)[0]
+            lattice = ((t1["pix"] & 0xffff) % stride == 0) & ((t1["pix"] >> 16) % stride == 0)
+            assert np.array_equal(mpix[pos], full_pix[pos1][lattice]) and np.array_equal(msrc[pos], full_src[pos1][lattice]), (level, stride, m)
 
 
 def test_fill_pass_on_bit_words_with_every_lattice_stride_and_the_widest_rows():
@@ -649,7 +662,7 @@ def test_fill_pass_on_bit_words_with_every_lattice_stride_and_the_widest_rows():
             assert np.array_equal(pix[idx], npy(tab.pix).view(np.uint32) & 0x7fffffff), m
             pad = np.ones(hi - lo, bool); pad[idx] = False
             assert not pix[pad].any()
-        _check_decimated_tables(batch)
+        _check_decimated_tables(batch, prs)
 
 
 @pytest.mark.parametrize("optimisers", [1, 3])
