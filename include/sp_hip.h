@@ -1188,6 +1188,52 @@ typedef struct SpMapKeyframe {
 int sp_map_points(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int stride, const SpTrajAlign* align, int n_align, float* points,
                   float* colours, int32_t* kf_index, int32_t* seg_ids, long long total_rows, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Map views (sp_views.hip): a point set rendered into camera views, and depth images lifted into a point cloud.  Both run on the
+ * caller's stream without a synchronisation; argument checks come before any device work.
+ *
+ * sp_render_views: V views of one point set in ONE call (tool/viz.py:180-190 render_pcd is mode 0 with one identity-pose view).
+ *     points   : (Q,3) float32;  colours : (Q,3) float32 (may be NULL when image is)
+ *     views    : V records on the device, pose camera-to-world (row major 4x4; the last row is not read)
+ *     keys     : V H W uint64 of scratch, zeroed by the call
+ *     image    : (V,H,W,3) uint8;  depth : (V,H,W) float32;  index : (V,H,W) int32 -- each may be NULL
+ * In float64 from the float32 inputs, every operation rounded on its own (no fma, no reciprocal):  d = p - t,
+ * p_c = ((R0r d0 + R1r d1) + R2r d2) for r = x, y, z (R^T d; a pose that is exactly the identity leaves p_c = p untouched, as render_pcd
+ * does), u = x fx / z + cx, v = y fy / z + cy.  A point is kept iff 0 <= u < W and 0 <= v < H (NaN and +-inf fail); its pixel is
+ * (trunc v, trunc u).
+ *     mode 0 : no test on z (points behind the camera are kept, as the reference keeps them); the kept point with the HIGHEST index
+ *              wins the pixel (NumPy's repeated-index assignment)
+ *     mode 1 : additionally z > z_min; the kept point with the smallest float32(z) wins, equal float32(z) goes to the highest index
+ * index = the winner (or -1); depth = float32(z) of the winner (or exactly 0); image = trunc(colour * 255) per channel from the exact
+ * float64 product, clamped to 0 .. 255 (the reference's astype(uint8) wraps), NaN gives 0; an untouched pixel is 0, 0, 0.  Integer
+ * atomic maxima: two runs give the same bits.
+ * Null points / views / keys (or colours with an image), Q, V, H or W <= 0, mode outside {0, 1}, z_min negative or NaN: SP_EINVAL.
+ * Q > 2^31 - 2, V > 65535, V H W >= 2^31: SP_ELIMIT. */
+typedef struct SpView {
+    float K[9];                        /* row major; fx = K[0], fy = K[4], cx = K[2], cy = K[5] */
+    float pose[16];                    /* camera-to-world */
+} SpView;                              /* 100 bytes */
+int sp_render_views(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, int mode, float z_min,
+                    unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream);
+
+/* sp_depth_lift: B depth images into one point cloud (tool/viz.py:30-51 depth_image_lift: Open3D's create_from_depth_image with
+ * depth_scale 1, stride 1 and depth_trunc, then transform).
+ *     depth : (B,H,W) float32;  K : (B,9) float32;  pose : (B,16) float32 camera-to-world or NULL (the identity)
+ *     image : planar (B,3,H,W) float32 or NULL, together with colours
+ *     block_counts : sp_depth_lift_blocks(B, H, W) int32 of scratch
+ * A pixel is valid iff 0 < d <= depth_trunc (NaN is invalid).  Valid pixels are compacted in row-major order, image after image: row
+ * offsets[b] + k is the k-th valid pixel of image b.  Three passes (count per 256-pixel block, scan of the block counts, write); no
+ * workgroup waits on another.
+ *     points  : (B H W, 3) float32.  In float64 from the float32 inputs, every operation rounded on its own:  x = ((c - cx) d) / fx,
+ *               y = ((r - cy) d) / fy, z = d, then per row of the pose ((T0 x + T1 y) + T2 z) + T3; rounded to float32 once, at the end
+ *     colours : (B H W, 3) float32 = image[b, :, r, c] (a load);  pixel : (B H W,) int32 = r W + c
+ *     counts  : (B,) int32;  offsets : (B + 1,) int64;  rows at or beyond offsets[B] are never written
+ * Null required pointers, image without colours (or the reverse), B, H, W <= 0, depth_trunc not > 0: SP_EINVAL.  B > 65535 or
+ * B H W >= 2^31: SP_ELIMIT (sp_depth_lift_blocks returns the same codes). */
+int sp_depth_lift_blocks(int B, int H, int W);
+int sp_depth_lift(const float* depth, const float* K, const float* pose, const float* image, int B, int H, int W, float depth_trunc,
+                  int32_t* block_counts, float* points, float* colours, int32_t* pixel, int32_t* counts, long long* offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

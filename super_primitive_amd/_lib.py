@@ -98,6 +98,9 @@ SIGNATURES = {
     "sp_depth_ingest": [P, I, I, I, F, F, I, I, I, I, I, I, P, P],
     "sp_traj_align": [P, P, P, I, I, I, P, P, P, P],
     "sp_map_points": [P, I, I, I, P, I, P, P, P, P, ctypes.c_longlong, P],
+    "sp_render_views": [P, P, ctypes.c_longlong, P, I, I, I, I, F, P, P, P, P, P],
+    "sp_depth_lift_blocks": [I, I, I],
+    "sp_depth_lift": [P, P, P, P, I, I, I, F, P, P, P, P, P, P, P],
 }
 
 SP_ABI_VERSION = 18
@@ -267,6 +270,14 @@ class SpMapKeyframe(ctypes.Structure):
     _fields_ = [("pix", c_void_p), ("baseL", c_void_p), ("seg_off", c_void_p), ("kp_L", c_void_p), ("kld", c_void_p), ("image", c_void_p),
                 ("K", c_void_p), ("pose", c_void_p), ("N", c_int), ("P", c_int), ("H", c_int), ("W", c_int), ("out_offset", ctypes.c_longlong),
                 ("align", c_int), ("first_block", c_int)]
+
+
+SP_VIEW_FLOATS = 25
+
+
+class SpView(ctypes.Structure):
+    """Mirror of ``struct SpView`` (include/sp_hip.h): one camera of sp_render_views; 100 bytes, device memory (a (V, 25) float32 tensor)."""
+    _fields_ = [("K", c_float * 9), ("pose", c_float * 16)]
 
 
 class SpWindowNode(ctypes.Structure):

@@ -1,0 +1,274 @@
+// Map views: a point set rendered into camera views (tool/viz.py:163-190 project_points_np / render_pcd, as gui/sfm_gui.py:460-468 uses
+// it, plus a depth-buffer mode the reference does not have) and depth images lifted into a point cloud (tool/viz.py:30-51
+// depth_image_lift, i.e. Open3D's PointCloud.create_from_depth_image with depth_scale 1, stride 1, then transform).
+//
+// sp_render_views.  Splat pass: one thread per point, its three floats staged through LDS (one coalesced read of the workgroup's 3 x 256
+// floats), then a loop over the views.  Every 16 views the workgroup forms their float64 numbers once into LDS -- R^T (9), t (3), fx, fy,
+// cx, cy and an "identity pose" flag -- so the per-view operands are wave-uniform LDS broadcasts.  Arithmetic in float64 from the float32
+// inputs, every operation rounded on its own (contraction is switched off for this file: the reference is NumPy in float64):
+//     d = p - t;   p_c = ((Rt0 d0 + Rt1 d1) + Rt2 d2) per row   (an exact identity pose skips both: p_c = p, as render_pcd has it --
+//     0 x inf would otherwise turn a point at z = inf, which the reference keeps, into NaN);   u = x fx / z + cx;   v = y fy / z + cy.
+// Kept iff 0 <= u < W and 0 <= v < H (NaN and +-inf fail); pixel (trunc v, trunc u).  One 64-bit atomicMax per kept (point, view), no
+// return value; a relaxed load of the key first skips points that already lose (the race is benign: the atomic decides).
+//     mode 0  key = (i + 1) << 32 | bits(float32 z): the highest index wins, NumPy's repeated-index assignment; no test on z at all
+//     mode 1  key = ~bits(float32 z) << 32 | (i + 1), only for z > z_min >= 0 (float32 z is then a non-negative float, whose bits order as
+//             unsigned integers): the smallest float32 z wins, equal float32 z goes to the highest index
+// Resolve pass: one thread per pixel decodes the winner: index (or -1), depth = float32 z (or 0), image = trunc(c * 255) from the exact
+// float64 product, clamped to 0 .. 255, NaN -> 0 (or 0, 0, 0).  Integer maxima commute: two runs give the same bits.
+//
+// sp_depth_lift.  Three plain passes, no workgroup waits on another: (1) per 256-pixel block of one image the number of valid pixels
+// (0 < d <= depth_trunc; NaN invalid) by ballot and popcount; (2) one workgroup scans the block counts in place (exclusive) and writes
+// offsets and counts; (3) every block recomputes its ballot and writes its valid pixels at block offset + rank: row-major order, image
+// after image.  Point arithmetic in float64, every operation rounded on its own, rounded to float32 once at the end:
+//     x = ((c - cx) d) / fx;   y = ((r - cy) d) / fy;   z = d;   world = ((T0 x + T1 y) + T2 z) + T3 per row (no pose: the point itself).
+#include "sp_device.h"
+
+#pragma clang fp contract(off)
+
+static_assert(sizeof(SpView) == 100, "view records are part of the ABI");
+
+namespace {
+
+constexpr int VIEW_CHUNK = 16;
+
+struct ViewD {
+    double Rt[9], t[3];                // R^T row major, t: p_c = R^T (p - t)
+    double fx, fy, cx, cy;
+    int ident, pad_;
+};
+
+__device__ __forceinline__ void view_setup(const SpView& v, ViewD& o) {
+    bool ident = true;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float e = v.pose[4 * c + r];
+            o.Rt[3 * r + c] = (double)e;
+            ident = ident && e == (r == c ? 1.f : 0.f);
+        }
+        const float t = v.pose[4 * r + 3];
+        o.t[r] = (double)t;
+        ident = ident && t == 0.f;
+    }
+    o.fx = (double)v.K[0]; o.fy = (double)v.K[4]; o.cx = (double)v.K[2]; o.cy = (double)v.K[5];
+    o.ident = ident ? 1 : 0;
+    o.pad_ = 0;
+}
+
+// grid ceil(Q / 256), block SP_BLOCK
+__global__ __launch_bounds__(SP_BLOCK) void k_render_keys(const float* __restrict__ points, int Q, const SpView* __restrict__ views, int V,
+                                                          int H, int W, int mode, float z_min, unsigned long long* __restrict__ keys) {
+    __shared__ float sp[3 * SP_BLOCK];
+    __shared__ ViewD vd[VIEW_CHUNK];
+    const int tid = threadIdx.x;
+    // the workgroups take the points from the END of the set: in mode 0 the highest index wins, so the early workgroups set keys that
+    // most later points lose against, and the load before the atomic skips them (ascending, every point would beat what it finds)
+    const long long first = (long long)(gridDim.x - 1 - blockIdx.x) * SP_BLOCK;
+    const int n = (int)((long long)Q - first < SP_BLOCK ? (long long)Q - first : SP_BLOCK);
+    for (int j = tid; j < 3 * n; j += SP_BLOCK) sp[j] = points[3 * first + j];
+    const size_t HW = (size_t)H * W;
+    const double Wd = (double)W, Hd = (double)H, zmin = (double)z_min;
+    const uint32_t id1 = (uint32_t)(first + tid) + 1u;     // index + 1 (Q <= 2^31 - 2)
+    for (int v0 = 0; v0 < V; v0 += VIEW_CHUNK) {
+        const int nv = V - v0 < VIEW_CHUNK ? V - v0 : VIEW_CHUNK;
+        __syncthreads();                                   // (sp is written; the previous chunk has been read)
+        if (tid < nv) view_setup(views[v0 + tid], vd[tid]);
+        __syncthreads();
+        if (tid >= n) continue;
+        const double px = (double)sp[3 * tid], py = (double)sp[3 * tid + 1], pz = (double)sp[3 * tid + 2];
+        for (int k = 0; k < nv; ++k) {
+            const ViewD& w = vd[k];
+            double x = px, y = py, z = pz;
+            if (!w.ident) {
+                const double d0 = px - w.t[0], d1 = py - w.t[1], d2 = pz - w.t[2];
+                x = (w.Rt[0] * d0 + w.Rt[1] * d1) + w.Rt[2] * d2;
+                y = (w.Rt[3] * d0 + w.Rt[4] * d1) + w.Rt[5] * d2;
+                z = (w.Rt[6] * d0 + w.Rt[7] * d1) + w.Rt[8] * d2;
+            }
+            const double u = (x * w.fx) / z + w.cx;
+            const double v = (y * w.fy) / z + w.cy;
+            if (!(u >= 0.0 && u < Wd && v >= 0.0 && v < Hd)) continue;
+            if (mode == 1 && !(z > zmin)) continue;
+            const uint32_t zb = __float_as_uint((float)z);
+            const unsigned long long key = mode == 1 ? ((unsigned long long)(~zb) << 32) | (unsigned long long)id1
+                                                     : ((unsigned long long)id1 << 32) | (unsigned long long)zb;
+            unsigned long long* slot = keys + (size_t)(v0 + k) * HW + (size_t)(int)v * W + (size_t)(int)u;
+            if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= key) continue;
+            atomicMax(slot, key);
+        }
+    }
+}
+
+__device__ __forceinline__ uint8_t colour_u8(float c) {
+    const double p = (double)c * 255.0;                    // exact: 24 + 8 significant bits
+    if (!(p > 0.0)) return 0;                              // NaN, zero, negative
+    return p >= 255.0 ? (uint8_t)255 : (uint8_t)(int)p;
+}
+
+// grid ceil(V H W / 256), block SP_BLOCK
+__global__ __launch_bounds__(SP_BLOCK) void k_render_resolve(const unsigned long long* __restrict__ keys, const float* __restrict__ colours,
+                                                             int n_pix, int mode, uint8_t* __restrict__ image, float* __restrict__ depth,
+                                                             int32_t* __restrict__ index) {
+    const long long at = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (at >= n_pix) return;
+    const unsigned long long k = keys[at];
+    int idx = -1;
+    float d = 0.f;
+    if (k) {
+        const uint32_t hi = (uint32_t)(k >> 32), lo = (uint32_t)(k & 0xffffffffull);
+        idx = (int)((mode == 1 ? lo : hi) - 1u);
+        d = __uint_as_float(mode == 1 ? ~hi : lo);
+    }
+    if (index) index[at] = idx;
+    if (depth) depth[at] = d;
+    if (image) {
+        uint8_t rgb[3] = {0, 0, 0};
+        if (idx >= 0) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) rgb[ch] = colour_u8(colours[3 * (size_t)idx + ch]);
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) image[3 * (size_t)at + ch] = rgb[ch];
+    }
+}
+
+// ---- depth lift ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool lift_valid(float d, float depth_trunc) { return d > 0.f && d <= depth_trunc; }
+
+// grid (ceil(H W / 256), B)
+__global__ __launch_bounds__(SP_BLOCK) void k_lift_count(const float* __restrict__ depth, int HW, float depth_trunc,
+                                                         int32_t* __restrict__ block_counts) {
+    __shared__ int wc[SP_WAVES];
+    const int p = blockIdx.x * SP_BLOCK + threadIdx.x;
+    const bool ok = p < HW && lift_valid(depth[(size_t)blockIdx.y * HW + p], depth_trunc);
+    const unsigned long long ballot = __ballot(ok);
+    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(ballot);
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (wc[0] + wc[1]) + (wc[2] + wc[3]);
+}
+
+// one workgroup: bc[n] (n = B nblk) becomes its exclusive prefix sum; offsets[b] = the prefix at image b's first block, offsets[B] the
+// total, counts[b] = offsets[b + 1] - offsets[b]
+__global__ __launch_bounds__(SP_BLOCK) void k_lift_scan(int32_t* __restrict__ bc, int n, int nblk, int B, int32_t* __restrict__ counts,
+                                                        long long* __restrict__ offsets) {
+    __shared__ long long part[SP_BLOCK];
+    const int tid = threadIdx.x;
+    const int per = (n + SP_BLOCK - 1) / SP_BLOCK;
+    const long long j0 = (long long)tid * per;
+    const long long j1 = j0 + per < n ? j0 + per : n;
+    long long s = 0;
+    for (long long j = j0; j < j1; ++j) s += bc[j];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        long long run = 0;
+        for (int t = 0; t < SP_BLOCK; ++t) { const long long x = part[t]; part[t] = run; run += x; }
+        offsets[B] = run;
+    }
+    __syncthreads();
+    long long run = part[tid];
+    for (long long j = j0; j < j1; ++j) {
+        const int c = bc[j];
+        bc[j] = (int32_t)run;
+        if (j % nblk == 0) offsets[j / nblk] = run;
+        run += c;
+    }
+    __syncthreads();
+    for (int b = tid; b < B; b += SP_BLOCK) counts[b] = (int32_t)(offsets[b + 1] - offsets[b]);
+}
+
+// grid (ceil(H W / 256), B)
+__global__ __launch_bounds__(SP_BLOCK) void k_lift_write(const float* __restrict__ depth, const float* __restrict__ K,
+                                                         const float* __restrict__ pose, const float* __restrict__ image, int HW, int W,
+                                                         float depth_trunc, const int32_t* __restrict__ block_offsets,
+                                                         float* __restrict__ points, float* __restrict__ colours,
+                                                         int32_t* __restrict__ pixel) {
+    __shared__ int wc[SP_WAVES];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int p = blockIdx.x * SP_BLOCK + threadIdx.x;
+    const float df = p < HW ? depth[(size_t)b * HW + p] : 0.f;
+    const bool ok = p < HW && lift_valid(df, depth_trunc);
+    const unsigned long long ballot = __ballot(ok);
+    if (lane == 0) wc[wave] = __popcll(ballot);
+    __syncthreads();
+    if (!ok) return;
+    size_t row = (size_t)block_offsets[(size_t)b * gridDim.x + blockIdx.x] + (size_t)__popcll(ballot & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) row += (size_t)wc[w];
+    const float* Kb = K + 9 * (size_t)b;
+    const double fx = (double)Kb[0], fy = (double)Kb[4], cx = (double)Kb[2], cy = (double)Kb[5];
+    const int r = p / W, c = p - r * W;
+    const double d = (double)df;
+    double x = (((double)c - cx) * d) / fx;
+    double y = (((double)r - cy) * d) / fy;
+    double z = d;
+    if (pose) {
+        const float* T = pose + 16 * (size_t)b;
+        const double wx = (((double)T[0] * x + (double)T[1] * y) + (double)T[2] * z) + (double)T[3];
+        const double wy = (((double)T[4] * x + (double)T[5] * y) + (double)T[6] * z) + (double)T[7];
+        const double wz = (((double)T[8] * x + (double)T[9] * y) + (double)T[10] * z) + (double)T[11];
+        x = wx; y = wy; z = wz;
+    }
+    points[3 * row] = (float)x;
+    points[3 * row + 1] = (float)y;
+    points[3 * row + 2] = (float)z;
+    if (colours) {
+        const float* img = image + 3 * (size_t)b * HW + p;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) colours[3 * row + ch] = img[(size_t)ch * HW];
+    }
+    pixel[row] = p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sp_render_views(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, int mode, float z_min,
+                    unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream) {
+    if (!points || !views || !keys || (image && !colours)) return SP_EINVAL;
+    if (Q <= 0 || V <= 0 || H <= 0 || W <= 0 || (mode != 0 && mode != 1) || !(z_min >= 0.f)) return SP_EINVAL;
+    const long long HW = (long long)H * W;
+    if (Q > 0x7ffffffeLL || V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long n_pix = (long long)V * HW;
+    hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)n_pix, s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_render_keys, dim3((unsigned)((Q + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, points, (int)Q, views, V, H, W,
+                       mode, z_min, keys);
+    SP_CHECK_LAUNCH();
+    if (image || depth || index) {
+        hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((n_pix + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, keys, colours,
+                           (int)n_pix, mode, image, depth, index);
+        SP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int sp_depth_lift_blocks(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return SP_EINVAL;
+    const long long HW = (long long)H * W;
+    if (B > 65535 || HW >= 0x80000000LL || (long long)B * HW >= 0x80000000LL) return SP_ELIMIT;
+    return (int)((long long)B * ((HW + SP_BLOCK - 1) / SP_BLOCK));
+}
+
+int sp_depth_lift(const float* depth, const float* K, const float* pose, const float* image, int B, int H, int W, float depth_trunc,
+                  int32_t* block_counts, float* points, float* colours, int32_t* pixel, int32_t* counts, long long* offsets, void* stream) {
+    if (!depth || !K || !block_counts || !points || !pixel || !counts || !offsets || ((image == nullptr) != (colours == nullptr)))
+        return SP_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0 || !(depth_trunc > 0.f)) return SP_EINVAL;
+    const int n = sp_depth_lift_blocks(B, H, W);
+    if (n < 0) return n;
+    const int HW = H * W, nblk = n / B;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_lift_count, dim3(nblk, B), dim3(SP_BLOCK), 0, s, depth, HW, depth_trunc, block_counts);
+    SP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_lift_scan, dim3(1), dim3(SP_BLOCK), 0, s, block_counts, n, nblk, B, counts, offsets);
+    SP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_lift_write, dim3(nblk, B), dim3(SP_BLOCK), 0, s, depth, K, pose, image, HW, W, depth_trunc, block_counts, points,
+                       colours, pixel);
+    SP_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // extern "C"

@@ -5,6 +5,8 @@
                       (gui/odometery_gui.py:569-575,665-686).  Here keyframes of any sizes, of any number of sequences, go through ONE
                       ``sp_map_points`` launch (include/sp_hip.h) that writes world points, colours, keyframe index and segment id.
 ``sequence_map``      the map of a ``run_sequence(..., keep_keyframes=True)`` result, aligned against ground-truth poses when given.
+``render_map``        the map seen from V cameras (image, depth buffer, winning point per pixel), ONE ``sp_render_views`` launch.
+``score_map``         the map's depth buffer in the ground-truth views against ground-truth depth: ``sp_depth_metrics`` and the coverage.
 ``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``."""
 from __future__ import annotations
 
@@ -101,6 +103,59 @@ def sequence_map(result, stride, gt_poses=None, anchor_rotation=True):
     out['ids'] = ids
     out.update(extra)
     return out
+
+
+def _view_cameras(Ks, poses, what):
+    """(V,3,3) cameras and (V,4,4) poses from tensors or lists; ``Ks`` may be one (3,3) for all."""
+    poses = poses if torch.is_tensor(poses) else torch.stack(list(poses))
+    Ks = Ks if torch.is_tensor(Ks) else torch.stack(list(Ks))
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.shape[0] == 0:
+        raise ValueError(f"{what}: poses must be (V,4,4), got {tuple(poses.shape)}")
+    return Ks, poses
+
+
+def render_map(world, Ks, poses, size, depth_buffer=True):
+    """The map seen from V cameras in ONE ``sp_render_views`` launch (``tool.viz.render_views``): ``world`` is what ``keyframe_points`` or
+    ``sequence_map`` returned (its ``points`` and ``colours``), ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world in the map's
+    frame, ``size`` = (H, W).  ``depth_buffer=True``: the nearest point in front of the camera wins a pixel; False: the reference's
+    ``render_pcd`` (the highest index wins, nothing is tested against z).
+    Returns dict(image (V,H,W,3) uint8, depth (V,H,W) float32 -- 0 where nothing landed --, index (V,H,W) int32 -- the winning row of
+    ``world['points']``, -1 where nothing landed).  Per-pixel keyframe and segment maps follow from it:
+    ``torch.where(index >= 0, world['kf_index'][index.clamp(min=0).long()], -1)``, and the same with ``world['seg_ids']``.
+    No synchronisation."""
+    from ..tool import viz
+    Ks, poses = _view_cameras(Ks, poses, "render_map")
+    H, W = size
+    return viz.render_views(world['points'], world['colours'], Ks, poses, H, W, depth_buffer=depth_buffer)
+
+
+def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size=None):
+    """The map against ground-truth depth images: its depth buffer is rendered into each of the V ground-truth views (``render_map``'s
+    launch, depth only) and scored where it landed.  ``gt_depths`` (V,H,W) float32, ``Ks`` (V,3,3) or (3,3), ``gt_poses`` (V,4,4)
+    camera-to-world; the map should already be in the ground truth's frame, as ``sequence_map(gt_poses=...)`` delivers it.
+    A pixel is scored iff the rendered depth is > 0 and ``min_depth <= gt <= max_depth``.  ONE ``sp_depth_metrics`` call for all views.
+    Returns dict(metrics (V,12) float64 on the device, columns: the names of its columns (``depth_completion.void``: n, rmse, mae, absrel
+    in mm, inv_rmse, inv_mae, inv_absrel in 1/km, delta105, delta110, delta1, delta2, delta3), coverage (V,) float64 = scored pixels /
+    pixels with ``min_depth <= gt <= max_depth`` (NaN for a view without any)).  ``size``: an (H, W) the depths must have, if given.
+    No synchronisation."""
+    from ..depth_completion import void
+    from ..tool import viz
+    Ks, gt_poses = _view_cameras(Ks, gt_poses, "score_map")
+    if not torch.is_tensor(gt_depths) or gt_depths.dim() != 3 or gt_depths.shape[0] != gt_poses.shape[0] or gt_depths.dtype != torch.float32:
+        raise ValueError(f"score_map: gt_depths must be float32 (V,H,W) for {gt_poses.shape[0]} views, got "
+                         f"{tuple(gt_depths.shape) if torch.is_tensor(gt_depths) else type(gt_depths).__name__}")
+    if not float(min_depth) <= float(max_depth):
+        raise ValueError(f"score_map: depth range {min_depth} .. {max_depth}")
+    V, H, W = gt_depths.shape
+    if size is not None and tuple(int(s) for s in size) != (H, W):
+        raise ValueError(f"score_map: size {tuple(size)} against ground-truth depths of {H}x{W}")
+    _lib.require_device(gt_depths, world['points'])
+    depth = viz.render_views(world['points'], None, Ks, gt_poses, H, W, depth_buffer=True, image=False, index=False)['depth']
+    in_range = (gt_depths >= min_depth) & (gt_depths <= max_depth)
+    scored = in_range & (depth > 0)
+    metrics = void.depth_metrics(depth, gt_depths, scored)
+    coverage = scored.sum(dim=(1, 2)).double() / in_range.sum(dim=(1, 2)).double()
+    return dict(metrics=metrics, columns=void._COLUMNS, coverage=coverage)
 
 
 def write_tum_format(timestamps, pred_poses, gt_poses, out_dir):

@@ -1,0 +1,165 @@
+"""The two array routines of the reference's ``tool/viz.py`` that the viewers call, on the device (csrc/sp_views.hip; no open3d, cv2 or
+matplotlib is imported):
+
+``render_pcd``         ``tool/viz.py:180-190``: camera-frame points splatted into an (H,W,3) uint8 image, the highest index winning a pixel;
+                       with ``depth_buffer=True`` the nearest point wins instead.
+``depth_image_lift``   ``tool/viz.py:30-51``: a depth image lifted into a coloured point cloud (Open3D's ``create_from_depth_image`` with
+                       ``depth_scale=1, depth_trunc=100, stride=1``, then ``transform(T)``).  Returns tensors, not an Open3D object.
+``lift_depth_images``  the batched lift without a synchronisation.
+``render_views``       the call under ``render_pcd`` and ``odometery.results.render_map``: V posed views of one point set per launch.
+
+Argument errors raise ``ValueError`` before anything is launched."""
+from __future__ import annotations
+
+import torch
+
+from .. import _lib
+
+Z_MIN = 1e-6          # the depth buffer's near bound: the project's figure in sp_depth_splat
+
+
+def _on_device(*tensors):
+    for t in tensors:
+        if t is not None and not torch.is_tensor(t):
+            raise ValueError(f"super_primitive_amd.tool.viz takes cuda tensors, got {type(t).__name__}")
+    try:
+        _lib.require_device(*tensors)
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+
+
+def _f32(t, shape, what):
+    """``t`` as a contiguous float32 tensor of ``shape`` (None: any size there); points, colours and depths must be float32 already."""
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what} must be float32, got {t.dtype}")
+    if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError(f"{what} must have shape {tuple('*' if s is None else s for s in shape)}, got {tuple(t.shape)}")
+    return t.detach().contiguous()
+
+
+def _cameras(K, n, what):
+    """(n,9) float32 from (3,3) (shared by all) or (n,3,3) of any floating type."""
+    if not K.is_floating_point() or tuple(K.shape) not in ((3, 3), (n, 3, 3)):
+        raise ValueError(f"{what} must be floating (3,3) or ({n},3,3), got {K.dtype} {tuple(K.shape)}")
+    return K.detach().float().reshape(-1, 9).expand(n, 9).contiguous()
+
+
+def _poses(T, n, what):
+    if not T.is_floating_point() or tuple(T.shape) not in ((4, 4), (n, 4, 4)):
+        raise ValueError(f"{what} must be floating (4,4) or ({n},4,4), got {T.dtype} {tuple(T.shape)}")
+    return T.detach().float().reshape(-1, 16).expand(n, 16).contiguous()
+
+
+def _size(H, W):
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError(f"image size {H}x{W}")
+    return H, W
+
+
+def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_MIN, image=True, depth=True, index=True):
+    """ONE ``sp_render_views`` launch (include/sp_hip.h has the arithmetic): ``points`` (Q,3) float32 in the world, ``colours`` (Q,3)
+    float32 in 0..1 (None allowed without ``image``), ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world.  Returns the requested
+    of ``image`` (V,H,W,3) uint8, ``depth`` (V,H,W) float32 (0 where nothing landed) and ``index`` (V,H,W) int32 (-1 there) as a dict.
+    No synchronisation."""
+    _on_device(points, colours, Ks, poses)
+    H, W = _size(H, W)
+    if poses.dim() != 3:
+        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
+    V = int(poses.shape[0])
+    pts = _f32(points, (None, 3), "points")
+    Q = int(pts.shape[0])
+    if Q == 0 or V == 0:
+        raise ValueError(f"render_views: {Q} points into {V} views")
+    if image and colours is None:
+        raise ValueError("render_views: an image needs colours")
+    cols = None if colours is None else _f32(colours, (Q, 3), "colours")
+    views = torch.cat((_cameras(Ks, V, "Ks"), _poses(poses, V, "poses")), dim=1).contiguous()         # V x SpView
+    if not float(z_min) >= 0.0:
+        raise ValueError(f"z_min {z_min}")
+    if Q > 2 ** 31 - 2 or V > 65535 or V * H * W >= 2 ** 31:
+        raise ValueError(f"render_views: {Q} points, {V} views of {H}x{W} are beyond the kernel's limits")
+    lib = _lib.load()
+    dev = pts.device
+    keys = torch.empty(V * H * W, dtype=torch.int64, device=dev)
+    out = {}
+    if image:
+        out['image'] = torch.empty(V, H, W, 3, dtype=torch.uint8, device=dev)
+    if depth:
+        out['depth'] = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    if index:
+        out['index'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    _lib.check(lib.sp_render_views(_lib.ptr(pts), _lib.ptr(cols), Q, _lib.ptr(views), V, H, W, 1 if depth_buffer else 0, float(z_min),
+                                   _lib.ptr(keys), _lib.ptr(out.get('image')), _lib.ptr(out.get('depth')), _lib.ptr(out.get('index')),
+                                   _lib.stream_ptr()), "sp_render_views")
+    return out
+
+
+def render_pcd(points_3d, points_colour, K, H, W, *, depth_buffer=False, return_maps=False):
+    """``tool/viz.py:180-190``: ``points_3d`` (Q,3) float32 in the CAMERA frame, ``points_colour`` (Q,3) float32 in 0..1, ``K`` (3,3).
+    Returns the (H,W,3) uint8 image; with ``return_maps`` also the (H,W) float32 depth and (H,W) int32 point index of every pixel.
+    The default is the reference: no test on z, the highest index wins a pixel (colours beyond 0..1 are clamped where the reference's
+    ``astype(uint8)`` wraps).  ``depth_buffer=True``: only z > 1e-6, the nearest point wins."""
+    _on_device(points_3d, points_colour, K)
+    if tuple(K.shape) != (3, 3):
+        raise ValueError(f"K must be (3,3), got {tuple(K.shape)}")
+    eye = torch.eye(4, dtype=torch.float32, device=points_3d.device)[None]
+    out = render_views(points_3d, points_colour, K, eye, H, W, depth_buffer=depth_buffer, depth=return_maps, index=return_maps)
+    return (out['image'][0], out['depth'][0], out['index'][0]) if return_maps else out['image'][0]
+
+
+def lift_depth_images(depths, Ks, poses=None, images=None, depth_trunc=100.0):
+    """ONE ``sp_depth_lift`` call: ``depths`` (B,H,W) float32, ``Ks`` (B,3,3) or (3,3), ``poses`` (B,4,4) camera-to-world or None,
+    ``images`` (B,3,H,W) float32 or None.  A pixel is valid iff 0 < d <= depth_trunc.  Returns the CAPACITY buffers ``points`` (B H W, 3),
+    ``colours`` (B H W, 3) (with images), ``pixel`` (B H W,) int32 = r W + c, and ``counts`` (B,) int32, ``offsets`` (B+1,) int64 on the
+    device: row offsets[b] + k is the k-th valid pixel of image b in row-major order; rows from offsets[B] on are uninitialised.
+    No synchronisation."""
+    _on_device(depths, Ks, poses, images)
+    d = _f32(depths, (None, None, None), "depths")
+    B, H, W = (int(s) for s in d.shape)
+    if B == 0 or H == 0 or W == 0:
+        raise ValueError(f"depths {tuple(d.shape)}")
+    K = _cameras(Ks, B, "Ks")
+    T = None if poses is None else _poses(poses, B, "poses")
+    img = None if images is None else _f32(images, (B, 3, H, W), "images")
+    if not float(depth_trunc) > 0.0:
+        raise ValueError(f"depth_trunc {depth_trunc}")
+    lib = _lib.load()
+    n_blocks = lib.sp_depth_lift_blocks(B, H, W)
+    if n_blocks < 0:
+        raise ValueError(f"lift_depth_images: {B} images of {H}x{W} are beyond the kernel's limits")
+    dev, cap = d.device, B * H * W
+    scratch = torch.empty(n_blocks, dtype=torch.int32, device=dev)
+    out = dict(points=torch.empty(cap, 3, dtype=torch.float32, device=dev), pixel=torch.empty(cap, dtype=torch.int32, device=dev),
+               counts=torch.empty(B, dtype=torch.int32, device=dev), offsets=torch.empty(B + 1, dtype=torch.int64, device=dev))
+    if img is not None:
+        out['colours'] = torch.empty(cap, 3, dtype=torch.float32, device=dev)
+    _lib.check(lib.sp_depth_lift(_lib.ptr(d), _lib.ptr(K), _lib.ptr(T), _lib.ptr(img), B, H, W, float(depth_trunc), _lib.ptr(scratch),
+                                 _lib.ptr(out['points']), _lib.ptr(out.get('colours')), _lib.ptr(out['pixel']), _lib.ptr(out['counts']),
+                                 _lib.ptr(out['offsets']), _lib.stream_ptr()), "sp_depth_lift")
+    return out
+
+
+def depth_image_lift(depth, K, image=None, mask=None, T=None, depth_trunc=100.0):
+    """``tool/viz.py:30-51`` for one image: ``depth`` (H,W) float32, ``K`` (3,3), ``image`` (3,H,W) float32 (the project's planar layout,
+    already in 0..1), ``T`` (4,4) camera-to-world.  ``mask``: as in the reference, a boolean over the COMPACTED rows (one entry per valid
+    pixel, row-major), applied to points, colours and pixel.  Returns ``dict(points (n,3), colours (n,3) or None, pixel (n,))`` trimmed to
+    the valid count: reading that count is the ONE synchronisation of this call (``lift_depth_images`` has none)."""
+    _on_device(depth, K, image, mask, T)
+    if depth.dim() != 2:
+        raise ValueError(f"depth must be (H,W), got {tuple(depth.shape)}")
+    if image is not None and image.dim() != 3:
+        raise ValueError(f"image must be (3,H,W), got {tuple(image.shape)}")
+    if T is not None and tuple(T.shape) != (4, 4):
+        raise ValueError(f"T must be (4,4), got {tuple(T.shape)}")
+    if mask is not None and mask.dtype != torch.bool:
+        raise ValueError(f"mask must be boolean, got {mask.dtype}")
+    out = lift_depth_images(depth[None], K, None if T is None else T[None], None if image is None else image[None], depth_trunc)
+    n = int(out['offsets'][1])                                               # the one host read
+    res = dict(points=out['points'][:n], colours=out['colours'][:n] if image is not None else None, pixel=out['pixel'][:n])
+    if mask is not None:
+        mask = mask.reshape(-1)
+        if mask.numel() != n:
+            raise ValueError(f"mask has {mask.numel()} entries for {n} valid pixels")
+        res = {k: (None if v is None else v[mask]) for k, v in res.items()}
+    return res
