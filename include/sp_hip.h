@@ -1216,6 +1216,36 @@ typedef struct SpView {
 int sp_render_views(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, int mode, float z_min,
                     unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream);
 
+/* sp_render_splats: sp_render_views' depth buffer (mode 1) with a FOOTPRINT per point, so that a map sparser than the view leaves no
+ * holes and a near surface hides a far one.  The arguments of sp_render_views without `mode`, plus
+ *     radii  : (Q,) float32, the half side of the point's square footprint in world units
+ *     max_px : the largest half-width in pixels, 0 .. 16
+ * Per (point, view) u, v, z exactly as sp_render_views forms them; then, in float64, ru = (r fx) / z and rv = (r fy) / z.  A half-width
+ * that is not >= 0 (a negative or NaN radius, inf / inf) becomes 0; otherwise it is min(., max_px), so an infinite radius gives max_px.
+ * The point is kept iff u and v are finite, z > z_min, and the square [u - ru, u + ru] x [v - rv, v + rv] touches the image:
+ * u + ru >= 0, u - ru < W, v + rv >= 0, v - rv < H.  It covers the columns max(floor(u - ru), 0) .. min(floor(u + ru), W - 1) and the
+ * rows likewise (clamped in float64, then converted): at most 33 x 33 pixels.  A pixel is covered when its cell [c, c + 1) meets the
+ * square, NOT when its centre lies inside: a footprint of exactly one source pixel (ru = 0.5) therefore usually covers 2 x 2 pixels
+ * (floor(u + 0.5) = floor(u - 0.5) + 1 wherever the two sums are exact), and one of half a pixel 1 or 2 per axis.
+ * Every covered pixel is contested with mode 1's key: the smallest float32(z) wins, equal float32(z) goes to the highest index; the
+ * depth written is the point's float32(z) on all of its pixels (a splat is flat, fronto-parallel).  With radius 0 the range is the one
+ * pixel (trunc v, trunc u) and the call is sp_render_views in mode 1, bit for bit.  Outputs as there; integer maxima: two runs give the
+ * same bits.
+ * Null points / views / keys / radii (or colours with an image), Q, V, H or W <= 0, z_min negative or NaN, max_px outside 0 .. 16:
+ * SP_EINVAL.  Q > 2^31 - 2, V > 65535, V H W >= 2^31: SP_ELIMIT. */
+int sp_render_splats(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, float z_min,
+                     const float* radii, int max_px, unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream);
+
+/* sp_image_metrics: rendered views against real images, in ONE launch.
+ *     rendered : (V,H,W,3) uint8 (sp_render_views' / sp_render_splats' image);  index : (V,H,W) int32 (their index)
+ *     target   : planar (V,3,H,W) float32, converted by the renderer's own rule: trunc(c * 255) from the exact float64 product, clamped
+ *                to 0 .. 255, NaN gives 0
+ *     out      : (V,3) int64, zeroed by the call: per view, over the pixels with index >= 0 and their three channels,
+ *                n (pixels), sum |a - b|, sum (a - b)^2
+ * All integers: exact, independent of the order of the sums.  Null pointers, V, H or W <= 0: SP_EINVAL.  V > 65535 or V H W >= 2^31:
+ * SP_ELIMIT. */
+int sp_image_metrics(const uint8_t* rendered, const float* target, const int32_t* index, int V, int H, int W, long long* out, void* stream);
+
 /* sp_depth_lift: B depth images into one point cloud (tool/viz.py:30-51 depth_image_lift: Open3D's create_from_depth_image with
  * depth_scale 1, stride 1 and depth_trunc, then transform).
  *     depth : (B,H,W) float32;  K : (B,9) float32;  pose : (B,16) float32 camera-to-world or NULL (the identity)

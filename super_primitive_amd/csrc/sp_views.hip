@@ -16,6 +16,15 @@
 // Resolve pass: one thread per pixel decodes the winner: index (or -1), depth = float32 z (or 0), image = trunc(c * 255) from the exact
 // float64 product, clamped to 0 .. 255, NaN -> 0 (or 0, 0, 0).  Integer maxima commute: two runs give the same bits.
 //
+// sp_render_splats.  The splat pass of mode 1 with a footprint per point (its radius staged through LDS beside its coordinates): the
+// half-widths ru = (r fx) / z, rv = (r fy) / z in float64, not >= 0 -> 0, capped at max_px; the thread loops over the pixels whose cell
+// meets [u - ru, u + ru] x [v - rv, v + rv], clipped to the image (bounds clamped in float64 before the conversion: at most 33 x 33),
+// with the same load-then-atomicMax per pixel and the point's one key: a splat is flat.  The resolve pass is k_render_resolve, unchanged.
+//
+// sp_image_metrics.  One launch, grid (ceil(H W / 1024), V): per counted pixel (index >= 0) and channel d = |rendered - u8(target)| with
+// the resolve pass's conversion; n, sum d and sum d^2 as 32-bit integers per thread, wave (lane swaps) and workgroup (LDS), then one 64-bit
+// integer atomicAdd per workgroup and quantity.  Integers: exact, whatever the order.
+//
 // sp_depth_lift.  Three plain passes, no workgroup waits on another: (1) per 256-pixel block of one image the number of valid pixels
 // (0 < d <= depth_trunc; NaN invalid) by ballot and popcount; (2) one workgroup scans the block counts in place (exclusive) and writes
 // offsets and counts; (3) every block recomputes its ballot and writes its valid pixels at block offset + rank: row-major order, image
@@ -100,10 +109,107 @@ __global__ __launch_bounds__(SP_BLOCK) void k_render_keys(const float* __restric
     }
 }
 
+// the half-width of a footprint in pixels: anything that is not >= 0 (a negative or NaN radius, inf / inf) is a point
+__device__ __forceinline__ double half_width(double h, double cap) { return !(h >= 0.0) ? 0.0 : (h < cap ? h : cap); }
+
+// grid ceil(Q / 256), block SP_BLOCK.  k_render_keys in mode 1 with a rectangle of pixels per kept (point, view): at most 33 x 33
+__global__ __launch_bounds__(SP_BLOCK) void k_splat_keys(const float* __restrict__ points, const float* __restrict__ radii, int Q,
+                                                         const SpView* __restrict__ views, int V, int H, int W, float z_min, int max_px,
+                                                         unsigned long long* __restrict__ keys) {
+    __shared__ float sp[3 * SP_BLOCK];
+    __shared__ float sr[SP_BLOCK];
+    __shared__ ViewD vd[VIEW_CHUNK];
+    const int tid = threadIdx.x;
+    // (from the end of the set, as k_render_keys: equal float32 z goes to the highest index)
+    const long long first = (long long)(gridDim.x - 1 - blockIdx.x) * SP_BLOCK;
+    const int n = (int)((long long)Q - first < SP_BLOCK ? (long long)Q - first : SP_BLOCK);
+    for (int j = tid; j < 3 * n; j += SP_BLOCK) sp[j] = points[3 * first + j];
+    if (tid < n) sr[tid] = radii[first + tid];
+    const size_t HW = (size_t)H * W;
+    const double Wd = (double)W, Hd = (double)H, zmin = (double)z_min, cap = (double)max_px;
+    const uint32_t id1 = (uint32_t)(first + tid) + 1u;
+    for (int v0 = 0; v0 < V; v0 += VIEW_CHUNK) {
+        const int nv = V - v0 < VIEW_CHUNK ? V - v0 : VIEW_CHUNK;
+        __syncthreads();
+        if (tid < nv) view_setup(views[v0 + tid], vd[tid]);
+        __syncthreads();
+        if (tid >= n) continue;
+        const double px = (double)sp[3 * tid], py = (double)sp[3 * tid + 1], pz = (double)sp[3 * tid + 2], rad = (double)sr[tid];
+        for (int k = 0; k < nv; ++k) {
+            const ViewD& w = vd[k];
+            double x = px, y = py, z = pz;
+            if (!w.ident) {
+                const double d0 = px - w.t[0], d1 = py - w.t[1], d2 = pz - w.t[2];
+                x = (w.Rt[0] * d0 + w.Rt[1] * d1) + w.Rt[2] * d2;
+                y = (w.Rt[3] * d0 + w.Rt[4] * d1) + w.Rt[5] * d2;
+                z = (w.Rt[6] * d0 + w.Rt[7] * d1) + w.Rt[8] * d2;
+            }
+            const double u = (x * w.fx) / z + w.cx;
+            const double v = (y * w.fy) / z + w.cy;
+            if (!(z > zmin) || !(fabs(u) < HUGE_VAL) || !(fabs(v) < HUGE_VAL)) continue;
+            const double ru = half_width((rad * w.fx) / z, cap), rv = half_width((rad * w.fy) / z, cap);
+            const double ul = u - ru, uh = u + ru, vl = v - rv, vh = v + rv;
+            if (!(uh >= 0.0 && ul < Wd && vh >= 0.0 && vl < Hd)) continue;
+            // clamped in float64, then converted: 0 <= c0 <= c1 <= W - 1 and 0 <= r0 <= r1 <= H - 1
+            const int c0 = (int)fmax(floor(ul), 0.0), c1 = (int)fmin(floor(uh), Wd - 1.0);
+            const int r0 = (int)fmax(floor(vl), 0.0), r1 = (int)fmin(floor(vh), Hd - 1.0);
+            const unsigned long long key = ((unsigned long long)(~__float_as_uint((float)z)) << 32) | (unsigned long long)id1;
+            unsigned long long* view_keys = keys + (size_t)(v0 + k) * HW;
+            for (int r = r0; r <= r1; ++r) {
+                unsigned long long* row = view_keys + (size_t)r * W;
+                for (int c = c0; c <= c1; ++c) {
+                    if (__hip_atomic_load(row + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= key) continue;
+                    atomicMax(row + c, key);
+                }
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ uint8_t colour_u8(float c) {
     const double p = (double)c * 255.0;                    // exact: 24 + 8 significant bits
     if (!(p > 0.0)) return 0;                              // NaN, zero, negative
     return p >= 255.0 ? (uint8_t)255 : (uint8_t)(int)p;
+}
+
+constexpr int METRIC_PIX = 4;                              // pixels per thread of k_image_metrics
+
+// grid (ceil(H W / 1024), V), block SP_BLOCK: n, sum |a - b| and sum (a - b)^2 over the counted pixels of one view, three channels each.
+// A thread's 4 pixels give at most 4 x 3 x 255^2 < 2^20, a workgroup's 256 threads < 2^28: 32-bit sums until the one 64-bit atomic
+__global__ __launch_bounds__(SP_BLOCK) void k_image_metrics(const uint8_t* __restrict__ rendered, const float* __restrict__ target,
+                                                            const int32_t* __restrict__ index, int HW, unsigned long long* __restrict__ out) {
+    __shared__ uint32_t part[SP_WAVES][3];
+    const int view = blockIdx.y, tid = threadIdx.x;
+    const size_t base = (size_t)view * HW;
+    uint32_t s[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < METRIC_PIX; ++j) {
+        const long long p = ((long long)blockIdx.x * METRIC_PIX + j) * SP_BLOCK + tid;
+        if (p >= HW || index[base + p] < 0) continue;
+        s[0] += 1u;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int a = (int)rendered[3 * (base + p) + ch];
+            const int b = (int)colour_u8(target[(3 * (size_t)view + ch) * HW + p]);
+            const int d = a > b ? a - b : b - a;
+            s[1] += (uint32_t)d;
+            s[2] += (uint32_t)(d * d);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) s[q] += (uint32_t)__shfl_xor((int)s[q], off, 64);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) part[tid >> 6][q] = s[q];
+    }
+    __syncthreads();
+    if (tid < 3) {
+        const uint32_t sum = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+        if (sum) atomicAdd(out + 3 * (size_t)view + tid, (unsigned long long)sum);
+    }
 }
 
 // grid ceil(V H W / 256), block SP_BLOCK
@@ -242,6 +348,41 @@ int sp_render_views(const float* points, const float* colours, long long Q, cons
                            (int)n_pix, mode, image, depth, index);
         SP_CHECK_LAUNCH();
     }
+    return 0;
+}
+
+int sp_render_splats(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, float z_min,
+                     const float* radii, int max_px, unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream) {
+    if (!points || !views || !keys || !radii || (image && !colours)) return SP_EINVAL;
+    if (Q <= 0 || V <= 0 || H <= 0 || W <= 0 || !(z_min >= 0.f) || max_px < 0 || max_px > 16) return SP_EINVAL;
+    const long long HW = (long long)H * W;
+    if (Q > 0x7ffffffeLL || V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long n_pix = (long long)V * HW;
+    hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)n_pix, s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_splat_keys, dim3((unsigned)((Q + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, points, radii, (int)Q, views, V, H,
+                       W, z_min, max_px, keys);
+    SP_CHECK_LAUNCH();
+    if (image || depth || index) {
+        hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((n_pix + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, keys, colours,
+                           (int)n_pix, 1, image, depth, index);
+        SP_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int sp_image_metrics(const uint8_t* rendered, const float* target, const int32_t* index, int V, int H, int W, long long* out, void* stream) {
+    if (!rendered || !target || !index || !out || V <= 0 || H <= 0 || W <= 0) return SP_EINVAL;
+    const long long HW = (long long)H * W;
+    if (V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(long long) * 3 * (size_t)V, s);
+    if (e != hipSuccess) return (int)e;
+    const long long per_block = (long long)METRIC_PIX * SP_BLOCK;
+    hipLaunchKernelGGL(k_image_metrics, dim3((unsigned)((HW + per_block - 1) / per_block), (unsigned)V), dim3(SP_BLOCK), 0, s, rendered, target,
+                       index, (int)HW, reinterpret_cast<unsigned long long*>(out));
+    SP_CHECK_LAUNCH();
     return 0;
 }
 

@@ -7,6 +7,9 @@
 ``sequence_map``      the map of a ``run_sequence(..., keep_keyframes=True)`` result, aligned against ground-truth poses when given.
 ``render_map``        the map seen from V cameras (image, depth buffer, winning point per pixel), ONE ``sp_render_views`` launch.
 ``score_map``         the map's depth buffer in the ground-truth views against ground-truth depth: ``sp_depth_metrics`` and the coverage.
+``point_radii``       the size of the source pixels every map point stands for: the footprints that ``render_map`` / ``score_map`` /
+                      ``score_map_images`` splat through the depth buffer (``sp_render_splats``), so a sparse map has no holes.
+``score_map_images``  the map's rendered views against real images: PSNR, L1 and coverage from ``sp_image_metrics``' integer sums.
 ``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``."""
 from __future__ import annotations
 
@@ -114,11 +117,44 @@ def _view_cameras(Ks, poses, what):
     return Ks, poses
 
 
-def render_map(world, Ks, poses, size, depth_buffer=True):
+def point_radii(world, result, footprint=1.0):
+    """The footprint of every map point in world units, for ``render_map`` / ``score_map`` / ``score_map_images`` (``radii=``): a point
+    stands for ``footprint`` source pixels of its keyframe, so its half side is ``radius_i = footprint / (2 fx_k) * a_k . (p_i - c_k)``
+    with ``k = world['kf_index'][i]`` and ``c_k``, ``a_k`` the centre and the optical axis (third rotation column) of keyframe k's pose
+    in the map's frame: the archive pose of ``result`` (what ``run_sequence(..., keep_keyframes=True)`` returned), moved by
+    ``pose_utils.apply_scale`` when ``world`` carries ``align``.  With an alignment ``a . (p - c) = s z_cam``: the radius scales with the
+    map.  ``stride`` of ``sequence_map`` counts points along TABLE order (segment after segment, row-major within one), not along both
+    image axes, so the footprint that closes a stride-4 map is the caller's choice (2 if the points were spread evenly, up to 4 along
+    a row).  Returns (Q,) float32 on the device; a handful of torch ops, no host read."""
+    archive = result['kf_archive']
+    ids = world['ids']
+    if any(archive[i]['kf'] is None for i in ids):
+        raise ValueError("point_radii: the result holds no keyframes (run with keep_keyframes=True)")
+    if not float(footprint) >= 0.0:
+        raise ValueError(f"point_radii: footprint {footprint}")
+    points = world['points']
+    _lib.require_device(points, world['kf_index'])
+    a = world.get('align')
+    poses = []
+    for i in ids:
+        T = archive[i]['pose'].detach().to(points.device)
+        if a is not None:
+            T = pose_utils.apply_scale(T, dict(s=a['s'][0], rot=a['rot'][0], trans_scaled=a['trans_scaled'][0], rot_reanchor=a['rot_reanchor'][0]))
+        poses.append(T.double())
+    poses = torch.stack(poses)                                                           # (n,4,4) float64
+    fx = torch.stack([archive[i]['kf'].K.detach().reshape(-1)[0].to(points.device) for i in ids]).double()
+    k = world['kf_index'].long()
+    depth = ((points.double() - poses[:, :3, 3][k]) * poses[:, :3, 2][k]).sum(dim=1)
+    return ((float(footprint) / (2.0 * fx))[k] * depth).float()
+
+
+def render_map(world, Ks, poses, size, depth_buffer=True, radii=None, max_px=8):
     """The map seen from V cameras in ONE ``sp_render_views`` launch (``tool.viz.render_views``): ``world`` is what ``keyframe_points`` or
     ``sequence_map`` returned (its ``points`` and ``colours``), ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world in the map's
     frame, ``size`` = (H, W).  ``depth_buffer=True``: the nearest point in front of the camera wins a pixel; False: the reference's
-    ``render_pcd`` (the highest index wins, nothing is tested against z).
+    ``render_pcd`` (the highest index wins, nothing is tested against z).  ``radii`` ((Q,) float32, ``point_radii``): every point is a
+    square footprint of that half side, at most ``max_px`` pixels to either side (ONE ``sp_render_splats`` launch): a map sparser than
+    the view leaves no holes and the nearer surface hides the farther one.
     Returns dict(image (V,H,W,3) uint8, depth (V,H,W) float32 -- 0 where nothing landed --, index (V,H,W) int32 -- the winning row of
     ``world['points']``, -1 where nothing landed).  Per-pixel keyframe and segment maps follow from it:
     ``torch.where(index >= 0, world['kf_index'][index.clamp(min=0).long()], -1)``, and the same with ``world['seg_ids']``.
@@ -126,10 +162,30 @@ def render_map(world, Ks, poses, size, depth_buffer=True):
     from ..tool import viz
     Ks, poses = _view_cameras(Ks, poses, "render_map")
     H, W = size
-    return viz.render_views(world['points'], world['colours'], Ks, poses, H, W, depth_buffer=depth_buffer)
+    return viz.render_views(world['points'], world['colours'], Ks, poses, H, W, depth_buffer=depth_buffer, radii=radii, max_px=max_px)
 
 
-def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size=None):
+def score_map_images(world, images, Ks, poses, radii=None, max_px=8):
+    """The map's rendered views against real images: ``images`` (V,3,H,W) float32 in 0..1, ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4)
+    camera-to-world in the map's frame; ``radii`` / ``max_px`` as in ``render_map``.  One render launch (depth buffer) plus ONE
+    ``sp_image_metrics`` launch; only pixels something landed on are compared, at 8 bits per channel.
+    Returns dict(sums (V,3) int64 -- n, sum |a - b|, sum (a - b)^2 over the compared pixels' three channels --, psnr (V,) float64 =
+    10 log10(255^2 3n / sum d^2) (NaN for n = 0, inf for identical pixels), l1 (V,) float64 in 0..255 = sum |a - b| / 3n (NaN for
+    n = 0), coverage (V,) float64 = n / (H W)).  No synchronisation."""
+    from ..tool import viz
+    Ks, poses = _view_cameras(Ks, poses, "score_map_images")
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[0] != poses.shape[0] or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError(f"score_map_images: images must be float32 (V,3,H,W) for {poses.shape[0]} views, got "
+                         f"{tuple(images.shape) if torch.is_tensor(images) else type(images).__name__}")
+    H, W = int(images.shape[2]), int(images.shape[3])
+    _lib.require_device(images, world['points'])
+    out = viz.render_views(world['points'], world['colours'], Ks, poses, H, W, depth_buffer=True, depth=False, radii=radii, max_px=max_px)
+    sums = viz.image_metrics(out['image'], images, out['index'])
+    n3, s1, s2 = 3.0 * sums[:, 0].double(), sums[:, 1].double(), sums[:, 2].double()
+    return dict(sums=sums, psnr=10.0 * torch.log10(255.0 ** 2 * n3 / s2), l1=s1 / n3, coverage=sums[:, 0].double() / float(H * W))
+
+
+def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size=None, radii=None, max_px=8):
     """The map against ground-truth depth images: its depth buffer is rendered into each of the V ground-truth views (``render_map``'s
     launch, depth only) and scored where it landed.  ``gt_depths`` (V,H,W) float32, ``Ks`` (V,3,3) or (3,3), ``gt_poses`` (V,4,4)
     camera-to-world; the map should already be in the ground truth's frame, as ``sequence_map(gt_poses=...)`` delivers it.
@@ -137,6 +193,7 @@ def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size
     Returns dict(metrics (V,12) float64 on the device, columns: the names of its columns (``depth_completion.void``: n, rmse, mae, absrel
     in mm, inv_rmse, inv_mae, inv_absrel in 1/km, delta105, delta110, delta1, delta2, delta3), coverage (V,) float64 = scored pixels /
     pixels with ``min_depth <= gt <= max_depth`` (NaN for a view without any)).  ``size``: an (H, W) the depths must have, if given.
+    ``radii`` / ``max_px``: the footprints of ``render_map``, so that a sparse map is scored on every pixel its surfaces cover.
     No synchronisation."""
     from ..depth_completion import void
     from ..tool import viz
@@ -150,7 +207,8 @@ def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size
     if size is not None and tuple(int(s) for s in size) != (H, W):
         raise ValueError(f"score_map: size {tuple(size)} against ground-truth depths of {H}x{W}")
     _lib.require_device(gt_depths, world['points'])
-    depth = viz.render_views(world['points'], None, Ks, gt_poses, H, W, depth_buffer=True, image=False, index=False)['depth']
+    depth = viz.render_views(world['points'], None, Ks, gt_poses, H, W, depth_buffer=True, image=False, index=False, radii=radii,
+                             max_px=max_px)['depth']
     in_range = (gt_depths >= min_depth) & (gt_depths <= max_depth)
     scored = in_range & (depth > 0)
     metrics = void.depth_metrics(depth, gt_depths, scored)

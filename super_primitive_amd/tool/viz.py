@@ -6,7 +6,9 @@ matplotlib is imported):
 ``depth_image_lift``   ``tool/viz.py:30-51``: a depth image lifted into a coloured point cloud (Open3D's ``create_from_depth_image`` with
                        ``depth_scale=1, depth_trunc=100, stride=1``, then ``transform(T)``).  Returns tensors, not an Open3D object.
 ``lift_depth_images``  the batched lift without a synchronisation.
-``render_views``       the call under ``render_pcd`` and ``odometery.results.render_map``: V posed views of one point set per launch.
+``render_views``       the call under ``render_pcd`` and ``odometery.results.render_map``: V posed views of one point set per launch;
+                       with ``radii`` every point is a square footprint (``sp_render_splats``): no holes where the map is sparser than the view.
+``image_metrics``      rendered views against real images: exact integer sums per view (``sp_image_metrics``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
 from __future__ import annotations
@@ -57,12 +59,15 @@ def _size(H, W):
     return H, W
 
 
-def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_MIN, image=True, depth=True, index=True):
+def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_MIN, image=True, depth=True, index=True, radii=None,
+                 max_px=8):
     """ONE ``sp_render_views`` launch (include/sp_hip.h has the arithmetic): ``points`` (Q,3) float32 in the world, ``colours`` (Q,3)
     float32 in 0..1 (None allowed without ``image``), ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world.  Returns the requested
     of ``image`` (V,H,W,3) uint8, ``depth`` (V,H,W) float32 (0 where nothing landed) and ``index`` (V,H,W) int32 (-1 there) as a dict.
-    No synchronisation."""
-    _on_device(points, colours, Ks, poses)
+    ``radii`` (Q,) float32 in world units: ONE ``sp_render_splats`` launch instead -- every point covers the pixels its square footprint
+    of that half side touches, at most ``max_px`` (0 .. 16) pixels to either side, through the depth buffer (``depth_buffer`` must be
+    true).  No synchronisation."""
+    _on_device(points, colours, Ks, poses, radii)
     H, W = _size(H, W)
     if poses.dim() != 3:
         raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
@@ -77,6 +82,13 @@ def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_M
     views = torch.cat((_cameras(Ks, V, "Ks"), _poses(poses, V, "poses")), dim=1).contiguous()         # V x SpView
     if not float(z_min) >= 0.0:
         raise ValueError(f"z_min {z_min}")
+    rad = None
+    if radii is not None:
+        if not depth_buffer:
+            raise ValueError("render_views: radii need depth_buffer=True (footprints go through the depth buffer)")
+        rad = _f32(radii, (Q,), "radii")
+        if int(max_px) != max_px or not 0 <= int(max_px) <= 16:
+            raise ValueError(f"render_views: max_px {max_px} (0 .. 16)")
     if Q > 2 ** 31 - 2 or V > 65535 or V * H * W >= 2 ** 31:
         raise ValueError(f"render_views: {Q} points, {V} views of {H}x{W} are beyond the kernel's limits")
     lib = _lib.load()
@@ -89,9 +101,35 @@ def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_M
         out['depth'] = torch.empty(V, H, W, dtype=torch.float32, device=dev)
     if index:
         out['index'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    if rad is not None:
+        _lib.check(lib.sp_render_splats(_lib.ptr(pts), _lib.ptr(cols), Q, _lib.ptr(views), V, H, W, float(z_min), _lib.ptr(rad), int(max_px),
+                                        _lib.ptr(keys), _lib.ptr(out.get('image')), _lib.ptr(out.get('depth')), _lib.ptr(out.get('index')),
+                                        _lib.stream_ptr()), "sp_render_splats")
+        return out
     _lib.check(lib.sp_render_views(_lib.ptr(pts), _lib.ptr(cols), Q, _lib.ptr(views), V, H, W, 1 if depth_buffer else 0, float(z_min),
                                    _lib.ptr(keys), _lib.ptr(out.get('image')), _lib.ptr(out.get('depth')), _lib.ptr(out.get('index')),
                                    _lib.stream_ptr()), "sp_render_views")
+    return out
+
+
+def image_metrics(rendered, target, index):
+    """ONE ``sp_image_metrics`` launch: ``rendered`` (V,H,W,3) uint8 and ``index`` (V,H,W) int32 as ``render_views`` returns them,
+    ``target`` (V,3,H,W) float32 in 0..1 (the project's planar layout), converted to 0 .. 255 by the renderer's own rule.  Returns (V,3)
+    int64 on the device: per view n, sum |a - b| and sum (a - b)^2 over the pixels with ``index >= 0`` and their three channels -- exact
+    integers.  No synchronisation."""
+    _on_device(rendered, target, index)
+    if rendered.dtype != torch.uint8 or rendered.dim() != 4 or rendered.shape[3] != 3 or 0 in rendered.shape:
+        raise ValueError(f"rendered must be uint8 (V,H,W,3), got {rendered.dtype} {tuple(rendered.shape)}")
+    V, H, W = (int(s) for s in rendered.shape[:3])
+    if index.dtype != torch.int32 or tuple(index.shape) != (V, H, W):
+        raise ValueError(f"index must be int32 {(V, H, W)}, got {index.dtype} {tuple(index.shape)}")
+    tgt = _f32(target, (V, 3, H, W), "target")
+    if V > 65535 or V * H * W >= 2 ** 31:
+        raise ValueError(f"image_metrics: {V} views of {H}x{W} are beyond the kernel's limits")
+    lib = _lib.load()
+    img, idx = rendered.contiguous(), index.contiguous()
+    out = torch.empty(V, 3, dtype=torch.int64, device=img.device)
+    _lib.check(lib.sp_image_metrics(_lib.ptr(img), _lib.ptr(tgt), _lib.ptr(idx), V, H, W, _lib.ptr(out), _lib.stream_ptr()), "sp_image_metrics")
     return out
 
 
