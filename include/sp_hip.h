@@ -1188,6 +1188,23 @@ typedef struct SpMapKeyframe {
 int sp_map_points(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int stride, const SpTrajAlign* align, int n_align, float* points,
                   float* colours, int32_t* kf_index, int32_t* seg_ids, long long total_rows, void* stream);
 
+/* sp_keyframe_depths: what each of n_kf keyframes of ONE size claims to see -- its own depth image and segment map, straight from its
+ * table (the renderer cannot deliver them: x fx / z + cx does not give back the integer column exactly, and the truncation can land one
+ * pixel to the left).
+ *     kfs   : the records of an sp_map_points call with stride 1 (first_block = the prefix sum of ceil(P_k / 256), total_blocks their
+ *             sum); image, pose, align and out_offset are not read.  Every record must carry the call's H and W (the caller's check:
+ *             the records live on the device); a point whose pixel lies outside H x W is skipped, never written
+ *     keys  : n_kf H W uint64 of scratch, zeroed by the call
+ *     depth : (n_kf,H,W) float32;  seg : (n_kf,H,W) int32, may be NULL
+ * Table point i of keyframe k lies on the pixel (row, col) of decode_pix(pix[i]) (col = bits 0..15, row = bits 16..30) and has the
+ * float32 depth z = exp(baseL[i] + (kld[n] - kp_L[n])), n its segment -- sp_map_points' own depth, bit for bit (one device function).
+ * A point whose z is not a finite float > 0 (NaN, underflow to 0, overflow to inf) is skipped.  The smallest z wins the pixel, equal z
+ * goes to the HIGHEST table index (sp_render_views mode 1's key: ~bits(z) << 32 | (i + 1)).  depth = the winner's z, or exactly 0 where
+ * no point lies; seg = the winner's segment, or -1.  Integer atomic maxima: two runs give the same bits.
+ * Null kfs / keys / depth, n_kf outside 1 .. 65535, total_blocks < 1, H or W <= 0: SP_EINVAL.  n_kf H W >= 2^31: SP_ELIMIT. */
+int sp_keyframe_depths(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int H, int W, unsigned long long* keys, float* depth,
+                       int32_t* seg, void* stream);
+
 /* ----------------------------------------------------------------------------------------------------
  * Map views (sp_views.hip): a point set rendered into camera views, and depth images lifted into a point cloud.  Both run on the
  * caller's stream without a synchronisation; argument checks come before any device work.
@@ -1235,6 +1252,30 @@ int sp_render_views(const float* points, const float* colours, long long Q, cons
  * SP_EINVAL.  Q > 2^31 - 2, V > 65535, V H W >= 2^31: SP_ELIMIT. */
 int sp_render_splats(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, float z_min,
                      const float* radii, int max_px, unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream);
+
+/* sp_map_consistency: every point of a map tested against V depth images -- the other keyframes' own (sp_keyframe_depths), or ground
+ * truth -- in ONE launch: does the surface a view claims at the point's pixel agree with the point, does the view look straight
+ * through it (a free-space violation), or is the point hidden (no evidence either way)?
+ *     points : (Q,3) float32 in the frame the view poses live in;  owner : (Q,) int32 or NULL
+ *     views  : V records on the device (as sp_render_views);  view_owner : (V,) int32 or NULL
+ *     depth  : (V,H,W) float32
+ *     counts : (Q,3) int32, WRITTEN FOR EVERY ROW by the call: the number of views in which the point agrees / is in front / is behind
+ * In float64 from the float32 inputs, every operation rounded on its own (no fma, no reciprocal).  Per pair (point i, view j):
+ *   - u, v, z exactly as sp_render_views forms them (the same device function; an exact identity pose leaves the point untouched);
+ *   - the pair is SKIPPED if owner and view_owner are both given and owner[i] == view_owner[j] >= 0 (a point is not tested against the
+ *     keyframe it came from);
+ *   - it is UNSEEN unless 0 <= u < W, 0 <= v < H and z > z_min (NaN and +-inf fail);
+ *   - (r, c) = (trunc v, trunc u), zf = float64(float32(z)); the window is the pixels (r + dr, c + dc), |dr|, |dc| <= window, clipped to
+ *     the image; a pixel with depth D is VALID iff 0 < D < inf (NaN is not), and then b = float64(tol) D;
+ *   - no valid pixel in the window: unseen;
+ *   - the pair AGREES if any valid pixel has |zf - D| <= b;
+ *   - otherwise it is IN FRONT if every valid pixel has zf < D - b;
+ *   - otherwise it is BEHIND: behind every surface, or between surfaces without agreeing with any -- neither is evidence against it.
+ * The unseen (and skipped) views of a point are V minus its three counts.  Integer counts: two runs give the same bits.
+ * Null points / views / depth / counts, Q, V, H or W <= 0, tol negative, NaN or >= 1, window outside 0 .. 2, z_min negative or NaN:
+ * SP_EINVAL.  Q > 2^31 - 2, V > 65535, V H W >= 2^31: SP_ELIMIT.  Invalid beats too large. */
+int sp_map_consistency(const float* points, const int32_t* owner, long long Q, const SpView* views, const int32_t* view_owner, int V,
+                       const float* depth, int H, int W, float tol, int window, float z_min, int32_t* counts, void* stream);
 
 /* sp_image_metrics: rendered views against real images, in ONE launch.
  *     rendered : (V,H,W,3) uint8 (sp_render_views' / sp_render_splats' image);  index : (V,H,W) int32 (their index)

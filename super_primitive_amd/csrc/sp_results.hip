@@ -11,6 +11,10 @@
 // sp_map_points.  One thread per output row; a workgroup belongs to ONE keyframe, found by a binary search of blockIdx.x in the records'
 // first_block (uniform: scalar loads).  Its pose -- composed with the alignment in float64 where there is one -- goes through LDS as 12
 // floats; the (row, 3) outputs are staged in LDS and written as runs of consecutive floats.
+//
+// sp_keyframe_depths.  What each keyframe claims to see, straight from its table (the renderer's x fx / z + cx does not give back the
+// integer column exactly): sp_map_points' walk at stride 1, the depth by the same device function, the pixel from decode_pix, the
+// nearest point of a pixel by a 64-bit atomicMax; a second pass decodes depth and segment.  Integer maxima: two runs give the same bits.
 #include <math.h>
 #include "sp_device.h"
 
@@ -209,6 +213,19 @@ __global__ __launch_bounds__(SP_BLOCK) void k_traj_align(const float* __restrict
     if (tid == 0) { rec.ate_scaled = sqrt(sq[0] / nd); rec.ate = sqrt(sq[1] / nd); }
 }
 
+// the segment of table point i: the last one whose offset is at or before it
+__device__ __forceinline__ int map_point_segment(const SpMapKeyframe& kf, int i) {
+    int s0 = 0, s1 = kf.N;
+    while (s1 - s0 > 1) { const int mid = (s0 + s1) >> 1; if (kf.seg_off[mid] <= i) s0 = mid; else s1 = mid; }
+    while (s0 + 1 < kf.N && kf.seg_off[s0 + 1] <= i) ++s0;              // (empty segments share an offset with their successor)
+    return s0;
+}
+
+// the camera-frame depth of table point i of segment n: one function for sp_map_points and sp_keyframe_depths
+__device__ __forceinline__ float map_point_depth(const SpMapKeyframe& kf, int i, int n) {
+    return expf(kf.baseL[i] + (kf.kld[n] - kf.kp_L[n]));
+}
+
 // grid total_blocks, block SP_BLOCK
 __global__ __launch_bounds__(SP_BLOCK) void k_map_points(const SpMapKeyframe* __restrict__ kfs, int n_kf, int stride,
                                                          const SpTrajAlign* __restrict__ align, int n_align, float* __restrict__ points,
@@ -252,13 +269,10 @@ __global__ __launch_bounds__(SP_BLOCK) void k_map_points(const SpMapKeyframe* __
     __syncthreads();
     if (tid < n_rows) {
         const int i = (int)(local0 + tid) * stride;        // table point (< P: the row is below Q)
-        int s0 = 0, s1 = kf.N;
-        while (s1 - s0 > 1) { const int mid = (s0 + s1) >> 1; if (kf.seg_off[mid] <= i) s0 = mid; else s1 = mid; }
-        while (s0 + 1 < kf.N && kf.seg_off[s0 + 1] <= i) ++s0;          // (empty segments share an offset with their successor)
-        const int n = s0;
+        const int n = map_point_segment(kf, i);
         float col, row; bool src_ok;
         decode_pix(kf.pix[i], col, row, src_ok);
-        const float d = expf(kf.baseL[i] + (kf.kld[n] - kf.kp_L[n]));
+        const float d = map_point_depth(kf, i, n);
         Cam Ks;
         load_cam(kf.K, Ks);
         float x, y;
@@ -280,6 +294,41 @@ __global__ __launch_bounds__(SP_BLOCK) void k_map_points(const SpMapKeyframe* __
         points[3 * row0 + j] = stage[0][j];
         colours[3 * row0 + j] = stage[1][j];
     }
+}
+
+// grid total_blocks, block SP_BLOCK: sp_map_points' walk at stride 1; the nearest point of a pixel by one 64-bit atomicMax on
+// ~bits(z) << 32 | (i + 1) -- sp_render_views mode 1's key: the smallest z wins, equal z goes to the highest table index
+__global__ __launch_bounds__(SP_BLOCK) void k_keyframe_depth_keys(const SpMapKeyframe* __restrict__ kfs, int n_kf, int H, int W,
+                                                                  unsigned long long* __restrict__ keys) {
+    const int tid = threadIdx.x, block = blockIdx.x;
+    int lo = 0, hi = n_kf;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (kfs[mid].first_block <= block) lo = mid; else hi = mid; }
+    const SpMapKeyframe kf = kfs[lo];
+    const long long at = (long long)(block - kf.first_block) * SP_BLOCK + tid;
+    if (at < 0 || at >= kf.P) return;
+    const int i = (int)at;
+    const int n = map_point_segment(kf, i);
+    float col, row; bool src_ok;
+    decode_pix(kf.pix[i], col, row, src_ok);
+    const float z = map_point_depth(kf, i, n);
+    if (!(z > 0.f && z < HUGE_VALF)) return;               // NaN, 0 (underflow), inf: no surface
+    const int r = (int)row, c = (int)col;
+    if (r >= H || c >= W) return;                          // (a table of another size: never written beyond the image)
+    const unsigned long long key = ((unsigned long long)(~__float_as_uint(z)) << 32) | (unsigned long long)((uint32_t)i + 1u);
+    unsigned long long* slot = keys + ((size_t)lo * H + r) * W + c;
+    if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= key) return;
+    atomicMax(slot, key);
+}
+
+// grid ceil(n_kf H W / 256), block SP_BLOCK
+__global__ __launch_bounds__(SP_BLOCK) void k_keyframe_depth_resolve(const unsigned long long* __restrict__ keys,
+                                                                     const SpMapKeyframe* __restrict__ kfs, int HW, int n_pix,
+                                                                     float* __restrict__ depth, int32_t* __restrict__ seg) {
+    const long long at = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (at >= n_pix) return;
+    const unsigned long long k = keys[at];
+    depth[at] = k ? __uint_as_float(~(uint32_t)(k >> 32)) : 0.f;
+    if (seg) seg[at] = k ? map_point_segment(kfs[at / HW], (int)((uint32_t)(k & 0xffffffffull) - 1u)) : -1;
 }
 
 }  // namespace
@@ -304,6 +353,23 @@ int sp_map_points(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int stri
     if (total_rows < 1 || total_rows > (long long)total_blocks * SP_BLOCK) return SP_EINVAL;
     hipLaunchKernelGGL(k_map_points, dim3(total_blocks), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), kfs, n_kf, stride, align,
                        n_align, points, colours, kf_index, seg_ids, total_rows);
+    SP_CHECK_LAUNCH();
+    return 0;
+}
+
+int sp_keyframe_depths(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int H, int W, unsigned long long* keys, float* depth,
+                       int32_t* seg, void* stream) {
+    if (!kfs || !keys || !depth || n_kf <= 0 || n_kf > 65535 || total_blocks < 1 || H <= 0 || W <= 0) return SP_EINVAL;
+    const long long HW = (long long)H * W;
+    if (HW >= 0x80000000LL || (long long)n_kf * HW >= 0x80000000LL) return SP_ELIMIT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long n_pix = (long long)n_kf * HW;
+    hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)n_pix, s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(k_keyframe_depth_keys, dim3(total_blocks), dim3(SP_BLOCK), 0, s, kfs, n_kf, H, W, keys);
+    SP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_keyframe_depth_resolve, dim3((unsigned)((n_pix + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, keys, kfs, (int)HW,
+                       (int)n_pix, depth, seg);
     SP_CHECK_LAUNCH();
     return 0;
 }

@@ -21,6 +21,12 @@
 // meets [u - ru, u + ru] x [v - rv, v + rv], clipped to the image (bounds clamped in float64 before the conversion: at most 33 x 33),
 // with the same load-then-atomicMax per pixel and the point's one key: a splat is flat.  The resolve pass is k_render_resolve, unchanged.
 //
+// sp_map_consistency.  The same projection (camera_point / pixel_of below, one pair of functions for every kernel here), no keys: one
+// lane per point, 32 views per workgroup in LDS, and per seen (point, view) a gather of the (2 window + 1)^2 depths around its pixel
+// from the V depth images, which every workgroup re-reads (they stay in L2 / the Infinity Cache).  Each pair is one of agree, in front,
+// behind or unseen; three integer counters per point in registers, stored plainly when V fits one chunk, else added by integer
+// atomicAdd onto zeroed counts.  Integers: two runs give the same bits.
+//
 // sp_image_metrics.  One launch, grid (ceil(H W / 1024), V): per counted pixel (index >= 0) and channel d = |rendered - u8(target)| with
 // the resolve pass's conversion; n, sum d and sum d^2 as 32-bit integers per thread, wave (lane swaps) and workgroup (LDS), then one 64-bit
 // integer atomicAdd per workgroup and quantity.  Integers: exact, whatever the order.
@@ -65,6 +71,24 @@ __device__ __forceinline__ void view_setup(const SpView& v, ViewD& o) {
     o.pad_ = 0;
 }
 
+// The projection of one point into one view, shared by every kernel of this file (the contract of sp_render_views in include/sp_hip.h):
+// p_c = R^T (p - t), the three-term sums as (a + b) + c; an exact identity pose leaves the point untouched.
+__device__ __forceinline__ void camera_point(const ViewD& w, double px, double py, double pz, double& x, double& y, double& z) {
+    x = px; y = py; z = pz;
+    if (!w.ident) {
+        const double d0 = px - w.t[0], d1 = py - w.t[1], d2 = pz - w.t[2];
+        x = (w.Rt[0] * d0 + w.Rt[1] * d1) + w.Rt[2] * d2;
+        y = (w.Rt[3] * d0 + w.Rt[4] * d1) + w.Rt[5] * d2;
+        z = (w.Rt[6] * d0 + w.Rt[7] * d1) + w.Rt[8] * d2;
+    }
+}
+
+// u = x fx / z + cx, v = y fy / z + cy: two IEEE divisions
+__device__ __forceinline__ void pixel_of(const ViewD& w, double x, double y, double z, double& u, double& v) {
+    u = (x * w.fx) / z + w.cx;
+    v = (y * w.fy) / z + w.cy;
+}
+
 // grid ceil(Q / 256), block SP_BLOCK
 __global__ __launch_bounds__(SP_BLOCK) void k_render_keys(const float* __restrict__ points, int Q, const SpView* __restrict__ views, int V,
                                                           int H, int W, int mode, float z_min, unsigned long long* __restrict__ keys) {
@@ -88,15 +112,9 @@ __global__ __launch_bounds__(SP_BLOCK) void k_render_keys(const float* __restric
         const double px = (double)sp[3 * tid], py = (double)sp[3 * tid + 1], pz = (double)sp[3 * tid + 2];
         for (int k = 0; k < nv; ++k) {
             const ViewD& w = vd[k];
-            double x = px, y = py, z = pz;
-            if (!w.ident) {
-                const double d0 = px - w.t[0], d1 = py - w.t[1], d2 = pz - w.t[2];
-                x = (w.Rt[0] * d0 + w.Rt[1] * d1) + w.Rt[2] * d2;
-                y = (w.Rt[3] * d0 + w.Rt[4] * d1) + w.Rt[5] * d2;
-                z = (w.Rt[6] * d0 + w.Rt[7] * d1) + w.Rt[8] * d2;
-            }
-            const double u = (x * w.fx) / z + w.cx;
-            const double v = (y * w.fy) / z + w.cy;
+            double x, y, z, u, v;
+            camera_point(w, px, py, pz, x, y, z);
+            pixel_of(w, x, y, z, u, v);
             if (!(u >= 0.0 && u < Wd && v >= 0.0 && v < Hd)) continue;
             if (mode == 1 && !(z > zmin)) continue;
             const uint32_t zb = __float_as_uint((float)z);
@@ -137,15 +155,9 @@ __global__ __launch_bounds__(SP_BLOCK) void k_splat_keys(const float* __restrict
         const double px = (double)sp[3 * tid], py = (double)sp[3 * tid + 1], pz = (double)sp[3 * tid + 2], rad = (double)sr[tid];
         for (int k = 0; k < nv; ++k) {
             const ViewD& w = vd[k];
-            double x = px, y = py, z = pz;
-            if (!w.ident) {
-                const double d0 = px - w.t[0], d1 = py - w.t[1], d2 = pz - w.t[2];
-                x = (w.Rt[0] * d0 + w.Rt[1] * d1) + w.Rt[2] * d2;
-                y = (w.Rt[3] * d0 + w.Rt[4] * d1) + w.Rt[5] * d2;
-                z = (w.Rt[6] * d0 + w.Rt[7] * d1) + w.Rt[8] * d2;
-            }
-            const double u = (x * w.fx) / z + w.cx;
-            const double v = (y * w.fy) / z + w.cy;
+            double x, y, z, u, v;
+            camera_point(w, px, py, pz, x, y, z);
+            pixel_of(w, x, y, z, u, v);
             if (!(z > zmin) || !(fabs(u) < HUGE_VAL) || !(fabs(v) < HUGE_VAL)) continue;
             const double ru = half_width((rad * w.fx) / z, cap), rv = half_width((rad * w.fy) / z, cap);
             const double ul = u - ru, uh = u + ru, vl = v - rv, vh = v + rv;
@@ -163,6 +175,82 @@ __global__ __launch_bounds__(SP_BLOCK) void k_splat_keys(const float* __restrict
                 }
             }
         }
+    }
+}
+
+constexpr int CONS_CHUNK = 32;                            // views per workgroup of k_map_consistency
+
+// grid (ceil(Q / 256), ceil(V / CONS_CHUNK)), block SP_BLOCK: one lane per point, the chunk's views in LDS (wave-uniform broadcasts),
+// the three counters in registers.  The test on z comes before the two divisions, so a point behind the camera pays for neither.
+// The window is a template argument (0, 1, 2): its 1, 9 or 25 loads are unrolled and in flight together.
+// add = 0: the one chunk stores its counters; add = 1: counts is zeroed and every chunk adds what it found (integers: any order).
+template <int WIN>
+__global__ __launch_bounds__(SP_BLOCK) void k_map_consistency(const float* __restrict__ points, const int32_t* __restrict__ owner, int Q,
+                                                              const SpView* __restrict__ views, const int32_t* __restrict__ view_owner, int V,
+                                                              const float* __restrict__ depth, int H, int W, float tol, float z_min,
+                                                              int32_t* __restrict__ counts, int add) {
+    __shared__ ViewD vd[CONS_CHUNK];
+    __shared__ int32_t vown[CONS_CHUNK];
+    const int tid = threadIdx.x;
+    const int v0 = blockIdx.y * CONS_CHUNK;
+    const int nv = V - v0 < CONS_CHUNK ? V - v0 : CONS_CHUNK;
+    if (tid < nv) {
+        view_setup(views[v0 + tid], vd[tid]);
+        vown[tid] = view_owner ? view_owner[v0 + tid] : -1;
+    }
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * SP_BLOCK + tid;
+    if (i >= Q) return;
+    const double px = (double)points[3 * i], py = (double)points[3 * i + 1], pz = (double)points[3 * i + 2];
+    const int own = owner ? owner[i] : -1;
+    const size_t HW = (size_t)H * W;
+    const double Wd = (double)W, Hd = (double)H, zmin = (double)z_min, tol64 = (double)tol;
+    int n_agree = 0, n_front = 0, n_behind = 0;
+    for (int k = 0; k < nv; ++k) {
+        if (own >= 0 && own == vown[k]) continue;          // the point's own keyframe: skipped
+        const ViewD& w = vd[k];
+        double x, y, z, u, v;
+        camera_point(w, px, py, pz, x, y, z);
+        if (!(z > zmin)) continue;
+        pixel_of(w, x, y, z, u, v);
+        if (!(u >= 0.0 && u < Wd && v >= 0.0 && v < Hd)) continue;
+        const int r = (int)v, c = (int)u;                  // 0 <= r < H, 0 <= c < W
+        const double zf = (double)(float)z;
+        const float* img = depth + (size_t)(v0 + k) * HW;
+        // the window's depths first (all loads in flight together; a pixel outside the image reads as 0: no surface), then the rule
+        constexpr int SIDE = 2 * WIN + 1;
+        float d[SIDE * SIDE];
+#pragma unroll
+        for (int dr = -WIN; dr <= WIN; ++dr) {
+            const int rr = r + dr, rc = rr < 0 ? 0 : (rr > H - 1 ? H - 1 : rr);
+#pragma unroll
+            for (int dc = -WIN; dc <= WIN; ++dc) {
+                const int cc = c + dc, ccl = cc < 0 ? 0 : (cc > W - 1 ? W - 1 : cc);
+                const float val = img[(size_t)rc * W + ccl];
+                d[(dr + WIN) * SIDE + dc + WIN] = rr == rc && cc == ccl ? val : 0.f;
+            }
+        }
+        bool any = false, agree = false, all_front = true;
+#pragma unroll
+        for (int j = 0; j < SIDE * SIDE; ++j) {
+            const bool valid = d[j] > 0.f && d[j] < HUGE_VALF;             // 0, negative, NaN, inf: no surface (float32 to float64 is exact)
+            const double D = (double)d[j], b = tol64 * D;
+            any = any || valid;
+            agree = agree || (valid && fabs(zf - D) <= b);
+            all_front = all_front && (!valid || zf < D - b);
+        }
+        if (!any) continue;
+        if (agree) ++n_agree;
+        else if (all_front) ++n_front;
+        else ++n_behind;
+    }
+    int32_t* out = counts + 3 * i;
+    if (!add) {
+        out[0] = n_agree; out[1] = n_front; out[2] = n_behind;
+    } else {
+        if (n_agree) atomicAdd(out, n_agree);
+        if (n_front) atomicAdd(out + 1, n_front);
+        if (n_behind) atomicAdd(out + 2, n_behind);
     }
 }
 
@@ -369,6 +457,30 @@ int sp_render_splats(const float* points, const float* colours, long long Q, con
                            (int)n_pix, 1, image, depth, index);
         SP_CHECK_LAUNCH();
     }
+    return 0;
+}
+
+int sp_map_consistency(const float* points, const int32_t* owner, long long Q, const SpView* views, const int32_t* view_owner, int V,
+                       const float* depth, int H, int W, float tol, int window, float z_min, int32_t* counts, void* stream) {
+    if (!points || !views || !depth || !counts || Q <= 0 || V <= 0 || H <= 0 || W <= 0) return SP_EINVAL;
+    if (!(tol >= 0.f && tol < 1.f) || window < 0 || window > 2 || !(z_min >= 0.f)) return SP_EINVAL;
+    const long long HW = (long long)H * W;
+    if (Q > 0x7ffffffeLL || V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int chunks = (V + CONS_CHUNK - 1) / CONS_CHUNK;
+    if (chunks > 1) {
+        hipError_t e = hipMemsetAsync(counts, 0, sizeof(int32_t) * 3 * (size_t)Q, s);
+        if (e != hipSuccess) return (int)e;
+    }
+    const dim3 grid((unsigned)((Q + SP_BLOCK - 1) / SP_BLOCK), (unsigned)chunks);
+    const int add = chunks > 1 ? 1 : 0;
+    if (window == 0)
+        hipLaunchKernelGGL(k_map_consistency<0>, grid, dim3(SP_BLOCK), 0, s, points, owner, (int)Q, views, view_owner, V, depth, H, W, tol, z_min, counts, add);
+    else if (window == 1)
+        hipLaunchKernelGGL(k_map_consistency<1>, grid, dim3(SP_BLOCK), 0, s, points, owner, (int)Q, views, view_owner, V, depth, H, W, tol, z_min, counts, add);
+    else
+        hipLaunchKernelGGL(k_map_consistency<2>, grid, dim3(SP_BLOCK), 0, s, points, owner, (int)Q, views, view_owner, V, depth, H, W, tol, z_min, counts, add);
+    SP_CHECK_LAUNCH();
     return 0;
 }
 

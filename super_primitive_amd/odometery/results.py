@@ -10,6 +10,10 @@
 ``point_radii``       the size of the source pixels every map point stands for: the footprints that ``render_map`` / ``score_map`` /
                       ``score_map_images`` splat through the depth buffer (``sp_render_splats``), so a sparse map has no holes.
 ``score_map_images``  the map's rendered views against real images: PSNR, L1 and coverage from ``sp_image_metrics``' integer sums.
+``map_consistency``   every map point against V depth images -- the other keyframes' own, or ground truth: per point the views it
+                      agrees with, floats in front of, is hidden behind (ONE ``sp_map_consistency`` launch); ``sequence_consistency`` is
+                      the self-check of a sequence's map without ground truth, ``segment_consistency`` the verdict per (keyframe,
+                      segment), ``filter_map`` the map with the unconfirmed points taken out.
 ``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``."""
 from __future__ import annotations
 
@@ -117,6 +121,21 @@ def _view_cameras(Ks, poses, what):
     return Ks, poses
 
 
+def _map_poses(world, result):
+    """(n,4,4) float64: the archive poses of ``world['ids']`` in the map's frame -- moved by ``pose_utils.apply_scale`` when ``world``
+    carries ``align``."""
+    archive = result['kf_archive']
+    dev = world['points'].device
+    a = world.get('align')
+    poses = []
+    for i in world['ids']:
+        T = archive[i]['pose'].detach().to(dev)
+        if a is not None:
+            T = pose_utils.apply_scale(T, dict(s=a['s'][0], rot=a['rot'][0], trans_scaled=a['trans_scaled'][0], rot_reanchor=a['rot_reanchor'][0]))
+        poses.append(T.double())
+    return torch.stack(poses)
+
+
 def point_radii(world, result, footprint=1.0):
     """The footprint of every map point in world units, for ``render_map`` / ``score_map`` / ``score_map_images`` (``radii=``): a point
     stands for ``footprint`` source pixels of its keyframe, so its half side is ``radius_i = footprint / (2 fx_k) * a_k . (p_i - c_k)``
@@ -134,14 +153,7 @@ def point_radii(world, result, footprint=1.0):
         raise ValueError(f"point_radii: footprint {footprint}")
     points = world['points']
     _lib.require_device(points, world['kf_index'])
-    a = world.get('align')
-    poses = []
-    for i in ids:
-        T = archive[i]['pose'].detach().to(points.device)
-        if a is not None:
-            T = pose_utils.apply_scale(T, dict(s=a['s'][0], rot=a['rot'][0], trans_scaled=a['trans_scaled'][0], rot_reanchor=a['rot_reanchor'][0]))
-        poses.append(T.double())
-    poses = torch.stack(poses)                                                           # (n,4,4) float64
+    poses = _map_poses(world, result)
     fx = torch.stack([archive[i]['kf'].K.detach().reshape(-1)[0].to(points.device) for i in ids]).double()
     k = world['kf_index'].long()
     depth = ((points.double() - poses[:, :3, 3][k]) * poses[:, :3, 2][k]).sum(dim=1)
@@ -214,6 +226,120 @@ def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size
     metrics = void.depth_metrics(depth, gt_depths, scored)
     coverage = scored.sum(dim=(1, 2)).double() / in_range.sum(dim=(1, 2)).double()
     return dict(metrics=metrics, columns=void._COLUMNS, coverage=coverage)
+
+
+def map_consistency(world, depths, Ks, poses, view_kf=None, tol=0.05, window=1):
+    """Every map point against V depth images in ONE ``sp_map_consistency`` launch (``tool.viz.map_consistency``; include/sp_hip.h has
+    the rule): ``depths`` (V,H,W) float32 is what each view claims to see -- the keyframes' own depth images (``sequence_consistency``)
+    or ground truth, for per-point accuracy --, ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world in the map's frame.
+    ``view_kf`` ((V,) integers or None): the keyframe (row of ``world['kf_index']``) each view belongs to; a point is never tested
+    against a view of its own keyframe.  Returns dict(counts (Q,3) int32 -- the views a point agrees with / floats in front of (the view
+    looks straight through it) / is hidden behind --, agree, in_front, behind: its columns, seen (Q,) int32: their sum).
+    No synchronisation."""
+    from ..tool import viz
+    Ks, poses = _view_cameras(Ks, poses, "map_consistency")
+    V = int(poses.shape[0])
+    if not torch.is_tensor(depths) or depths.dim() != 3 or depths.shape[0] != V or depths.dtype != torch.float32:
+        raise ValueError(f"map_consistency: depths must be float32 (V,H,W) for {V} views, got "
+                         f"{tuple(depths.shape) if torch.is_tensor(depths) else type(depths).__name__}")
+    owner = view_owner = None
+    if view_kf is not None:
+        view_owner = torch.as_tensor(view_kf)
+        if view_owner.is_floating_point() or tuple(view_owner.shape) != (V,):
+            raise ValueError(f"map_consistency: view_kf must be {V} integers, got {view_owner.dtype} {tuple(view_owner.shape)}")
+        view_owner = view_owner.to(device=world['points'].device, dtype=torch.int32)
+        owner = world['kf_index']
+    counts = viz.map_consistency(world['points'], Ks, poses, depths, owner=owner, view_owner=view_owner, tol=tol, window=window)
+    return dict(counts=counts, agree=counts[:, 0], in_front=counts[:, 1], behind=counts[:, 2], seen=counts.sum(dim=1, dtype=torch.int32))
+
+
+def sequence_consistency(world, result, tol=0.05, window=1):
+    """The map's self-check, without ground truth: every point of ``world`` (``sequence_map`` of ``result``) against the depth image each
+    OTHER keyframe claims to see (``tool.viz.keyframe_depths`` on the archive, in ``world['ids']`` order; multiplied by the alignment
+    scale when ``world`` carries ``align``: the world points are scaled, the tables are not), through the archive poses in the map's
+    frame (``point_radii``'s).  Returns ``map_consistency``'s dict plus ``depths`` (n,H,W) float32 and ``seg_maps`` (n,H,W) int32.
+    No synchronisation beyond the keyframes' table builds."""
+    from ..tool import viz
+    archive = result['kf_archive']
+    ids = world['ids']
+    if any(archive[i]['kf'] is None for i in ids):
+        raise ValueError("sequence_consistency: the result holds no keyframes (run with keep_keyframes=True)")
+    _lib.require_device(world['points'], world['kf_index'])
+    own = viz.keyframe_depths([archive[i]['kf'] for i in ids], [archive[i]['kld'] for i in ids])
+    depths = own['depth']
+    a = world.get('align')
+    if a is not None:
+        depths = depths * a['s'][0].to(torch.float32)
+    dev = depths.device
+    Ks = torch.stack([archive[i]['kf'].K.detach().reshape(3, 3).to(dev) for i in ids])
+    out = map_consistency(world, depths, Ks, _map_poses(world, result), view_kf=torch.arange(len(ids), dtype=torch.int32), tol=tol,
+                          window=window)
+    out.update(depths=depths, seg_maps=own['seg'])
+    return out
+
+
+def segment_consistency(world, consistency, n_segments=None):
+    """A verdict per (keyframe, segment) from ``map_consistency``'s per-point counts: (n_kf, N_max, 5) int64 on the points' device --
+    points; points seen at least once; points with ``agree >= 1``; points with ``in_front >= 1`` and ``agree == 0`` (some view looks
+    through them and none confirms them); the sum of ``agree``.  Integer sums per integer key (one ``index_add_``): exact, whatever the
+    order.  ``n_segments``: N_max; without it the largest segment id is read from the device (the one host read).  Points whose
+    segment id lies outside 0 .. N_max - 1 are counted nowhere."""
+    kf, seg = world['kf_index'].long(), world['seg_ids'].long()
+    counts = consistency['counts']
+    if counts.dim() != 2 or counts.shape != (kf.shape[0], 3) or seg.shape != kf.shape:
+        raise ValueError(f"segment_consistency: counts {tuple(counts.shape)} for {kf.shape[0]} points")
+    n_kf = len(world['offsets']) - 1
+    n_max = int(n_segments) if n_segments is not None else int(seg.max()) + 1
+    if n_max < 1:
+        raise ValueError(f"segment_consistency: {n_max} segments")
+    agree, front = counts[:, 0].long(), counts[:, 1].long()
+    seen = counts.sum(dim=1) > 0
+    values = torch.stack((torch.ones_like(agree), seen.long(), (agree >= 1).long(), ((front >= 1) & (agree == 0)).long(), agree), dim=1)
+    inside = (seg >= 0) & (seg < n_max) & (kf >= 0) & (kf < n_kf)
+    key = torch.where(inside, kf * n_max + seg, torch.full_like(kf, n_kf * n_max))     # (one row beyond the table takes the rest)
+    out = torch.zeros(n_kf * n_max + 1, 5, dtype=torch.int64, device=kf.device).index_add_(0, key, values)
+    return out[:-1].reshape(n_kf, n_max, 5)
+
+
+_PER_POINT = ('points', 'colours', 'kf_index', 'seg_ids')
+
+
+def filter_map(world, consistency, min_agree=1, max_in_front=None):
+    """The map a user would export: the rows of ``world`` with ``agree >= min_agree`` -- and ``in_front <= max_in_front`` if given --,
+    in their order.  Returns a new dict: ``points``, ``colours``, ``kf_index``, ``seg_ids`` compacted, ``offsets`` recomputed (host
+    integers, as ``keyframe_points`` returns them), ``kept`` (int64, on the device: the surviving rows of ``world``); every other entry
+    (``ids``, ``align``, the ATE fields) is carried over.  ``world`` must hold all four per-point tensors, of one length, and ``offsets``
+    ending at that length (``ValueError`` otherwise).  Sizing the output takes ONE host read -- the new offsets, n_kf + 1 integers;
+    everything before it is asynchronous, and the compaction after it (a scatter of the row numbers to their ranks) reads nothing
+    back."""
+    counts = consistency['counts']
+    missing = [k for k in _PER_POINT + ('offsets',) if world.get(k) is None]
+    if missing or not all(torch.is_tensor(world[k]) for k in _PER_POINT):
+        raise ValueError(f"filter_map: world needs tensors {_PER_POINT} and offsets; missing or not tensors: "
+                         f"{missing or [k for k in _PER_POINT if not torch.is_tensor(world[k])]}")
+    Q = int(world['points'].shape[0])
+    if any(int(world[k].shape[0]) != Q for k in _PER_POINT) or int(np.asarray(world['offsets'])[-1]) != Q:
+        raise ValueError(f"filter_map: {[(k, int(world[k].shape[0])) for k in _PER_POINT]} rows and offsets ending at "
+                         f"{int(np.asarray(world['offsets'])[-1])} for {Q} points")
+    if counts.dim() != 2 or tuple(counts.shape) != (Q, 3):
+        raise ValueError(f"filter_map: counts {tuple(counts.shape)} for {Q} points")
+    keep = counts[:, 0] >= int(min_agree)
+    if max_in_front is not None:
+        keep = keep & (counts[:, 1] <= int(max_in_front))
+    dev = counts.device
+    rank = torch.cumsum(keep.long(), dim=0)                                            # inclusive: rank[i] - 1 is row i's new place
+    before = torch.cat((rank.new_zeros(1), rank))                                      # before[o] = kept rows among the first o
+    old = torch.as_tensor(np.asarray(world['offsets'], dtype=np.int64)).to(dev)
+    offsets = before[old].cpu().numpy()                                                # the one host read
+    total = int(offsets[-1])
+    dest = torch.where(keep, rank - 1, torch.full_like(rank, total))                   # (dropped rows all go to one spare slot)
+    kept = torch.empty(total + 1, dtype=torch.int64, device=dev).scatter_(0, dest, torch.arange(Q, dtype=torch.int64, device=dev))[:total]
+    out = {k: v for k, v in world.items() if k not in _PER_POINT and k != 'offsets'}
+    for k in _PER_POINT:
+        out[k] = world[k][kept]
+    out['offsets'] = offsets
+    out['kept'] = kept
+    return out
 
 
 def write_tum_format(timestamps, pred_poses, gt_poses, out_dir):

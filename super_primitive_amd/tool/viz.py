@@ -9,6 +9,8 @@ matplotlib is imported):
 ``render_views``       the call under ``render_pcd`` and ``odometery.results.render_map``: V posed views of one point set per launch;
                        with ``radii`` every point is a square footprint (``sp_render_splats``): no holes where the map is sparser than the view.
 ``image_metrics``      rendered views against real images: exact integer sums per view (``sp_image_metrics``).
+``keyframe_depths``    what each keyframe claims to see: its own depth image and segment map, from its table (``sp_keyframe_depths``).
+``map_consistency``    every point against V depth images: agree / in front / behind counts per point (``sp_map_consistency``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
 from __future__ import annotations
@@ -201,3 +203,89 @@ def depth_image_lift(depth, K, image=None, mask=None, T=None, depth_trunc=100.0)
             raise ValueError(f"mask has {mask.numel()} entries for {n} valid pixels")
         res = {k: (None if v is None else v[mask]) for k, v in res.items()}
     return res
+
+
+_BLOCK = 256          # table points per workgroup of sp_keyframe_depths (sp_map_points' walk at stride 1)
+
+
+def keyframe_depths(kfs, klds):
+    """ONE ``sp_keyframe_depths`` call (include/sp_hip.h): what each keyframe claims to see, straight from its segment table -- per
+    pixel the nearest table point's depth ``exp(baseL + (kld[n] - kp_L[n]))`` (the depth ``odometery.results.keyframe_points`` gives
+    the same point, bit for bit) and its segment.  ``kfs``: keyframes with segments, all of ONE size; ``klds``: their keypoint
+    log-depths.  Returns ``dict(depth (n,H,W) float32 -- 0 where no point lies --, seg (n,H,W) int32 -- -1 there)``.  Raises
+    ``ValueError`` for keyframes of differing sizes or without segment pixels.  No synchronisation beyond the table builds."""
+    from ..segment_table import table_of
+    n = len(kfs)
+    if n == 0 or len(klds) != n:
+        raise ValueError(f"keyframe_depths: {n} keyframes, {len(klds)} log-depth vectors")
+    _on_device(*klds)
+    tabs, kld_cs = [], []
+    for k, (kf, kld) in enumerate(zip(kfs, klds)):
+        tab = table_of(kf)                                 # (raises ValueError for a keyframe without segment pixels)
+        if tabs and (tab.H, tab.W) != (tabs[0].H, tabs[0].W):
+            raise ValueError(f"keyframe_depths: keyframe {k} is {tab.H}x{tab.W}, keyframe 0 is {tabs[0].H}x{tabs[0].W}")
+        kld_c = kld.detach().contiguous().float()
+        if kld_c.numel() != tab.N:
+            raise ValueError(f"keyframe_depths: keyframe {k}: {kld_c.numel()} log-depths for {tab.N} segments")
+        tabs.append(tab)
+        kld_cs.append(kld_c)
+    size = (tabs[0].H, tabs[0].W)
+    recs = (_lib.SpMapKeyframe * n)()
+    block = 0
+    for r, tab, kld_c in zip(recs, tabs, kld_cs):          # (image, pose, align and out_offset are not read)
+        r.pix, r.baseL, r.seg_off, r.kp_L, r.kld = tab.pix.data_ptr(), tab.baseL.data_ptr(), tab.seg_off.data_ptr(), tab.kp_L.data_ptr(), kld_c.data_ptr()
+        r.N, r.P, r.H, r.W = tab.N, tab.P, tab.H, tab.W
+        r.out_offset, r.align, r.first_block = 0, -1, block
+        block += (tab.P + _BLOCK - 1) // _BLOCK
+    H, W = size
+    if n > 65535 or n * H * W >= 2 ** 31:
+        raise ValueError(f"keyframe_depths: {n} keyframes of {H}x{W} are beyond the kernel's limits")
+    lib = _lib.load()
+    dev = kld_cs[0].device
+    recs_d = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(dev)
+    keys = torch.empty(n * H * W, dtype=torch.int64, device=dev)
+    out = dict(depth=torch.empty(n, H, W, dtype=torch.float32, device=dev), seg=torch.empty(n, H, W, dtype=torch.int32, device=dev))
+    _lib.check(lib.sp_keyframe_depths(_lib.ptr(recs_d), n, block, H, W, _lib.ptr(keys), _lib.ptr(out['depth']), _lib.ptr(out['seg']),
+                                      _lib.stream_ptr()), "sp_keyframe_depths")
+    return out
+
+
+def _i32(t, n, what):
+    if t.dtype != torch.int32 or tuple(t.shape) != (n,):
+        raise ValueError(f"{what} must be int32 ({n},), got {t.dtype} {tuple(t.shape)}")
+    return t.detach().contiguous()
+
+
+def map_consistency(points, Ks, poses, depths, owner=None, view_owner=None, tol=0.05, window=1, z_min=Z_MIN):
+    """ONE ``sp_map_consistency`` launch (include/sp_hip.h has the rule): ``points`` (Q,3) float32 in the frame of ``poses`` (V,4,4)
+    camera-to-world, ``Ks`` (V,3,3) or (3,3), ``depths`` (V,H,W) float32 -- what each view claims to see (``keyframe_depths``) or ground
+    truth.  A point agrees with a view when a valid depth within ``window`` (0 .. 2) pixels of its projection is within ``tol``
+    (relative, 0 <= tol < 1) of its own; it is in front when it is nearer than all of them, else behind.  ``owner`` (Q,) and
+    ``view_owner`` (V,) int32: a point is not tested against a view of its own owner (>= 0).  Returns (Q,3) int32 on the device: per
+    point the number of views it agrees with, is in front of, is behind.  No synchronisation."""
+    _on_device(points, Ks, poses, depths, owner, view_owner)
+    if poses.dim() != 3:
+        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
+    V = int(poses.shape[0])
+    pts = _f32(points, (None, 3), "points")
+    Q = int(pts.shape[0])
+    if Q == 0 or V == 0:
+        raise ValueError(f"map_consistency: {Q} points against {V} views")
+    d = _f32(depths, (V, None, None), "depths")
+    H, W = _size(d.shape[1], d.shape[2])
+    views = torch.cat((_cameras(Ks, V, "Ks"), _poses(poses, V, "poses")), dim=1).contiguous()         # V x SpView
+    own = None if owner is None else _i32(owner, Q, "owner")
+    vown = None if view_owner is None else _i32(view_owner, V, "view_owner")
+    if not 0.0 <= float(tol) < 1.0:
+        raise ValueError(f"map_consistency: tol {tol} (0 <= tol < 1)")
+    if int(window) != window or not 0 <= int(window) <= 2:
+        raise ValueError(f"map_consistency: window {window} (0 .. 2)")
+    if not float(z_min) >= 0.0:
+        raise ValueError(f"z_min {z_min}")
+    if Q > 2 ** 31 - 2 or V > 65535 or V * H * W >= 2 ** 31:
+        raise ValueError(f"map_consistency: {Q} points, {V} views of {H}x{W} are beyond the kernel's limits")
+    lib = _lib.load()
+    counts = torch.empty(Q, 3, dtype=torch.int32, device=pts.device)
+    _lib.check(lib.sp_map_consistency(_lib.ptr(pts), _lib.ptr(own), Q, _lib.ptr(views), _lib.ptr(vown), V, _lib.ptr(d), H, W, float(tol),
+                                      int(window), float(z_min), _lib.ptr(counts), _lib.stream_ptr()), "sp_map_consistency")
+    return counts
