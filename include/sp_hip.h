@@ -327,6 +327,25 @@ int sp_host_work_list(const long long* pc, const long long* seg_pos, const long 
  * segment record (SP_GNA_SEG_FLOATS): [0..7] as mode 1, [8] H_{a,depth}, [9] H_{b,depth}.  Consumed by sp_window_gn_step.
  * mode 2 takes neither flag; any other value of mode is SP_EINVAL (checked before any device work).
  *
+ * WHAT EVERY RECORD SUMS (tests/cost_pass_ref.py restates one launch in float64 from this paragraph; tests/test_gpu_cost_pass.py holds every
+ * column of every record of every variant to it).  Per table point, with col / row / src_ok from its pixel word:
+ *     d = exp(src4.w + kld[seg] - kp_L[seg])   (depth tables: src4.w * exp(kld[seg] - kp_L[seg]));   p = ((col - cx_s) d / fx_s, (row - cy_s) d / fy_s, d)
+ *     q = R p + t;   zi = 1 / qz where |qz| > 1e-6, else 1e-6;   u = fx_t qx zi + cx_t;   xn = 2 u / (W - 1) - 1;   ix = (xn + 1) (Wl - 1) / 2   (v, yn, iy alike)
+ *     m = src_ok and d > 1e-7 and |xn| <= 0.99 and |yn| <= 0.99 and qz > zmin:  a point whose m is false -- every padding point -- adds ZERO to every column
+ *     I, Ix, Iy per channel: bilinear value and slopes (level pixels) from the four taps at floor(ix), floor(iy);   gain = exp(-(a_t - a_s)), bias = b_t - b_s
+ *     r = I_src - (gain I + bias);   w = 1 / max(|r|, irls_eps);   J = -gain (Ix ax fx_t zi Ahat0 + Iy ay fy_t zi Ahat1),  ax = (Wl - 1) / (W - 1), ay = (Hl - 1) / (H - 1)
+ *     Ahat0 = [1, 0, -ux, -ux qy, qz + ux qx, -qy, ex - ux ez],  Ahat1 = [0, 1, -vy, -(qz + vy qy), vy qx, qx, ey - vy ez],  ux = qx / qz, vy = qy / qz, e = q - t
+ *   over the unknowns [tau(3), phi(3)] of the left perturbation Exp(xi) T and the segment's log-depth (column 6).  Modes 1, 2 sum over channels and points
+ *   m w J_i J_j (H_pp: i <= j < 6, row-major; h_pd: j = 6; D: i = j = 6), m w r J_i (b_p, b_d), m |r| and m; mode 2 the same with j_a = gain I, j_b = -1 for
+ *   [29..45] / segment [8], [9] ([30] = sum w j_a j_b, [33] = sum w r j_b).  Mode 0 sums, with s = sign(r) and g = -gain (ax fx_t zi sum s Ix, ay fy_t zi
+ *   sum s Iy, .) whose third component is -(g_x qx + g_y qy) / qz:  [0] m |r|, [1..3] g, [4..12] g p^T (row-major), [14] gain sum s I, [15] -sum s; segment: g . (q - t).
+ *   WHICH POINTS:  span record s sums the points of the chunks spans[s].first .. + spans[s].n.  Segment record 4 q + w of chunk q sums the points
+ *   chunk.start + 256 j + 64 w + lane (j < count / 256, lane < 64) -- those wave w handles -- and under SP_COST_WAVE_SPANS record q sums all points of chunk q.
+ *   [8] / [9] of a mode-1 segment record are sum |r| and the valid points of exactly those points.
+ *   UNUSED COLUMNS:  every float of a span record is written, the columns without a meaning as 0 (mode 0: [13]; mode 1: [29..31]; mode 2: [46], [47]).
+ *   Of a segment record modes 1 and 2 write [0..9] and NEVER [10], [11], which keep what the buffer held.  Nothing is written past record n_spans - 1 /
+ *   4 C - 1 (C - 1 under wave spans), nor to the records of a span skipped through `done`; a segment without points has no chunk and no record.
+ *
  * sp_pairs_cost_opt is sp_pairs_cost with three optional arguments; sp_pairs_cost passes NULL for each.
  *   done (n_pairs int32, see sp_pairs_gn_step_conv): workgroups return at once for spans of marked pairs, so that an iteration
  *     costs time only for the pairs still moving.
