@@ -1324,6 +1324,47 @@ int sp_depth_lift_blocks(int B, int H, int W);
 int sp_depth_lift(const float* depth, const float* K, const float* pose, const float* image, int B, int H, int W, float depth_trunc,
                   int32_t* block_counts, float* points, float* colours, int32_t* pixel, int32_t* counts, long long* offsets, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Map fusion (sp_fuse.hip): one averaged point per occupied voxel.  A world map is the concatenation of its keyframes' points, so a
+ * surface seen by ten keyframes is stored ten times; sp_map_fuse replaces the points of one voxel by their mean.  Everything runs on
+ * the caller's stream without a synchronisation; argument checks come before any device work.
+ *     points      : (Q,3) float32;  colours : (Q,3) float32, or NULL together with out_colours
+ *     voxel       : the voxel's side, a finite float32 > 0;  ox, oy, oz : the grid's origin o, finite float32
+ *     scratch     : sp_map_fuse_scratch_units(Q) units of 64 bytes, aligned to 8 bytes, initialised by the call
+ *     out_points, out_colours : (Q,3) float32;  count, first : (Q,) int32 -- CAPACITY buffers (the convention of sp_depth_lift): rows
+ *                   at or beyond n_fused[0] are never written
+ *     label       : (Q,) int32, WRITTEN FOR EVERY ROW;  n_fused : one int64 on the device
+ * The voxel of a point.  In float64 from the float32 inputs, every operation rounded on its own (no fma, no reciprocal).  Per axis a:
+ *     q = (p_a - o_a) / voxel,  g = floor(q).
+ * A point is DROPPED (label = -1, it contributes nowhere) unless all three q are finite and all three g lie in -2^20 .. 2^20 - 1; the
+ * range is tested on the float64 value, before any conversion to an integer.  The voxel's key is
+ *     key = (gx + 2^20) << 42 | (gy + 2^20) << 21 | (gz + 2^20)                              (63 bits).
+ * The sub-voxel position of a kept point is f = q - g (float64), s_a = min(trunc(f * 65536), 65535), an integer in 0 .. 65535 (the
+ * minimum acts only for -2^-54 < q < 0, where q + 1 rounds to 1).  Its colour per channel is the renderer's 8-bit value: trunc of the
+ * exact float64 product c * 255, clamped to 0 .. 255, NaN gives 0 (sp_render_views' device function).
+ * Per occupied voxel, over its kept points: n (their number), S_a = sum s_a, C_ch = sum colour8, i0 = their lowest input row.  These
+ * are integers: the sums are exact in any order, two runs give the same bits.
+ * Output order: voxels in ascending order of i0 -- fused row j is the voxel with the j-th smallest first row.  No sort is involved,
+ * and input rows grouped by keyframe give fused rows grouped by keyframe, every voxel under the keyframe that saw it first.
+ * Fused row j:  first[j] = i0, count[j] = n, and in float64, each operation rounded on its own, rounded to float32 once at the end:
+ *     m = float64(S_a) / float64(n),  c = (m + 0.5) / 65536,  out_points[j][a] = (float64(g) + c) * voxel + o_a;
+ *     out_colours[j][ch] = float64(C_ch) / (255 * float64(n)).
+ * label[i] = the fused row of point i's voxel (-1 for a dropped point);  n_fused[0] = M, the number of occupied voxels.
+ * The fused position is the mean of the members, each quantised to 1 / 65536 of a voxel and placed at the middle of its step: per
+ * coordinate it differs from the float64 mean of the members' (p_a - o_a) + o_a by less than voxel * 2^-16.
+ * Null points / scratch / out_points / count / first / label / n_fused, colours without out_colours or the reverse, Q <= 0, voxel not
+ * finite or not > 0, a non-finite origin: SP_EINVAL.  Q > 2^28 (SP_MAP_FUSE_MAX_POINTS: the table's slot numbers and the scratch size
+ * in units stay below 2^31; the 64-bit sums hold 2^28 x 65535 with room to spare): SP_ELIMIT.  Invalid beats too large.
+ * sp_map_fuse_scratch_units answers Q <= 0 and Q > 2^28 with the same codes.
+ * The table: open addressing with linear probing over S slots of 64 bytes, S the smallest power of two >= 2 Q (load <= 0.5), 64-bit
+ * keys claimed by compare-and-swap; then Q slot numbers and ceil(Q / 256) block counts.  Five launches after the table's
+ * initialisation (insert, count the first rows per 256-row block, scan, emit, label); no workgroup waits on another and every loop is
+ * bounded. */
+#define SP_MAP_FUSE_MAX_POINTS (1LL << 28)
+int sp_map_fuse_scratch_units(long long Q);
+int sp_map_fuse(const float* points, const float* colours, long long Q, float voxel, float ox, float oy, float oz, void* scratch,
+                float* out_points, float* out_colours, int32_t* count, int32_t* first, int32_t* label, long long* n_fused, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,8 @@ SIGNATURES = {
     "sp_image_metrics": [P, P, P, I, I, I, P, P],
     "sp_depth_lift_blocks": [I, I, I],
     "sp_depth_lift": [P, P, P, P, I, I, I, F, P, P, P, P, P, P, P],
+    "sp_map_fuse_scratch_units": [ctypes.c_longlong],
+    "sp_map_fuse": [P, P, ctypes.c_longlong, F, F, F, F, P, P, P, P, P, P, P, P],
 }
 
 SP_ABI_VERSION = 18
@@ -277,6 +279,7 @@ class SpMapKeyframe(ctypes.Structure):
 
 
 SP_VIEW_FLOATS = 25
+SP_MAP_FUSE_MAX_POINTS = 1 << 28
 
 
 class SpView(ctypes.Structure):

@@ -167,6 +167,14 @@ __device__ __forceinline__ float block_sum_to_thread(float (&acc)[NV], float* ld
     return block_sum_to_thread<NV>(acc, lds, (int)threadIdx.x);
 }
 
+// the 8-bit value of a colour channel, one rule for the renderer (sp_views.hip) and the map fusion (sp_fuse.hip): trunc(c * 255) from
+// the float64 product, clamped to 0 .. 255, NaN -> 0
+__device__ __forceinline__ uint8_t colour_u8(float c) {
+    const double p = (double)c * 255.0;                    // exact: 24 + 8 significant bits
+    if (!(p > 0.0)) return 0;                              // NaN, zero, negative
+    return p >= 255.0 ? (uint8_t)255 : (uint8_t)(int)p;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // XCD-aware tile order: the dispatcher places block b on XCD b % 8 (MI355X_MICROARCH.md, observed, used for
 // speed only).  Give every XCD one contiguous chunk of the tile list so that the tiles of one frame pair --

@@ -254,12 +254,6 @@ __global__ __launch_bounds__(SP_BLOCK) void k_map_consistency(const float* __res
     }
 }
 
-__device__ __forceinline__ uint8_t colour_u8(float c) {
-    const double p = (double)c * 255.0;                    // exact: 24 + 8 significant bits
-    if (!(p > 0.0)) return 0;                              // NaN, zero, negative
-    return p >= 255.0 ? (uint8_t)255 : (uint8_t)(int)p;
-}
-
 constexpr int METRIC_PIX = 4;                              // pixels per thread of k_image_metrics
 
 // grid (ceil(H W / 1024), V), block SP_BLOCK: n, sum |a - b| and sum (a - b)^2 over the counted pixels of one view, three channels each.

@@ -14,7 +14,10 @@
                       agrees with, floats in front of, is hidden behind (ONE ``sp_map_consistency`` launch); ``sequence_consistency`` is
                       the self-check of a sequence's map without ground truth, ``segment_consistency`` the verdict per (keyframe,
                       segment), ``filter_map`` the map with the unconfirmed points taken out.
-``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``."""
+``fuse_map``          the map as a map: one averaged point per occupied voxel (ONE ``sp_map_fuse`` call), a world dict every function
+                      above accepts; ``pool_map`` sums per-input-point integers (consistency counts) per fused point.
+``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``.
+``write_ply``         the map's points and 8-bit colours as a binary PLY file."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -304,6 +307,19 @@ def segment_consistency(world, consistency, n_segments=None):
 _PER_POINT = ('points', 'colours', 'kf_index', 'seg_ids')
 
 
+def _check_world(world, what):
+    """``filter_map``'s conditions on a world dict: the four per-point tensors, of one length, and offsets ending at it."""
+    missing = [k for k in _PER_POINT + ('offsets',) if world.get(k) is None]
+    if missing or not all(torch.is_tensor(world[k]) for k in _PER_POINT):
+        raise ValueError(f"{what}: world needs tensors {_PER_POINT} and offsets; missing or not tensors: "
+                         f"{missing or [k for k in _PER_POINT if not torch.is_tensor(world[k])]}")
+    Q = int(world['points'].shape[0])
+    if any(int(world[k].shape[0]) != Q for k in _PER_POINT) or int(np.asarray(world['offsets'])[-1]) != Q:
+        raise ValueError(f"{what}: {[(k, int(world[k].shape[0])) for k in _PER_POINT]} rows and offsets ending at "
+                         f"{int(np.asarray(world['offsets'])[-1])} for {Q} points")
+    return Q
+
+
 def filter_map(world, consistency, min_agree=1, max_in_front=None):
     """The map a user would export: the rows of ``world`` with ``agree >= min_agree`` -- and ``in_front <= max_in_front`` if given --,
     in their order.  Returns a new dict: ``points``, ``colours``, ``kf_index``, ``seg_ids`` compacted, ``offsets`` recomputed (host
@@ -313,14 +329,7 @@ def filter_map(world, consistency, min_agree=1, max_in_front=None):
     everything before it is asynchronous, and the compaction after it (a scatter of the row numbers to their ranks) reads nothing
     back."""
     counts = consistency['counts']
-    missing = [k for k in _PER_POINT + ('offsets',) if world.get(k) is None]
-    if missing or not all(torch.is_tensor(world[k]) for k in _PER_POINT):
-        raise ValueError(f"filter_map: world needs tensors {_PER_POINT} and offsets; missing or not tensors: "
-                         f"{missing or [k for k in _PER_POINT if not torch.is_tensor(world[k])]}")
-    Q = int(world['points'].shape[0])
-    if any(int(world[k].shape[0]) != Q for k in _PER_POINT) or int(np.asarray(world['offsets'])[-1]) != Q:
-        raise ValueError(f"filter_map: {[(k, int(world[k].shape[0])) for k in _PER_POINT]} rows and offsets ending at "
-                         f"{int(np.asarray(world['offsets'])[-1])} for {Q} points")
+    Q = _check_world(world, "filter_map")
     if counts.dim() != 2 or tuple(counts.shape) != (Q, 3):
         raise ValueError(f"filter_map: counts {tuple(counts.shape)} for {Q} points")
     keep = counts[:, 0] >= int(min_agree)
@@ -340,6 +349,75 @@ def filter_map(world, consistency, min_agree=1, max_in_front=None):
     out['offsets'] = offsets
     out['kept'] = kept
     return out
+
+
+def fuse_map(world, voxel, origin=None):
+    """The map as a map: every keyframe contributes its own copy of each surface it sees, so ``world`` grows with the number of
+    keyframes; here the points of one voxel (side ``voxel``, grid through ``origin``, default 0, 0, 0) become ONE point, their mean
+    position and mean colour (ONE ``sp_map_fuse`` call, ``tool.viz.fuse_points``; include/sp_hip.h has the arithmetic: integer sums,
+    two runs give the same bits).  Fused points come in the order of their first member row, so they stay grouped by keyframe, each
+    under the keyframe that saw its voxel first.  Returns a new world dict: ``points`` (M,3), ``colours`` (M,3), ``kf_index`` and
+    ``seg_ids`` (M,) -- those of the first member --, ``count`` (M,) int32 (members), ``first`` (M,) int32 (the first member's row of
+    ``world``), ``label`` (Q,) int32 (per INPUT row its fused row, -1 for a row that was dropped: a non-finite coordinate, or beyond
+    2^20 voxels from the origin) and ``offsets`` recomputed (host integers); every other entry (``ids``, ``align``, the ATE fields) is
+    carried over.  ``render_map``, ``score_map``, ``score_map_images``, ``map_consistency`` and ``filter_map`` accept the result as it
+    is (``filter_map`` compacts the four per-point tensors; ``count``, ``first`` and ``label`` then still describe the unfiltered
+    fused map).  The footprint of a fused point is its voxel: ``radii = torch.full((M,), voxel / 2)``.  ``world`` is validated as
+    ``filter_map`` does (``ValueError``).  Sizing the output takes ONE host read -- the new offsets, n_kf + 1 integers from
+    ``torch.searchsorted(first, old_offsets)``, the last of which is M."""
+    from ..tool import viz
+    Q = _check_world(world, "fuse_map")
+    if Q == 0:
+        raise ValueError("fuse_map: no points")
+    fused = viz.fuse_points(world['points'], world['colours'], voxel=voxel, origin=origin)
+    dev = fused['first'].device
+    old = torch.as_tensor(np.asarray(world['offsets'], dtype=np.int64)).to(dev)
+    offsets = torch.searchsorted(fused['first'].long(), old).cpu().numpy()             # the one host read (rows beyond M hold 2^31 - 1)
+    M = int(offsets[-1])
+    first = fused['first'][:M]
+    out = {k: v for k, v in world.items() if k not in _PER_POINT and k != 'offsets'}
+    out.update(points=fused['points'][:M], colours=fused['colours'][:M], kf_index=world['kf_index'][first.long()],
+               seg_ids=world['seg_ids'][first.long()], count=fused['count'][:M], first=first, label=fused['label'], offsets=offsets)
+    return out
+
+
+def pool_map(fused, values):
+    """Per-input-row integers summed per fused point: ``fused`` is what ``fuse_map`` returned, ``values`` an integer tensor of shape
+    (Q,) or (Q,k) over the rows of the map that was fused -- ``sequence_consistency(...)['counts']`` gives every fused point the agree /
+    in front / behind counts of all its members.  Returns int64 (M,) or (M,k) on the values' device.  One ``index_add_`` through
+    ``fused['label']``: exact, whatever the order; rows with ``label = -1`` are counted nowhere.  No host read."""
+    label = fused['label']
+    M = int(fused['points'].shape[0])
+    if not torch.is_tensor(values) or values.is_floating_point() or values.is_complex() or values.dim() not in (1, 2) \
+            or values.shape[0] != label.shape[0]:
+        raise ValueError(f"pool_map: values must be integers of shape ({label.shape[0]},) or ({label.shape[0]},k), got "
+                         f"{(values.dtype, tuple(values.shape)) if torch.is_tensor(values) else type(values).__name__}")
+    lab = label.long()
+    key = torch.where(lab >= 0, lab, torch.full_like(lab, M))                          # (one row beyond the map takes the dropped rows)
+    out = torch.zeros((M + 1,) + tuple(values.shape[1:]), dtype=torch.int64, device=values.device).index_add_(0, key, values.long())
+    return out[:M]
+
+
+def write_ply(path, world):
+    """``world['points']`` (M,3) float32 and ``world['colours']`` (M,3) float32 in 0..1 as a binary little-endian PLY file: per vertex
+    ``x y z`` float32 and ``red green blue`` uchar, the colours by the renderer's 8-bit rule (trunc(c * 255) from the float64 product,
+    clamped to 0 .. 255, NaN gives 0).  Device tensors come to the host in one copy of 15 bytes per point; CPU tensors work too.
+    Returns the path."""
+    points, colours = world.get('points'), world.get('colours')
+    if not torch.is_tensor(points) or not torch.is_tensor(colours) or points.dtype != torch.float32 or colours.dtype != torch.float32 \
+            or points.dim() != 2 or points.shape[1] != 3 or tuple(colours.shape) != tuple(points.shape) or points.device != colours.device:
+        raise ValueError("write_ply: world needs float32 points (M,3) and colours (M,3) on one device")
+    M = int(points.shape[0])
+    rgb = torch.nan_to_num(colours.detach().double() * 255.0, nan=0.0).clamp(0.0, 255.0).to(torch.uint8)
+    rows = torch.cat((points.detach().contiguous().view(torch.uint8).reshape(M, 12), rgb), dim=1).cpu().numpy()   # the one copy
+    header = ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {M}\n" + "property float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+    if np.little_endian is False:                                                      # (the float bytes above are the host's)
+        raise ValueError("write_ply: a big-endian host")
+    with open(path, 'wb') as f:
+        f.write(header.encode('ascii'))
+        f.write(rows.tobytes())
+    return path
 
 
 def write_tum_format(timestamps, pred_poses, gt_poses, out_dir):

@@ -11,6 +11,7 @@ matplotlib is imported):
 ``image_metrics``      rendered views against real images: exact integer sums per view (``sp_image_metrics``).
 ``keyframe_depths``    what each keyframe claims to see: its own depth image and segment map, from its table (``sp_keyframe_depths``).
 ``map_consistency``    every point against V depth images: agree / in front / behind counts per point (``sp_map_consistency``).
+``fuse_points``        one averaged point per occupied voxel of a point set (``sp_map_fuse``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
 from __future__ import annotations
@@ -289,3 +290,44 @@ def map_consistency(points, Ks, poses, depths, owner=None, view_owner=None, tol=
     _lib.check(lib.sp_map_consistency(_lib.ptr(pts), _lib.ptr(own), Q, _lib.ptr(views), _lib.ptr(vown), V, _lib.ptr(d), H, W, float(tol),
                                       int(window), float(z_min), _lib.ptr(counts), _lib.stream_ptr()), "sp_map_consistency")
     return counts
+
+
+def fuse_points(points, colours=None, voxel=0.05, origin=None):
+    """ONE ``sp_map_fuse`` call (include/sp_hip.h has the rule): ``points`` (Q,3) float32, ``colours`` (Q,3) float32 or None, ``voxel``
+    the voxel's side (a finite float32 > 0), ``origin`` three finite numbers (default: 0, 0, 0).  The points of one voxel become their
+    mean -- positions quantised to 1/65536 of a voxel, colours to 8 bits, so the sums are integers and two runs give the same bits --;
+    the voxels come in the order of their first input row.  Points with a non-finite coordinate, or beyond 2^20 voxels from the origin,
+    are dropped.  Returns the CAPACITY buffers ``points`` (Q,3), ``colours`` (Q,3) or None, ``count`` (Q,) int32 (members per fused
+    point), ``first`` (Q,) int32 (its lowest input row; pre-filled with 2^31 - 1, so rows beyond ``n`` sort after every real row),
+    ``label`` (Q,) int32 (the fused row of every input row, -1 for a dropped one) and ``n`` (0-dim int64 on the device: the number of
+    fused points; rows from ``n`` on are uninitialised).  No synchronisation."""
+    _on_device(points, colours)
+    pts = _f32(points, (None, 3), "points")
+    Q = int(pts.shape[0])
+    if Q == 0:
+        raise ValueError("fuse_points: no points")
+    cols = None if colours is None else _f32(colours, (Q, 3), "colours")
+    try:
+        vox = float(torch.tensor(float(voxel), dtype=torch.float32))           # the float32 the kernel divides by
+        org = [0.0, 0.0, 0.0] if origin is None else [float(o) for o in torch.as_tensor(origin, dtype=torch.float64).reshape(-1).float().tolist()]
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"fuse_points: voxel {voxel!r}, origin {origin!r}: {e}") from None
+    if not (vox > 0.0 and vox < float("inf")):
+        raise ValueError(f"fuse_points: voxel {voxel} (a finite float32 > 0)")
+    if len(org) != 3 or not all(abs(o) < float("inf") for o in org):
+        raise ValueError(f"fuse_points: origin {origin} (three finite float32 numbers)")
+    if Q > _lib.SP_MAP_FUSE_MAX_POINTS:
+        raise ValueError(f"fuse_points: {Q} points are beyond the kernel's limit of {_lib.SP_MAP_FUSE_MAX_POINTS}")
+    lib = _lib.load()
+    units = lib.sp_map_fuse_scratch_units(Q)
+    if units < 0:
+        raise ValueError(f"fuse_points: {Q} points are beyond the kernel's limits")
+    dev = pts.device
+    scratch = torch.empty(units, 8, dtype=torch.int64, device=dev)
+    out = dict(points=torch.empty(Q, 3, dtype=torch.float32, device=dev), colours=None if cols is None else torch.empty(Q, 3, dtype=torch.float32, device=dev),
+               count=torch.empty(Q, dtype=torch.int32, device=dev), first=torch.full((Q,), 2 ** 31 - 1, dtype=torch.int32, device=dev),
+               label=torch.empty(Q, dtype=torch.int32, device=dev), n=torch.empty((), dtype=torch.int64, device=dev))
+    _lib.check(lib.sp_map_fuse(_lib.ptr(pts), _lib.ptr(cols), Q, vox, org[0], org[1], org[2], _lib.ptr(scratch), _lib.ptr(out['points']),
+                               _lib.ptr(out['colours']), _lib.ptr(out['count']), _lib.ptr(out['first']), _lib.ptr(out['label']), _lib.ptr(out['n']),
+                               _lib.stream_ptr()), "sp_map_fuse")
+    return out
