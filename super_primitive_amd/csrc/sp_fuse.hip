@@ -12,15 +12,16 @@
 //                  atomic decides) and integer atomicAdd into n, S[3], C[3].  Every lane of a wave hits another 64-byte line, the slow
 //                  shape for atomics, so their number is what the call costs: with 16 points per voxel the merge halves the call's
 //                  time, with 64 it takes it to 0.28, and a map without runs pays nothing measurable (profiles/map_fuse_wave_merge_ab.txt)
-//   k_fuse_count   a point is its voxel's representative iff its row is the slot's `first`; per 256-row block their number (ballot)
-//   k_fuse_scan    one workgroup: the exclusive prefix sum of the block counts, in place; the total is n_fused
+//   k_fuse_count   a point is its voxel's representative iff its row is the slot's `first`; per 256-row block their number (block_rank)
+//   k_fuse_scan    one workgroup: the exclusive prefix sum of the block counts, in place (block_count_scan); the total is n_fused
 //   k_fuse_emit    representative i writes fused row rank(i) = block prefix + its place in the block from its slot, and the rank back
 //                  into the slot (over n, which only the representative reads)
 //   k_fuse_label   label[i] = the rank in point i's slot
-// The three-pass shape of sp_depth_lift: no workgroup waits on another, no flags, nothing spins.  Every loop is bounded: a probe visits at
-// most S slots and cannot exhaust them (at most Q < S keys are ever claimed); should it ever, the point is dropped, not looped on.
+// The ordered compaction of sp_depth_lift, from the same pieces (sp_map_device.h): no workgroup waits on another, no flags, nothing
+// spins.  Every loop is bounded: a probe visits at most S slots and cannot exhaust them (at most Q < S keys are ever claimed); should it
+// ever, the point is dropped, not looped on.
 // All sums are integers: any order gives the same bits.
-#include "sp_device.h"
+#include "sp_map_device.h"
 
 #pragma clang fp contract(off)
 
@@ -139,35 +140,15 @@ __global__ __launch_bounds__(SP_BLOCK) void k_fuse_count(const FuseSlot* __restr
     __shared__ int wc[SP_WAVES];
     int32_t slot;
     const bool rep = fuse_is_first(table, slot_of, (long long)blockIdx.x * SP_BLOCK + threadIdx.x, Q, slot);
-    const unsigned long long ballot = __ballot(rep);
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(ballot);
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = (wc[0] + wc[1]) + (wc[2] + wc[3]);
+    const int count = block_rank(rep, wc).count;
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = count;
 }
 
 // one workgroup: bc[n] becomes its exclusive prefix sum, n_fused[0] the total
 __global__ __launch_bounds__(SP_BLOCK) void k_fuse_scan(int32_t* __restrict__ bc, int n, long long* __restrict__ n_fused) {
     __shared__ long long part[SP_BLOCK];
-    const int tid = threadIdx.x;
-    const int per = (n + SP_BLOCK - 1) / SP_BLOCK;
-    const long long j0 = (long long)tid * per;
-    const long long j1 = j0 + per < n ? j0 + per : n;
-    long long s = 0;
-    for (long long j = j0; j < j1; ++j) s += bc[j];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int t = 0; t < SP_BLOCK; ++t) { const long long x = part[t]; part[t] = run; run += x; }
-        n_fused[0] = run;
-    }
-    __syncthreads();
-    long long run = part[tid];
-    for (long long j = j0; j < j1; ++j) {
-        const int c = bc[j];
-        bc[j] = (int32_t)run;
-        run += c;
-    }
+    const long long total = block_count_scan(bc, n, part, [](long long, long long) {});
+    if (threadIdx.x == 0) n_fused[0] = total;
 }
 
 // grid ceil(Q / 256)
@@ -176,16 +157,12 @@ __global__ __launch_bounds__(SP_BLOCK) void k_fuse_emit(FuseSlot* __restrict__ t
                                                         float* __restrict__ out_points, float* __restrict__ out_colours,
                                                         int32_t* __restrict__ count, int32_t* __restrict__ first) {
     __shared__ int wc[SP_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long i = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
     int32_t slot;
     const bool rep = fuse_is_first(table, slot_of, i, Q, slot);
-    const unsigned long long ballot = __ballot(rep);
-    if (lane == 0) wc[wave] = __popcll(ballot);
-    __syncthreads();
+    const int rank = block_rank(rep, wc).rank;
     if (!rep) return;
-    int32_t row = block_offsets[blockIdx.x] + __popcll(ballot & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) row += wc[w];
+    const int32_t row = block_offsets[blockIdx.x] + rank;
     FuseSlot* t = table + slot;
     const unsigned long long key = t->key;
     const int32_t n = t->n;

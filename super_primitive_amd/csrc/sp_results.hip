@@ -8,15 +8,15 @@
 // U diag(1, 1, det(U) det(Vh)) Vh; with the third left vector taken as u1 x u2 this is u1 v1^T + u2 v2^T + det(V) (u1 x u2) v3^T, whatever
 // sign a library would give u3 -- and well defined when the third singular value is exactly 0 (a planar trajectory).
 //
-// sp_map_points.  One thread per output row; a workgroup belongs to ONE keyframe, found by a binary search of blockIdx.x in the records'
-// first_block (uniform: scalar loads).  Its pose -- composed with the alignment in float64 where there is one -- goes through LDS as 12
-// floats; the (row, 3) outputs are staged in LDS and written as runs of consecutive floats.
+// sp_map_points.  One thread per output row; a workgroup belongs to ONE keyframe (keyframe_of_block, sp_map_device.h).  Its pose --
+// composed with the alignment in float64 where there is one -- goes through LDS as 12 floats; the (row, 3) outputs are staged in LDS and
+// written as runs of consecutive floats.
 //
 // sp_keyframe_depths.  What each keyframe claims to see, straight from its table (the renderer's x fx / z + cx does not give back the
 // integer column exactly): sp_map_points' walk at stride 1, the depth by the same device function, the pixel from decode_pix, the
 // nearest point of a pixel by a 64-bit atomicMax; a second pass decodes depth and segment.  Integer maxima: two runs give the same bits.
 #include <math.h>
-#include "sp_device.h"
+#include "sp_map_device.h"
 
 static_assert(sizeof(SpTrajAlign) == 256 && sizeof(SpMapKeyframe) == 96, "result records are part of the ABI");
 
@@ -234,9 +234,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_map_points(const SpMapKeyframe* __
     __shared__ float M[13];                                // R' (9, row major), t' (3), s
     __shared__ float stage[2][3 * SP_BLOCK];
     const int tid = threadIdx.x, block = blockIdx.x;
-    // the keyframe of this workgroup: the last record whose first_block is at or before it
-    int lo = 0, hi = n_kf;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (kfs[mid].first_block <= block) lo = mid; else hi = mid; }
+    const int lo = keyframe_of_block(kfs, n_kf, block);
     const SpMapKeyframe kf = kfs[lo];
     const int Q = (int)(((long long)kf.P + stride - 1) / stride);
     const long long local0 = (long long)(block - kf.first_block) * SP_BLOCK;
@@ -296,13 +294,12 @@ __global__ __launch_bounds__(SP_BLOCK) void k_map_points(const SpMapKeyframe* __
     }
 }
 
-// grid total_blocks, block SP_BLOCK: sp_map_points' walk at stride 1; the nearest point of a pixel by one 64-bit atomicMax on
-// ~bits(z) << 32 | (i + 1) -- sp_render_views mode 1's key: the smallest z wins, equal z goes to the highest table index
+// grid total_blocks, block SP_BLOCK: sp_map_points' walk at stride 1; the nearest point of a pixel by the "nearest" key of
+// sp_map_device.h, sp_render_views mode 1's: the smallest z wins, equal z goes to the highest table index
 __global__ __launch_bounds__(SP_BLOCK) void k_keyframe_depth_keys(const SpMapKeyframe* __restrict__ kfs, int n_kf, int H, int W,
                                                                   unsigned long long* __restrict__ keys) {
     const int tid = threadIdx.x, block = blockIdx.x;
-    int lo = 0, hi = n_kf;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (kfs[mid].first_block <= block) lo = mid; else hi = mid; }
+    const int lo = keyframe_of_block(kfs, n_kf, block);
     const SpMapKeyframe kf = kfs[lo];
     const long long at = (long long)(block - kf.first_block) * SP_BLOCK + tid;
     if (at < 0 || at >= kf.P) return;
@@ -314,10 +311,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_keyframe_depth_keys(const SpMapKey
     if (!(z > 0.f && z < HUGE_VALF)) return;               // NaN, 0 (underflow), inf: no surface
     const int r = (int)row, c = (int)col;
     if (r >= H || c >= W) return;                          // (a table of another size: never written beyond the image)
-    const unsigned long long key = ((unsigned long long)(~__float_as_uint(z)) << 32) | (unsigned long long)((uint32_t)i + 1u);
-    unsigned long long* slot = keys + ((size_t)lo * H + r) * W + c;
-    if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= key) return;
-    atomicMax(slot, key);
+    key_offer(keys + ((size_t)lo * H + r) * W + c, key_nearest(z, (uint32_t)i));
 }
 
 // grid ceil(n_kf H W / 256), block SP_BLOCK
@@ -327,8 +321,8 @@ __global__ __launch_bounds__(SP_BLOCK) void k_keyframe_depth_resolve(const unsig
     const long long at = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
     if (at >= n_pix) return;
     const unsigned long long k = keys[at];
-    depth[at] = k ? __uint_as_float(~(uint32_t)(k >> 32)) : 0.f;
-    if (seg) seg[at] = k ? map_point_segment(kfs[at / HW], (int)((uint32_t)(k & 0xffffffffull) - 1u)) : -1;
+    depth[at] = key_nearest_z(k);
+    if (seg) seg[at] = k ? map_point_segment(kfs[at / HW], key_nearest_id(k)) : -1;
 }
 
 }  // namespace

@@ -2,24 +2,26 @@
 // it, plus a depth-buffer mode the reference does not have) and depth images lifted into a point cloud (tool/viz.py:30-51
 // depth_image_lift, i.e. Open3D's PointCloud.create_from_depth_image with depth_scale 1, stride 1, then transform).
 //
-// sp_render_views.  Splat pass: one thread per point, its three floats staged through LDS (one coalesced read of the workgroup's 3 x 256
+// sp_render_views and sp_render_splats check their own arguments and share everything after that (render_launch): the limits, the empty
+// keys, ONE key pass -- k_view_keys, a template on "a point is a pixel" / "a point is a footprint" -- and the resolve pass.
+//
+// Key pass, common part: one thread per point, its three floats staged through LDS (one coalesced read of the workgroup's 3 x 256
 // floats), then a loop over the views.  Every 16 views the workgroup forms their float64 numbers once into LDS -- R^T (9), t (3), fx, fy,
 // cx, cy and an "identity pose" flag -- so the per-view operands are wave-uniform LDS broadcasts.  Arithmetic in float64 from the float32
 // inputs, every operation rounded on its own (contraction is switched off for this file: the reference is NumPy in float64):
 //     d = p - t;   p_c = ((Rt0 d0 + Rt1 d1) + Rt2 d2) per row   (an exact identity pose skips both: p_c = p, as render_pcd has it --
 //     0 x inf would otherwise turn a point at z = inf, which the reference keeps, into NaN);   u = x fx / z + cx;   v = y fy / z + cy.
-// Kept iff 0 <= u < W and 0 <= v < H (NaN and +-inf fail); pixel (trunc v, trunc u).  One 64-bit atomicMax per kept (point, view), no
-// return value; a relaxed load of the key first skips points that already lose (the race is benign: the atomic decides).
-//     mode 0  key = (i + 1) << 32 | bits(float32 z): the highest index wins, NumPy's repeated-index assignment; no test on z at all
-//     mode 1  key = ~bits(float32 z) << 32 | (i + 1), only for z > z_min >= 0 (float32 z is then a non-negative float, whose bits order as
-//             unsigned integers): the smallest float32 z wins, equal float32 z goes to the highest index
+// A kept (point, view) offers its key to its pixels (key_offer; the two key forms, their decoders and why float32 z orders as an
+// integer are in sp_map_device.h).
+//     pixel, mode 0  kept iff 0 <= u < W and 0 <= v < H (NaN and +-inf fail), pixel (trunc v, trunc u); the "highest id" key: NumPy's
+//                    repeated-index assignment; no test on z at all
+//     pixel, mode 1  the same test, then z > z_min >= 0; the "nearest" key
+//     footprint      (sp_render_splats; the radius staged through LDS beside the coordinates, in this instantiation only) z > z_min and
+//                    finite u, v; the half-widths ru = (r fx) / z, rv = (r fy) / z in float64, not >= 0 -> 0, capped at max_px; the
+//                    thread loops over the pixels whose cell meets [u - ru, u + ru] x [v - rv, v + rv], clipped to the image (bounds
+//                    clamped in float64 before the conversion: at most 33 x 33) with the point's one "nearest" key: a splat is flat
 // Resolve pass: one thread per pixel decodes the winner: index (or -1), depth = float32 z (or 0), image = trunc(c * 255) from the exact
 // float64 product, clamped to 0 .. 255, NaN -> 0 (or 0, 0, 0).  Integer maxima commute: two runs give the same bits.
-//
-// sp_render_splats.  The splat pass of mode 1 with a footprint per point (its radius staged through LDS beside its coordinates): the
-// half-widths ru = (r fx) / z, rv = (r fy) / z in float64, not >= 0 -> 0, capped at max_px; the thread loops over the pixels whose cell
-// meets [u - ru, u + ru] x [v - rv, v + rv], clipped to the image (bounds clamped in float64 before the conversion: at most 33 x 33),
-// with the same load-then-atomicMax per pixel and the point's one key: a splat is flat.  The resolve pass is k_render_resolve, unchanged.
 //
 // sp_map_consistency.  The same projection (camera_point / pixel_of below, one pair of functions for every kernel here), no keys: one
 // lane per point, 32 views per workgroup in LDS, and per seen (point, view) a gather of the (2 window + 1)^2 depths around its pixel
@@ -31,12 +33,13 @@
 // the resolve pass's conversion; n, sum d and sum d^2 as 32-bit integers per thread, wave (lane swaps) and workgroup (LDS), then one 64-bit
 // integer atomicAdd per workgroup and quantity.  Integers: exact, whatever the order.
 //
-// sp_depth_lift.  Three plain passes, no workgroup waits on another: (1) per 256-pixel block of one image the number of valid pixels
-// (0 < d <= depth_trunc; NaN invalid) by ballot and popcount; (2) one workgroup scans the block counts in place (exclusive) and writes
-// offsets and counts; (3) every block recomputes its ballot and writes its valid pixels at block offset + rank: row-major order, image
-// after image.  Point arithmetic in float64, every operation rounded on its own, rounded to float32 once at the end:
+// sp_depth_lift.  Ordered compaction (block_rank / block_count_scan of sp_map_device.h), three plain passes, no workgroup waits on
+// another: (1) per 256-pixel block of one image the number of valid pixels (0 < d <= depth_trunc; NaN invalid); (2) one workgroup scans
+// the block counts in place (exclusive) and writes offsets and counts; (3) every block recomputes its ranks and writes its valid pixels
+// at block offset + rank: row-major order, image after image.  Point arithmetic in float64, every operation rounded on its own, rounded
+// to float32 once at the end:
 //     x = ((c - cx) d) / fx;   y = ((r - cy) d) / fy;   z = d;   world = ((T0 x + T1 y) + T2 z) + T3 per row (no pose: the point itself).
-#include "sp_device.h"
+#include "sp_map_device.h"
 
 #pragma clang fp contract(off)
 
@@ -89,20 +92,39 @@ __device__ __forceinline__ void pixel_of(const ViewD& w, double x, double y, dou
     v = (y * w.fy) / z + w.cy;
 }
 
-// grid ceil(Q / 256), block SP_BLOCK
-__global__ __launch_bounds__(SP_BLOCK) void k_render_keys(const float* __restrict__ points, int Q, const SpView* __restrict__ views, int V,
-                                                          int H, int W, int mode, float z_min, unsigned long long* __restrict__ keys) {
+// the half-width of a footprint in pixels: anything that is not >= 0 (a negative or NaN radius, inf / inf) is a point
+__device__ __forceinline__ double half_width(double h, double cap) { return !(h >= 0.0) ? 0.0 : (h < cap ? h : cap); }
+
+// the radii of a workgroup's points: LDS that only the footprint instantiation of k_view_keys has
+template <bool FOOTPRINT>
+__device__ __forceinline__ float* radius_stage() {
+    if constexpr (!FOOTPRINT) return nullptr;
+    else { __shared__ float sr[SP_BLOCK]; return sr; }
+}
+
+// grid ceil(Q / 256), block SP_BLOCK: the key pass of sp_render_views (FOOTPRINT = false: one pixel per kept (point, view), mode 0 or
+// 1) and of sp_render_splats (FOOTPRINT = true: mode 1 with a rectangle of pixels per kept (point, view), at most 33 x 33; `mode` is
+// not read).  `mode` comes last, after the arguments the footprint pass had before the two passes became one: its instantiation is then
+// that pass instruction for instruction, pixel loops at the same offsets.  Those short loops (load, compare, atomic) are sensitive to
+// where they fall: the same instructions 16 bytes earlier cost 2 - 4 % at large footprints (profiles/map_kernels_refactor.txt)
+template <bool FOOTPRINT>
+__global__ __launch_bounds__(SP_BLOCK) void k_view_keys(const float* __restrict__ points, const float* __restrict__ radii, int Q,
+                                                        const SpView* __restrict__ views, int V, int H, int W, float z_min,
+                                                        int max_px, unsigned long long* __restrict__ keys, int mode) {
     __shared__ float sp[3 * SP_BLOCK];
     __shared__ ViewD vd[VIEW_CHUNK];
+    float* sr = radius_stage<FOOTPRINT>();
     const int tid = threadIdx.x;
     // the workgroups take the points from the END of the set: in mode 0 the highest index wins, so the early workgroups set keys that
-    // most later points lose against, and the load before the atomic skips them (ascending, every point would beat what it finds)
+    // most later points lose against, and the load before the atomic skips them (ascending, every point would beat what it finds);
+    // in mode 1 equal float32 z goes to the highest index
     const long long first = (long long)(gridDim.x - 1 - blockIdx.x) * SP_BLOCK;
     const int n = (int)((long long)Q - first < SP_BLOCK ? (long long)Q - first : SP_BLOCK);
     for (int j = tid; j < 3 * n; j += SP_BLOCK) sp[j] = points[3 * first + j];
+    if (FOOTPRINT && tid < n) sr[tid] = radii[first + tid];
     const size_t HW = (size_t)H * W;
     const double Wd = (double)W, Hd = (double)H, zmin = (double)z_min;
-    const uint32_t id1 = (uint32_t)(first + tid) + 1u;     // index + 1 (Q <= 2^31 - 2)
+    const uint32_t id = (uint32_t)(first + tid);           // (Q <= 2^31 - 2)
     for (int v0 = 0; v0 < V; v0 += VIEW_CHUNK) {
         const int nv = V - v0 < VIEW_CHUNK ? V - v0 : VIEW_CHUNK;
         __syncthreads();                                   // (sp is written; the previous chunk has been read)
@@ -110,69 +132,28 @@ __global__ __launch_bounds__(SP_BLOCK) void k_render_keys(const float* __restric
         __syncthreads();
         if (tid >= n) continue;
         const double px = (double)sp[3 * tid], py = (double)sp[3 * tid + 1], pz = (double)sp[3 * tid + 2];
+        const double rad = FOOTPRINT ? (double)sr[tid] : 0.0, cap = (double)max_px;       // (footprints only)
         for (int k = 0; k < nv; ++k) {
             const ViewD& w = vd[k];
             double x, y, z, u, v;
             camera_point(w, px, py, pz, x, y, z);
             pixel_of(w, x, y, z, u, v);
-            if (!(u >= 0.0 && u < Wd && v >= 0.0 && v < Hd)) continue;
-            if (mode == 1 && !(z > zmin)) continue;
-            const uint32_t zb = __float_as_uint((float)z);
-            const unsigned long long key = mode == 1 ? ((unsigned long long)(~zb) << 32) | (unsigned long long)id1
-                                                     : ((unsigned long long)id1 << 32) | (unsigned long long)zb;
-            unsigned long long* slot = keys + (size_t)(v0 + k) * HW + (size_t)(int)v * W + (size_t)(int)u;
-            if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= key) continue;
-            atomicMax(slot, key);
-        }
-    }
-}
-
-// the half-width of a footprint in pixels: anything that is not >= 0 (a negative or NaN radius, inf / inf) is a point
-__device__ __forceinline__ double half_width(double h, double cap) { return !(h >= 0.0) ? 0.0 : (h < cap ? h : cap); }
-
-// grid ceil(Q / 256), block SP_BLOCK.  k_render_keys in mode 1 with a rectangle of pixels per kept (point, view): at most 33 x 33
-__global__ __launch_bounds__(SP_BLOCK) void k_splat_keys(const float* __restrict__ points, const float* __restrict__ radii, int Q,
-                                                         const SpView* __restrict__ views, int V, int H, int W, float z_min, int max_px,
-                                                         unsigned long long* __restrict__ keys) {
-    __shared__ float sp[3 * SP_BLOCK];
-    __shared__ float sr[SP_BLOCK];
-    __shared__ ViewD vd[VIEW_CHUNK];
-    const int tid = threadIdx.x;
-    // (from the end of the set, as k_render_keys: equal float32 z goes to the highest index)
-    const long long first = (long long)(gridDim.x - 1 - blockIdx.x) * SP_BLOCK;
-    const int n = (int)((long long)Q - first < SP_BLOCK ? (long long)Q - first : SP_BLOCK);
-    for (int j = tid; j < 3 * n; j += SP_BLOCK) sp[j] = points[3 * first + j];
-    if (tid < n) sr[tid] = radii[first + tid];
-    const size_t HW = (size_t)H * W;
-    const double Wd = (double)W, Hd = (double)H, zmin = (double)z_min, cap = (double)max_px;
-    const uint32_t id1 = (uint32_t)(first + tid) + 1u;
-    for (int v0 = 0; v0 < V; v0 += VIEW_CHUNK) {
-        const int nv = V - v0 < VIEW_CHUNK ? V - v0 : VIEW_CHUNK;
-        __syncthreads();
-        if (tid < nv) view_setup(views[v0 + tid], vd[tid]);
-        __syncthreads();
-        if (tid >= n) continue;
-        const double px = (double)sp[3 * tid], py = (double)sp[3 * tid + 1], pz = (double)sp[3 * tid + 2], rad = (double)sr[tid];
-        for (int k = 0; k < nv; ++k) {
-            const ViewD& w = vd[k];
-            double x, y, z, u, v;
-            camera_point(w, px, py, pz, x, y, z);
-            pixel_of(w, x, y, z, u, v);
-            if (!(z > zmin) || !(fabs(u) < HUGE_VAL) || !(fabs(v) < HUGE_VAL)) continue;
-            const double ru = half_width((rad * w.fx) / z, cap), rv = half_width((rad * w.fy) / z, cap);
-            const double ul = u - ru, uh = u + ru, vl = v - rv, vh = v + rv;
-            if (!(uh >= 0.0 && ul < Wd && vh >= 0.0 && vl < Hd)) continue;
-            // clamped in float64, then converted: 0 <= c0 <= c1 <= W - 1 and 0 <= r0 <= r1 <= H - 1
-            const int c0 = (int)fmax(floor(ul), 0.0), c1 = (int)fmin(floor(uh), Wd - 1.0);
-            const int r0 = (int)fmax(floor(vl), 0.0), r1 = (int)fmin(floor(vh), Hd - 1.0);
-            const unsigned long long key = ((unsigned long long)(~__float_as_uint((float)z)) << 32) | (unsigned long long)id1;
             unsigned long long* view_keys = keys + (size_t)(v0 + k) * HW;
-            for (int r = r0; r <= r1; ++r) {
-                unsigned long long* row = view_keys + (size_t)r * W;
-                for (int c = c0; c <= c1; ++c) {
-                    if (__hip_atomic_load(row + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= key) continue;
-                    atomicMax(row + c, key);
-                }
+            if constexpr (!FOOTPRINT) {
+                if (!(u >= 0.0 && u < Wd && v >= 0.0 && v < Hd)) continue;
+                if (mode == 1 && !(z > zmin)) continue;
+                key_offer(view_keys + (size_t)(int)v * W + (size_t)(int)u, mode == 1 ? key_nearest((float)z, id) : key_highest_id((float)z, id));
+            } else {
+                if (!(z > zmin) || !(fabs(u) < HUGE_VAL) || !(fabs(v) < HUGE_VAL)) continue;
+                const double ru = half_width((rad * w.fx) / z, cap), rv = half_width((rad * w.fy) / z, cap);
+                const double ul = u - ru, uh = u + ru, vl = v - rv, vh = v + rv;
+                if (!(uh >= 0.0 && ul < Wd && vh >= 0.0 && vl < Hd)) continue;
+                // clamped in float64, then converted: 0 <= c0 <= c1 <= W - 1 and 0 <= r0 <= r1 <= H - 1
+                const int c0 = (int)fmax(floor(ul), 0.0), c1 = (int)fmin(floor(uh), Wd - 1.0);
+                const int r0 = (int)fmax(floor(vl), 0.0), r1 = (int)fmin(floor(vh), Hd - 1.0);
+                const unsigned long long key = key_nearest((float)z, id);                // a splat is flat: the point's one key
+                for (int r = r0; r <= r1; ++r)
+                    for (int c = c0; c <= c1; ++c) key_offer(view_keys + (size_t)r * W + c, key);
             }
         }
     }
@@ -301,13 +282,8 @@ __global__ __launch_bounds__(SP_BLOCK) void k_render_resolve(const unsigned long
     const long long at = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
     if (at >= n_pix) return;
     const unsigned long long k = keys[at];
-    int idx = -1;
-    float d = 0.f;
-    if (k) {
-        const uint32_t hi = (uint32_t)(k >> 32), lo = (uint32_t)(k & 0xffffffffull);
-        idx = (int)((mode == 1 ? lo : hi) - 1u);
-        d = __uint_as_float(mode == 1 ? ~hi : lo);
-    }
+    const int idx = mode == 1 ? key_nearest_id(k) : key_highest_id_id(k);
+    const float d = mode == 1 ? key_nearest_z(k) : key_highest_id_z(k);
     if (index) index[at] = idx;
     if (depth) depth[at] = d;
     if (image) {
@@ -330,10 +306,8 @@ __global__ __launch_bounds__(SP_BLOCK) void k_lift_count(const float* __restrict
     __shared__ int wc[SP_WAVES];
     const int p = blockIdx.x * SP_BLOCK + threadIdx.x;
     const bool ok = p < HW && lift_valid(depth[(size_t)blockIdx.y * HW + p], depth_trunc);
-    const unsigned long long ballot = __ballot(ok);
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(ballot);
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (wc[0] + wc[1]) + (wc[2] + wc[3]);
+    const int count = block_rank(ok, wc).count;
+    if (threadIdx.x == 0) block_counts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = count;
 }
 
 // one workgroup: bc[n] (n = B nblk) becomes its exclusive prefix sum; offsets[b] = the prefix at image b's first block, offsets[B] the
@@ -341,29 +315,12 @@ __global__ __launch_bounds__(SP_BLOCK) void k_lift_count(const float* __restrict
 __global__ __launch_bounds__(SP_BLOCK) void k_lift_scan(int32_t* __restrict__ bc, int n, int nblk, int B, int32_t* __restrict__ counts,
                                                         long long* __restrict__ offsets) {
     __shared__ long long part[SP_BLOCK];
-    const int tid = threadIdx.x;
-    const int per = (n + SP_BLOCK - 1) / SP_BLOCK;
-    const long long j0 = (long long)tid * per;
-    const long long j1 = j0 + per < n ? j0 + per : n;
-    long long s = 0;
-    for (long long j = j0; j < j1; ++j) s += bc[j];
-    part[tid] = s;
+    const long long total = block_count_scan(bc, n, part, [=](long long j, long long prefix) {
+        if (j % nblk == 0) offsets[j / nblk] = prefix;
+    });
+    if (threadIdx.x == 0) offsets[B] = total;
     __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int t = 0; t < SP_BLOCK; ++t) { const long long x = part[t]; part[t] = run; run += x; }
-        offsets[B] = run;
-    }
-    __syncthreads();
-    long long run = part[tid];
-    for (long long j = j0; j < j1; ++j) {
-        const int c = bc[j];
-        bc[j] = (int32_t)run;
-        if (j % nblk == 0) offsets[j / nblk] = run;
-        run += c;
-    }
-    __syncthreads();
-    for (int b = tid; b < B; b += SP_BLOCK) counts[b] = (int32_t)(offsets[b + 1] - offsets[b]);
+    for (int b = threadIdx.x; b < B; b += SP_BLOCK) counts[b] = (int32_t)(offsets[b + 1] - offsets[b]);
 }
 
 // grid (ceil(H W / 256), B)
@@ -373,16 +330,13 @@ __global__ __launch_bounds__(SP_BLOCK) void k_lift_write(const float* __restrict
                                                          float* __restrict__ points, float* __restrict__ colours,
                                                          int32_t* __restrict__ pixel) {
     __shared__ int wc[SP_WAVES];
-    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
     const int p = blockIdx.x * SP_BLOCK + threadIdx.x;
     const float df = p < HW ? depth[(size_t)b * HW + p] : 0.f;
     const bool ok = p < HW && lift_valid(df, depth_trunc);
-    const unsigned long long ballot = __ballot(ok);
-    if (lane == 0) wc[wave] = __popcll(ballot);
-    __syncthreads();
+    const int rank = block_rank(ok, wc).rank;
     if (!ok) return;
-    size_t row = (size_t)block_offsets[(size_t)b * gridDim.x + blockIdx.x] + (size_t)__popcll(ballot & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) row += (size_t)wc[w];
+    const size_t row = (size_t)block_offsets[(size_t)b * gridDim.x + blockIdx.x] + (size_t)rank;
     const float* Kb = K + 9 * (size_t)b;
     const double fx = (double)Kb[0], fy = (double)Kb[4], cx = (double)Kb[2], cy = (double)Kb[5];
     const int r = p / W, c = p - r * W;
@@ -408,22 +362,18 @@ __global__ __launch_bounds__(SP_BLOCK) void k_lift_write(const float* __restrict
     pixel[row] = p;
 }
 
-}  // namespace
-
-extern "C" {
-
-int sp_render_views(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, int mode, float z_min,
-                    unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream) {
-    if (!points || !views || !keys || (image && !colours)) return SP_EINVAL;
-    if (Q <= 0 || V <= 0 || H <= 0 || W <= 0 || (mode != 0 && mode != 1) || !(z_min >= 0.f)) return SP_EINVAL;
+// what sp_render_views (radii = NULL) and sp_render_splats launch once their own arguments are checked: the limits, empty keys, the key
+// pass and, if any output is asked for, the resolve pass
+int render_launch(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, int mode, float z_min,
+                  const float* radii, int max_px, unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream) {
     const long long HW = (long long)H * W;
     if (Q > 0x7ffffffeLL || V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long n_pix = (long long)V * HW;
     hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)n_pix, s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_render_keys, dim3((unsigned)((Q + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, points, (int)Q, views, V, H, W,
-                       mode, z_min, keys);
+    hipLaunchKernelGGL(radii ? k_view_keys<true> : k_view_keys<false>, dim3((unsigned)((Q + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s,
+                       points, radii, (int)Q, views, V, H, W, z_min, max_px, keys, mode);
     SP_CHECK_LAUNCH();
     if (image || depth || index) {
         hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((n_pix + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, keys, colours,
@@ -433,25 +383,22 @@ int sp_render_views(const float* points, const float* colours, long long Q, cons
     return 0;
 }
 
+}  // namespace
+
+extern "C" {
+
+int sp_render_views(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, int mode, float z_min,
+                    unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream) {
+    if (!points || !views || !keys || (image && !colours)) return SP_EINVAL;
+    if (Q <= 0 || V <= 0 || H <= 0 || W <= 0 || (mode != 0 && mode != 1) || !(z_min >= 0.f)) return SP_EINVAL;
+    return render_launch(points, colours, Q, views, V, H, W, mode, z_min, nullptr, 0, keys, image, depth, index, stream);
+}
+
 int sp_render_splats(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, float z_min,
                      const float* radii, int max_px, unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream) {
     if (!points || !views || !keys || !radii || (image && !colours)) return SP_EINVAL;
     if (Q <= 0 || V <= 0 || H <= 0 || W <= 0 || !(z_min >= 0.f) || max_px < 0 || max_px > 16) return SP_EINVAL;
-    const long long HW = (long long)H * W;
-    if (Q > 0x7ffffffeLL || V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long n_pix = (long long)V * HW;
-    hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)n_pix, s);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_splat_keys, dim3((unsigned)((Q + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, points, radii, (int)Q, views, V, H,
-                       W, z_min, max_px, keys);
-    SP_CHECK_LAUNCH();
-    if (image || depth || index) {
-        hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((n_pix + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, keys, colours,
-                           (int)n_pix, 1, image, depth, index);
-        SP_CHECK_LAUNCH();
-    }
-    return 0;
+    return render_launch(points, colours, Q, views, V, H, W, 1, z_min, radii, max_px, keys, image, depth, index, stream);
 }
 
 int sp_map_consistency(const float* points, const int32_t* owner, long long Q, const SpView* views, const int32_t* view_owner, int V,

@@ -27,10 +27,7 @@ import torch
 
 from .. import _lib
 from ..lie.lie_algebra import pose_to_tq
-from ..segment_table import table_of
 from ..tool import pose_utils
-
-_BLOCK = 256          # rows per workgroup of sp_map_points
 
 
 def keyframe_points(kfs, klds, poses, stride=1, align=None, align_index=None):
@@ -40,6 +37,7 @@ def keyframe_points(kfs, klds, poses, stride=1, align=None, align_index=None):
     record that moves it into the aligned frame, or -1 for none (default: record 0 for all when ``align`` is given).
     Returns dict(points (Q,3), colours (Q,3) float32, kf_index (Q,), seg_ids (Q,) int32 on the device, offsets: (n+1,) host integers --
     keyframe k owns rows offsets[k] .. offsets[k+1])."""
+    from ..tool import viz
     n = len(kfs)
     if n == 0 or len(klds) != n or len(poses) != n:
         raise ValueError(f"keyframe_points: {n} keyframes, {len(klds)} log-depth vectors, {len(poses)} poses")
@@ -57,35 +55,13 @@ def keyframe_points(kfs, klds, poses, stride=1, align=None, align_index=None):
     _lib.require_device(poses_c, record, *[kf.image for kf in kfs], *klds)
     if record is not None and (record.dtype != torch.float64 or record.shape[1:] != (_lib.SP_TRAJ_ALIGN_DOUBLES,) or not record.is_contiguous()):
         raise ValueError("keyframe_points: align must be the (S, 32) float64 records of align_trajectories")
-    recs = (_lib.SpMapKeyframe * n)()
-    keep = [poses_c]                                       # the tensors the records point at, alive until the launch is queued
-    offsets = np.zeros(n + 1, dtype=np.int64)
-    block = 0
-    for k, (kf, kld) in enumerate(zip(kfs, klds)):
-        tab = table_of(kf)                                 # (raises ValueError for a keyframe without segment pixels)
-        image = kf.image[:3].detach().contiguous().float()
-        if tuple(image.shape) != (3, tab.H, tab.W):
-            raise ValueError(f"keyframe_points: keyframe {k}: image {tuple(image.shape)} against segments of {tab.H}x{tab.W}")
-        kld_c, K_c = kld.detach().contiguous().float(), kf.K.detach().contiguous().float()
-        if kld_c.numel() != tab.N or K_c.numel() != 9 or poses_c[k].numel() != 16:
-            raise ValueError(f"keyframe_points: keyframe {k}: {kld_c.numel()} log-depths for {tab.N} segments, K of {K_c.numel()}, pose of {poses_c[k].numel()}")
-        keep += [tab, image, kld_c, K_c]
-        r = recs[k]
-        r.pix, r.baseL, r.seg_off, r.kp_L = tab.pix.data_ptr(), tab.baseL.data_ptr(), tab.seg_off.data_ptr(), tab.kp_L.data_ptr()
-        r.kld, r.image, r.K, r.pose = kld_c.data_ptr(), image.data_ptr(), K_c.data_ptr(), poses_c[k].data_ptr()
-        r.N, r.P, r.H, r.W = tab.N, tab.P, tab.H, tab.W
-        q = (tab.P + stride - 1) // stride
-        r.out_offset, r.align, r.first_block = int(offsets[k]), int(align_index[k]), block
-        offsets[k + 1] = offsets[k] + q
-        block += (q + _BLOCK - 1) // _BLOCK
-    total = int(offsets[-1])
-    dev = poses_c.device
-    recs_d = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(dev)
+    recs_d, keep, offsets, blocks = viz.keyframe_records("keyframe_points", kfs, klds, stride, poses_c, align_index)    # (keep: alive until the launch)
+    total, dev = offsets[-1], poses_c.device
     out = dict(points=torch.empty(total, 3, dtype=torch.float32, device=dev), colours=torch.empty(total, 3, dtype=torch.float32, device=dev),
                kf_index=torch.empty(total, dtype=torch.int32, device=dev), seg_ids=torch.empty(total, dtype=torch.int32, device=dev))
-    _lib.check(lib.sp_map_points(_lib.ptr(recs_d), n, block, stride, _lib.ptr(record), n_align, _lib.ptr(out['points']), _lib.ptr(out['colours']),
+    _lib.check(lib.sp_map_points(_lib.ptr(recs_d), n, blocks, stride, _lib.ptr(record), n_align, _lib.ptr(out['points']), _lib.ptr(out['colours']),
                                  _lib.ptr(out['kf_index']), _lib.ptr(out['seg_ids']), total, _lib.stream_ptr()), "sp_map_points")
-    out['offsets'] = offsets
+    out['offsets'] = np.asarray(offsets, dtype=np.int64)
     return out
 
 

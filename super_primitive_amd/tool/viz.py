@@ -62,6 +62,22 @@ def _size(H, W):
     return H, W
 
 
+def _views(Ks, poses, V):
+    """The (V,25) contiguous float32 tensor of V ``SpView`` records: K row major, then the camera-to-world pose."""
+    return torch.cat((_cameras(Ks, V, "Ks"), _poses(poses, V, "poses")), dim=1).contiguous()
+
+
+def _z_min(z_min):
+    if not float(z_min) >= 0.0:
+        raise ValueError(f"z_min {z_min}")
+
+
+def _limits(what, V, H, W, Q=0, views="views"):
+    """The map kernels' limits: ids and pixels are 32-bit, a grid dimension 16-bit."""
+    if Q > 2 ** 31 - 2 or V > 65535 or V * H * W >= 2 ** 31:
+        raise ValueError(f"{what}: {f'{Q} points, ' if Q else ''}{V} {views} of {H}x{W} are beyond the kernel's limits")
+
+
 def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_MIN, image=True, depth=True, index=True, radii=None,
                  max_px=8):
     """ONE ``sp_render_views`` launch (include/sp_hip.h has the arithmetic): ``points`` (Q,3) float32 in the world, ``colours`` (Q,3)
@@ -82,9 +98,8 @@ def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_M
     if image and colours is None:
         raise ValueError("render_views: an image needs colours")
     cols = None if colours is None else _f32(colours, (Q, 3), "colours")
-    views = torch.cat((_cameras(Ks, V, "Ks"), _poses(poses, V, "poses")), dim=1).contiguous()         # V x SpView
-    if not float(z_min) >= 0.0:
-        raise ValueError(f"z_min {z_min}")
+    views = _views(Ks, poses, V)
+    _z_min(z_min)
     rad = None
     if radii is not None:
         if not depth_buffer:
@@ -92,8 +107,7 @@ def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_M
         rad = _f32(radii, (Q,), "radii")
         if int(max_px) != max_px or not 0 <= int(max_px) <= 16:
             raise ValueError(f"render_views: max_px {max_px} (0 .. 16)")
-    if Q > 2 ** 31 - 2 or V > 65535 or V * H * W >= 2 ** 31:
-        raise ValueError(f"render_views: {Q} points, {V} views of {H}x{W} are beyond the kernel's limits")
+    _limits("render_views", V, H, W, Q)
     lib = _lib.load()
     dev = pts.device
     keys = torch.empty(V * H * W, dtype=torch.int64, device=dev)
@@ -127,8 +141,7 @@ def image_metrics(rendered, target, index):
     if index.dtype != torch.int32 or tuple(index.shape) != (V, H, W):
         raise ValueError(f"index must be int32 {(V, H, W)}, got {index.dtype} {tuple(index.shape)}")
     tgt = _f32(target, (V, 3, H, W), "target")
-    if V > 65535 or V * H * W >= 2 ** 31:
-        raise ValueError(f"image_metrics: {V} views of {H}x{W} are beyond the kernel's limits")
+    _limits("image_metrics", V, H, W)
     lib = _lib.load()
     img, idx = rendered.contiguous(), index.contiguous()
     out = torch.empty(V, 3, dtype=torch.int64, device=img.device)
@@ -206,7 +219,35 @@ def depth_image_lift(depth, K, image=None, mask=None, T=None, depth_trunc=100.0)
     return res
 
 
-_BLOCK = 256          # table points per workgroup of sp_keyframe_depths (sp_map_points' walk at stride 1)
+_BLOCK = 256          # rows per workgroup of the keyframe walk (sp_map_points, sp_keyframe_depths): SP_BLOCK
+
+
+def keyframe_records(what, kfs, klds, stride=1, poses=None, align_index=None):
+    """The ``SpMapKeyframe`` records of one keyframe walk over every ``stride``-th table point: tables, log-depths and the ``first_block``
+    / ``out_offset`` accounting.  ``poses`` ((n,4,4) contiguous float32): also the keyframes' images and cameras, these poses and
+    ``align_index`` (n integers, default -1), which sp_map_points reads on top.  Raises ``ValueError`` as ``what`` before any pointer is
+    taken.  Returns (the records on the device, what they point at -- alive until the launch is queued --, the (n+1) row offsets, the workgroups)."""
+    from ..segment_table import table_of
+    rows = []                                              # per keyframe: table, log-depths and, with poses, image and K
+    for k, (kf, kld) in enumerate(zip(kfs, klds)):
+        tab = table_of(kf)                                 # (raises ValueError for a keyframe without segment pixels)
+        cam = [] if poses is None else [kf.image[:3].detach().contiguous().float(), kf.K.detach().contiguous().float()]
+        if cam and (tuple(cam[0].shape) != (3, tab.H, tab.W) or cam[1].numel() != 9 or poses[k].numel() != 16):
+            raise ValueError(f"{what}: keyframe {k}: image {tuple(cam[0].shape)} against segments of {tab.H}x{tab.W}, K of {cam[1].numel()}, pose of {poses[k].numel()}")
+        rows.append((tab, kld.detach().contiguous().float(), *cam))
+        if rows[-1][1].numel() != tab.N:
+            raise ValueError(f"{what}: keyframe {k}: {rows[-1][1].numel()} log-depths for {tab.N} segments")
+    recs, offsets, block = (_lib.SpMapKeyframe * len(rows))(), [0], 0
+    for k, (r, (tab, kld_c, *cam)) in enumerate(zip(recs, rows)):
+        r.pix, r.baseL, r.seg_off, r.kp_L, r.kld = tab.pix.data_ptr(), tab.baseL.data_ptr(), tab.seg_off.data_ptr(), tab.kp_L.data_ptr(), kld_c.data_ptr()
+        if cam:
+            r.image, r.K, r.pose = cam[0].data_ptr(), cam[1].data_ptr(), poses[k].data_ptr()
+        r.N, r.P, r.H, r.W = tab.N, tab.P, tab.H, tab.W
+        q = (tab.P + stride - 1) // stride
+        r.out_offset, r.align, r.first_block = offsets[k], -1 if align_index is None else int(align_index[k]), block
+        offsets.append(offsets[k] + q)
+        block += (q + _BLOCK - 1) // _BLOCK
+    return torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(rows[0][1].device), [poses, rows], offsets, block
 
 
 def keyframe_depths(kfs, klds):
@@ -220,33 +261,17 @@ def keyframe_depths(kfs, klds):
     if n == 0 or len(klds) != n:
         raise ValueError(f"keyframe_depths: {n} keyframes, {len(klds)} log-depth vectors")
     _on_device(*klds)
-    tabs, kld_cs = [], []
-    for k, (kf, kld) in enumerate(zip(kfs, klds)):
-        tab = table_of(kf)                                 # (raises ValueError for a keyframe without segment pixels)
-        if tabs and (tab.H, tab.W) != (tabs[0].H, tabs[0].W):
-            raise ValueError(f"keyframe_depths: keyframe {k} is {tab.H}x{tab.W}, keyframe 0 is {tabs[0].H}x{tabs[0].W}")
-        kld_c = kld.detach().contiguous().float()
-        if kld_c.numel() != tab.N:
-            raise ValueError(f"keyframe_depths: keyframe {k}: {kld_c.numel()} log-depths for {tab.N} segments")
-        tabs.append(tab)
-        kld_cs.append(kld_c)
-    size = (tabs[0].H, tabs[0].W)
-    recs = (_lib.SpMapKeyframe * n)()
-    block = 0
-    for r, tab, kld_c in zip(recs, tabs, kld_cs):          # (image, pose, align and out_offset are not read)
-        r.pix, r.baseL, r.seg_off, r.kp_L, r.kld = tab.pix.data_ptr(), tab.baseL.data_ptr(), tab.seg_off.data_ptr(), tab.kp_L.data_ptr(), kld_c.data_ptr()
-        r.N, r.P, r.H, r.W = tab.N, tab.P, tab.H, tab.W
-        r.out_offset, r.align, r.first_block = 0, -1, block
-        block += (tab.P + _BLOCK - 1) // _BLOCK
-    H, W = size
-    if n > 65535 or n * H * W >= 2 ** 31:
-        raise ValueError(f"keyframe_depths: {n} keyframes of {H}x{W} are beyond the kernel's limits")
+    sizes = [(tab.H, tab.W) for tab in map(table_of, kfs)]                   # (raises ValueError for a keyframe without segment pixels)
+    H, W = sizes[0]
+    if sizes.count(sizes[0]) != n:
+        raise ValueError(f"keyframe_depths: keyframes of differing sizes {sorted(set(sizes))}")
+    _limits("keyframe_depths", n, H, W, views="keyframes")
+    recs_d, keep, _, blocks = keyframe_records("keyframe_depths", kfs, klds)   # (image, pose, align and out_offset are not read)
     lib = _lib.load()
-    dev = kld_cs[0].device
-    recs_d = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(dev)
+    dev = recs_d.device
     keys = torch.empty(n * H * W, dtype=torch.int64, device=dev)
     out = dict(depth=torch.empty(n, H, W, dtype=torch.float32, device=dev), seg=torch.empty(n, H, W, dtype=torch.int32, device=dev))
-    _lib.check(lib.sp_keyframe_depths(_lib.ptr(recs_d), n, block, H, W, _lib.ptr(keys), _lib.ptr(out['depth']), _lib.ptr(out['seg']),
+    _lib.check(lib.sp_keyframe_depths(_lib.ptr(recs_d), n, blocks, H, W, _lib.ptr(keys), _lib.ptr(out['depth']), _lib.ptr(out['seg']),
                                       _lib.stream_ptr()), "sp_keyframe_depths")
     return out
 
@@ -274,17 +299,15 @@ def map_consistency(points, Ks, poses, depths, owner=None, view_owner=None, tol=
         raise ValueError(f"map_consistency: {Q} points against {V} views")
     d = _f32(depths, (V, None, None), "depths")
     H, W = _size(d.shape[1], d.shape[2])
-    views = torch.cat((_cameras(Ks, V, "Ks"), _poses(poses, V, "poses")), dim=1).contiguous()         # V x SpView
+    views = _views(Ks, poses, V)
     own = None if owner is None else _i32(owner, Q, "owner")
     vown = None if view_owner is None else _i32(view_owner, V, "view_owner")
     if not 0.0 <= float(tol) < 1.0:
         raise ValueError(f"map_consistency: tol {tol} (0 <= tol < 1)")
     if int(window) != window or not 0 <= int(window) <= 2:
         raise ValueError(f"map_consistency: window {window} (0 .. 2)")
-    if not float(z_min) >= 0.0:
-        raise ValueError(f"z_min {z_min}")
-    if Q > 2 ** 31 - 2 or V > 65535 or V * H * W >= 2 ** 31:
-        raise ValueError(f"map_consistency: {Q} points, {V} views of {H}x{W} are beyond the kernel's limits")
+    _z_min(z_min)
+    _limits("map_consistency", V, H, W, Q)
     lib = _lib.load()
     counts = torch.empty(Q, 3, dtype=torch.int32, device=pts.device)
     _lib.check(lib.sp_map_consistency(_lib.ptr(pts), _lib.ptr(own), Q, _lib.ptr(views), _lib.ptr(vown), V, _lib.ptr(d), H, W, float(tol),

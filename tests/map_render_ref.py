@@ -275,3 +275,15 @@ def lift_case_small():
 def lift_case_single():
     """One image of 64 x 80 (20 blocks of 256 pixels)."""
     return lift_inputs(1, 64, 80, 106)
+
+
+def lift_case_blocks():
+    """B = 3 images of 150 x 150: 88 blocks of 256 pixels per image, 264 in all -- more than the 256 threads of the block-count scan, so
+    every scan thread takes two blocks; images 1 and 2 start at blocks 88 and 176, the FIRST of a thread's pair."""
+    return lift_inputs(3, 150, 150, 108)
+
+
+def lift_case_blocks_odd():
+    """B = 3 images of 149 x 149: 87 blocks per image, 261 in all, two per scan thread; image 1 starts at block 87, the SECOND of a
+    thread's pair (an image boundary inside a thread's range), image 2 at block 174, the first of one."""
+    return lift_inputs(3, 149, 149, 109)

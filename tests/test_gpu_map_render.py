@@ -17,6 +17,7 @@ import torch
 
 import map_render_ref as ref
 from conftest import load_golden
+from map_splat_ref import case_splat_views17
 from gpu_util import T, npy
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +30,7 @@ LIFT_RTOL = 2.0 ** -23
 def _case(name):
     if name == "duplicates":
         return ref.case_duplicates()[0]
-    return dict(golden0=ref.case_golden0, collide=ref.case_collide, posed=ref.case_posed, edges=ref.case_edges)[name]()
+    return dict(golden0=ref.case_golden0, collide=ref.case_collide, posed=ref.case_posed, edges=ref.case_edges, views17=case_splat_views17)[name]()
 
 
 @functools.lru_cache(maxsize=None)
@@ -126,12 +127,16 @@ def _raw_render(name, mode, image=True, depth=True, index=True):
     return {k: None if v is None else npy(v) for k, v in out.items()}
 
 
-@pytest.mark.parametrize("mode", [0, 1])
-def test_three_posed_views_in_one_call(mode):
-    """Case 4: one view looks at the cloud, one has half of it behind, one sees nothing; outputs pre-filled with junk."""
-    c = _case("posed")
-    out = _raw_render("posed", mode)
-    _compare("posed", mode, out)
+@pytest.mark.parametrize("name,mode", [("posed", 0), ("posed", 1), ("views17", 0), ("views17", 1)], ids=["0", "1", "views17-0", "views17-1"])
+def test_three_posed_views_in_one_call(name, mode):
+    """Case 4: one view looks at the cloud, one has half of it behind, one sees nothing; outputs pre-filled with junk.  views17: the 17
+    views and 300 points of map_splat_ref.case_splat_views17 as points (radii ignored): one view more than the key pass stages at a time."""
+    c = _case(name)
+    out = _raw_render(name, mode)
+    _compare(name, mode, out)
+    if name == "views17":
+        assert out['index'].shape == (17, 30, 40) and (_want(name, 16, mode)[0][2] >= 0).any()      # the view of the second chunk sees points
+        return
     _, _, z1 = ref.project(c['points'], c['K'], c['poses'][1])
     won = out['index'][1][out['index'][1] >= 0]
     if mode == 0:
@@ -216,7 +221,8 @@ def _raw_lift(depth, K, poses, image):
     return out
 
 
-@pytest.mark.parametrize("make", [ref.lift_case_small, ref.lift_case_single], ids=["3x19x23", "1x64x80"])
+@pytest.mark.parametrize("make", [ref.lift_case_small, ref.lift_case_single, ref.lift_case_blocks, ref.lift_case_blocks_odd],
+                         ids=["3x19x23", "1x64x80", "3x150x150", "3x149x149"])
 def test_depth_lift(make):
     """Case 7: 0, negative, NaN, inf and > depth_trunc depths, an all-invalid and an all-valid image; the capacity buffers keep their
     junk beyond offsets[B]."""

@@ -7,6 +7,7 @@ import pytest
 
 import map_render_ref as ref
 from conftest import load_golden
+from map_splat_ref import case_splat_views17
 
 TAINT_CAP = 0.02          # the project's cap on excluded pixels (tests/test_gpu_segment_depth.py)
 
@@ -40,7 +41,8 @@ def test_mode0_statement_reproduces_the_reference_image(name):
 def _views():
     """(name, case, view, pose) of every view of every device case."""
     dup, _ = ref.case_duplicates()
-    cases = dict(golden0=ref.case_golden0(), collide=ref.case_collide(), duplicates=dup, posed=ref.case_posed(), edges=ref.case_edges())
+    cases = dict(golden0=ref.case_golden0(), collide=ref.case_collide(), duplicates=dup, posed=ref.case_posed(), edges=ref.case_edges(),
+                 views17=case_splat_views17())                                # (its points and views as points: the radii are not read)
     for name, case in cases.items():
         poses = case.get('poses')
         for k in range(1 if poses is None else len(poses)):
@@ -101,7 +103,8 @@ def test_summation_order_moves_no_position_by_a_sixteenth_of_delta(name, case, k
     assert worst <= ref.DELTA / 16
 
 
-@pytest.mark.parametrize("make", [ref.lift_case_small, ref.lift_case_single], ids=["3x19x23", "1x64x80"])
+@pytest.mark.parametrize("make", [ref.lift_case_small, ref.lift_case_single, ref.lift_case_blocks, ref.lift_case_blocks_odd],
+                         ids=["3x19x23", "1x64x80", "3x150x150", "3x149x149"])
 def test_lift_statement_against_a_literal_loop(make):
     depth, K, poses, image = make()
     B, H, W = depth.shape
@@ -127,7 +130,11 @@ def test_lift_statement_against_a_literal_loop(make):
     np.testing.assert_array_equal(got['pixel'], pix)
     np.testing.assert_array_equal(got['points'], np.array(rows).reshape(-1, 3))
     np.testing.assert_array_equal(got['colours'], np.array(cols).reshape(-1, 3))
-    if B == 3:
+    if H * W > 65536 // 3:                                                   # more blocks than the scan has threads: two per thread
+        nblk = -(-H * W // 256)
+        assert 256 < B * nblk <= 512 and min(counts) > 0
+        assert (nblk % 2 == 1) == (make is ref.lift_case_blocks_odd)         # image 1 starts at an odd block: inside a scan thread's pair
+    elif B == 3:
         assert counts[1] == 0 and counts[2] == H * W and 0 < counts[0] < H * W and pix[0] == 0       # 100.0 itself is valid
         for bad in (0.0, -1.5, 100.5):
             assert (depth[0] == bad).any()
