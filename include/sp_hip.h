@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 18
+#define SP_ABI_VERSION 19
 
 #define SP_EINVAL (-1)   /* bad argument (null pointer, non-positive size, ...) */
 #define SP_ELIMIT (-2)   /* size outside what the kernels support (H or W > 32767, N > 65535, ...) */
@@ -615,17 +615,7 @@ int sp_pairs_schedule_run_queue(const SpSchedule* sched, const SpQueue* queue, i
                                 int check_every, int max_rounds, int32_t* flag_dev, int32_t* flag_host, const SpVerdict* verdict /* or NULL */,
                                 void* stream);
 
-/* One optimiser iteration of every pair as a SINGLE launch: the workgroup that completes the last span of a pair
- * runs that pair's update in place (same arithmetic, same fixed reduction order as sp_pairs_cost followed by
- * sp_pairs_adam_step / sp_pairs_gn_step -- results are bitwise identical).  arrivals: n_pairs int32, zeroed once by
- * the caller (the kernel leaves it zeroed).  Other arguments as in the two-launch forms. */
-int sp_pairs_adam_iterate(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int n_pairs, int max_N,
-                          float* span_partials, float* seg_partials, int32_t* arrivals, float lr_kld, float lr_pose, float lr_aff, float* state,
-                          float* losses, void* stream);
-int sp_pairs_gn_iterate(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int n_pairs, int max_N,
-                        float irls_eps, float* span_partials, float* seg_partials, int32_t* arrivals, float lm_up, float lm_down,
-                        float lm_min,
-                        float* lm_state, float* backup, float* costs, void* stream);
+/* (ABI 19) sp_pairs_adam_iterate / sp_pairs_gn_iterate are retired: an iteration is sp_pairs_cost[_opt] followed by sp_pairs_adam_step / sp_pairs_gn_step. */
 
 /* ------------------------------------------------------------------------------------------------------
  * Fused SE(3)-Adam optimiser of the reference's driver loops (SURVEY.md section 8(b) "sp_adam_se3_step", 8(f) N1):

@@ -51,8 +51,6 @@ SIGNATURES = {
     "sp_pairs_schedule_gn_step": [P, I, I, F, F, F, P, P, P, P, P, P, P],
     "sp_pairs_schedule_run": [P, I, I, F, F, F, P, P, P, P, P, I, I, P, P, P, P],
     "sp_pairs_schedule_run_queue": [P, P, I, I, F, F, F, P, P, P, P, P, I, I, P, P, P, P],
-    "sp_pairs_adam_iterate": [P, P, P, I, I, I, P, P, P, F, F, F, P, P, P],
-    "sp_pairs_gn_iterate": [P, P, P, I, I, I, F, P, P, P, F, F, F, P, P, P, P],
     "sp_window_scratch_doubles": [I, I],
     "sp_window_compose": [P, P, I, P, I, P],
     "sp_window_step": [P, P, I, P, I, P, I, I, P, P, P, I, I, F, P, P, I, P],
@@ -109,7 +107,7 @@ SIGNATURES = {
     "sp_map_fuse": [P, P, ctypes.c_longlong, F, F, F, F, P, P, P, P, P, P, P, P],
 }
 
-SP_ABI_VERSION = 18
+SP_ABI_VERSION = 19
 SP_GRAD_PARTIAL_FLOATS = 16
 SP_GN_PARTIAL_FLOATS = 32
 SP_GNA_PARTIAL_FLOATS = 48

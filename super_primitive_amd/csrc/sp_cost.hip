@@ -8,7 +8,7 @@
 // launches forward + the autograd backward) -- see include/sp_hip.h for the ABI and DESIGN.md for the layout.
 #include <type_traits>
 
-#include "sp_solve_device.h"
+#include "sp_device.h"
 
 namespace {
 
@@ -630,24 +630,17 @@ __device__ __forceinline__ bool cursor_advance(SpanCursor& k, int& done_q) {
     return true;
 }
 
-template <bool WT>
-__device__ __forceinline__ void store_partial(float* p, float v) {
-    // fused cost+solve: the record is read by ANOTHER workgroup of this launch -> write-through (sc1) store
-    if (WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // mode 1: flush {h_pd(6), D, b_d} of the chunk this wave just finished into its segment record (mode 2: + {h_da, h_db})
-template <bool WT, bool AFF = false>
+template <bool AFF = false>
 __device__ __forceinline__ void flush_segment_gn(GnAcc& A, float* __restrict__ rec, AffAcc* aa = nullptr) {
     const int lane = lane_id();
     int pos; bool ok;
     if constexpr (AFF) {
         float v[10] = {A.hd01.x, A.hd01.y, A.hd[0].x, A.hd[0].y, A.hd[1].x, A.hd[1].y, A.D.x + A.D.y, A.bd.x + A.bd.y, aa->hda, aa->hdb};
         wave_sum_to_lanes<10>(v, lane, pos, ok);
-        if (ok) store_partial<WT>(rec + pos, v[0]);
+        if (ok) rec[pos] = v[0];
         aa->hda = 0.f; aa->hdb = 0.f;
     } else {
         // [8], [9]: the chunk's own sum |r| and valid points (round 6: the verdict's WITHIN-PAIR test looks at the cost per segment).
@@ -656,7 +649,7 @@ __device__ __forceinline__ void flush_segment_gn(GnAcc& A, float* __restrict__ r
         float v[10] = {A.hd01.x, A.hd01.y, A.hd[0].x, A.hd[0].y, A.hd[1].x, A.hd[1].y, A.D.x + A.D.y, A.bd.x + A.bd.y,
                        A.cost - A.cost_mark, A.n - A.n_mark};
         wave_sum_to_lanes<10>(v, lane, pos, ok);
-        if (ok) store_partial<WT>(rec + pos, v[0]);
+        if (ok) rec[pos] = v[0];
         A.cost_mark = A.cost; A.n_mark = A.n;
     }
     const f32x2 z{0.f, 0.f};
@@ -668,7 +661,7 @@ __device__ __forceinline__ void flush_segment_gn(GnAcc& A, float* __restrict__ r
 // over the wave only -- so that the padding granule of the tables is 64 points instead of 256 (small ragged segments: 1200
 // SAM-like masks of ~280 pixels pad 40 % at 256 and 11 % at 64); the four waves of a workgroup work on four consecutive spans.
 // RD (W64 depth tables only): pixel words from the run descriptors of the pair's table (rd = its group 0) instead of pix
-template <bool DT, bool WT, bool AFF = false, bool W64 = false, bool RD = false>
+template <bool DT, bool AFF = false, bool W64 = false, bool RD = false>
 __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, const int4* __restrict__ chunks, int q0,
                                             int n_chunks, int total, float irls_eps, float* __restrict__ span_rec,
                                             float* __restrict__ seg_partials, float* lds, const SpRunDesc* rd = nullptr) {
@@ -759,7 +752,7 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
         f32x3 td = buf_load3(r_trg, a.p.off0 + 4u * SP_TEXEL_FLOATS, c.row_bytes);
         __builtin_amdgcn_sched_barrier(0);
         fold_gn2<AFF>(kc, GeoGn{b.p.qxy, b.p.qz, b.p.zinv, b.p.zi}, m, A, &ma, &AA);
-        if (b.last) flush_segment_gn<WT, AFF>(A, seg_partials + (size_t)(W64 ? b.q : 4 * b.q + wave) * NS, &AA);
+        if (b.last) flush_segment_gn<AFF>(A, seg_partials + (size_t)(W64 ? b.q : 4 * b.q + wave) * NS, &AA);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("" : "+v"(ta), "+v"(tb), "+v"(tc), "+v"(td), "+v"(A.blk[0]), "+v"(A.blk[1]), "+v"(A.blk[2]),
                      "+v"(A.blk[3]), "+v"(A.blk[4]), "+v"(A.blk[5]), "+v"(A.bp[0]), "+v"(A.bp[1]), "+v"(A.hd[0]),
@@ -778,10 +771,10 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
     if (j < n_iter) {                    // odd trip count: the last point sits in S0
         trip(S0, S1);
         fold_gn2<AFF>(kc, GeoGn{S0.p.qxy, S0.p.qz, S0.p.zinv, S0.p.zi}, m, A, &ma, &AA);
-        flush_segment_gn<WT, AFF>(A, seg_partials + (size_t)(W64 ? S0.q : 4 * S0.q + wave) * NS, &AA);
+        flush_segment_gn<AFF>(A, seg_partials + (size_t)(W64 ? S0.q : 4 * S0.q + wave) * NS, &AA);
     } else {
         fold_gn2<AFF>(kc, GeoGn{S1.p.qxy, S1.p.qz, S1.p.zinv, S1.p.zi}, m, A, &ma, &AA);
-        flush_segment_gn<WT, AFF>(A, seg_partials + (size_t)(W64 ? S1.q : 4 * S1.q + wave) * NS, &AA);
+        flush_segment_gn<AFF>(A, seg_partials + (size_t)(W64 ? S1.q : 4 * S1.q + wave) * NS, &AA);
     }
     float acc[NV];
     acc[0] = A.cost;
@@ -808,16 +801,16 @@ __device__ __forceinline__ void run_span_gn(const TileCtx& c, const SpPair& pr, 
     if (W64) {
         int pos; bool ok;
         wave_sum_to_lanes<NV>(acc, (int)((op >> 2) & 63u), pos, ok);
-        if (ok) store_partial<WT>(span_rec + pos, acc[0]);
+        if (ok) span_rec[pos] = acc[0];
     } else {
         const int tid = (int)((op >> 2) & (uint32_t)(SP_BLOCK - 1));
         const float tot = block_sum_to_thread<NV>(acc, lds, tid);
-        if (tid < NV) store_partial<WT>(span_rec + tid, tot);
+        if (tid < NV) span_rec[tid] = tot;
     }
 }
 
 // mode 0: the segment column is 13 (d/dkld)
-template <bool DT, bool WT, bool W64 = false, bool RD = false>
+template <bool DT, bool W64 = false, bool RD = false>
 __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr, const int4* __restrict__ chunks, int q0,
                                               int n_chunks, int total, float* __restrict__ span_rec,
                                               float* __restrict__ seg_partials, float* lds, const SpRunDesc* rd = nullptr) {
@@ -859,7 +852,7 @@ __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr
     Mix0 m0{0.f, 0.f, 0.f, 0.f};
     auto flush = [&](int q) {
         const float tot = wave_sum(acc[13]);
-        if (lane_id() == 0) store_partial<WT>(seg_partials + (size_t)(W64 ? q : 4 * q + wave) * SP_GRAD_SEG_FLOATS, tot);
+        if (lane_id() == 0) seg_partials[(size_t)(W64 ? q : 4 * q + wave) * SP_GRAD_SEG_FLOATS] = tot;
         acc[13] = 0.f;
     };
     auto trip = [&](Slot& a, Slot& b) {
@@ -902,11 +895,11 @@ __device__ __forceinline__ void run_span_grad(const TileCtx& c, const SpPair& pr
     if (W64) {
         int pos; bool ok;
         wave_sum_to_lanes<NV>(acc, (int)((op >> 2) & 63u), pos, ok);
-        if (ok) store_partial<WT>(span_rec + pos, acc[0]);
+        if (ok) span_rec[pos] = acc[0];
     } else {
         const int tid = (int)((op >> 2) & (uint32_t)(SP_BLOCK - 1));
         const float tot = block_sum_to_thread<NV>(acc, lds, tid);      // (column 13 is zero here: flushed per chunk)
-        if (tid < NV) store_partial<WT>(span_rec + tid, tot);
+        if (tid < NV) span_rec[tid] = tot;
     }
 }
 
@@ -1031,15 +1024,8 @@ __global__ __launch_bounds__(SP_BLOCK) void k_finalise_single(const float* __res
 // ------------------------------------------------------------------------------------------------
 // many independent pairs: grid = n_tiles_total
 // ------------------------------------------------------------------------------------------------
-// FUSED = 0: cost pass only.  FUSED = 1 / 2: the workgroup that finishes the LAST tile of a frame pair also runs
-// that pair's Adam / Gauss-Newton update (solve_adam / solve_gn), so one optimiser iteration of the whole batch is a
-// single launch and solver work overlaps with other pairs' tiles.  Hand-off protocol (cdna_hip_programming.md
-// Guideline 16, write-through form): partial stores are sc1, every storing lane drains them (s_waitcnt vmcnt(0)),
-// workgroup barrier, one relaxed agent-scope fetch-add on the pair's arrival counter; the last arriver performs one
-// agent-scope acquire (invalidates its CU's L1), barrier, then reads the partials with plain loads.  The counter is
-// reset by the last arriver, so the buffer stays all-zero between launches.
 #define SP_SCHED_LISTS 8
-struct SchedList {            // one work list of a launch over SEVERAL (k_cost_pairs with FuseArgs.sched.n_lists > 0)
+struct SchedList {            // one work list of a launch over SEVERAL (k_cost_pairs with CostArgs.sched.n_lists > 0)
     const int4* chunks;
     const int4* spans;
     float* partials;
@@ -1057,10 +1043,7 @@ struct SchedCost {            // what the cost kernel needs of an SpSchedule
     int32_t n_lists;          // > 0: the launch covers `list[0 .. n_lists)`, one after the other in block order
     SchedList list[SP_SCHED_LISTS];
 };
-struct FuseArgs {
-    int32_t* arrivals;
-    AdamArgs adam;
-    GnArgs gn;
+struct CostArgs {
     const int32_t* done;      // [n_pairs] or NULL: spans of pairs marked done by the solver return at once
     const int32_t* phase;     // per-pair schedules (sp_pairs_schedule_cost): the phase of a pair selects its level descriptors and
     SchedCost sched;          // IRLS epsilon; spans of pairs that are finished, or in a phase of another work list, return at once
@@ -1077,16 +1060,18 @@ constexpr int FORM_LOG_DEPTH = 0, FORM_DEPTH = 6;
 
 // Where the pixel word of a point comes from: the pix stream, or the run descriptors f.rd_pix / f.rd_desc (wave-span depth tables only).
 // The source is the argument of the CLASS the kernel is a member of, not one of the kernel's own template arguments: a kernel's
-// profiler-visible name is CostFrom<..>::k_cost_pairs<MODE, FORM, FUSED, W64>, and that tail is what bench.py looks for.
+// profiler-visible name is CostFrom<..>::k_cost_pairs<MODE, FORM, 0, W64>, and that tail is what bench.py looks for.
 struct Pix;
 struct RunDesc;
 template <class SRC>
 struct CostFrom {
-template <int MODE, int FORM = FORM_LOG_DEPTH, int FUSED = 0, bool W64 = false>
-static __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 4)) void k_cost_pairs(
+// (ZERO: read by nothing; it exists only so that the profiler-visible name keeps its four arguments)
+template <int MODE, int FORM = FORM_LOG_DEPTH, int ZERO = 0, bool W64 = false>
+static __global__ __launch_bounds__(SP_BLOCK, MODE == 2 ? 2 : 4) void k_cost_pairs(
         const SpPair* __restrict__ pairs, const int4* __restrict__ chunks, const int4* __restrict__ spans, int n_spans,
-        float irls_eps, float* __restrict__ partials, float* __restrict__ seg_partials, FuseArgs f) {
+        float irls_eps, float* __restrict__ partials, float* __restrict__ seg_partials, CostArgs f) {
     static_assert(FORM == FORM_LOG_DEPTH || FORM == FORM_DEPTH, "FORM: log-depth tables (0) or depth tables (6)");
+    static_assert(ZERO == 0, "the third template argument is a placeholder");
     constexpr bool RD = std::is_same<SRC, RunDesc>::value;
     constexpr bool DT = FORM == FORM_DEPTH;
     constexpr int NV = MODE == 0 ? SP_GRAD_PARTIAL_FLOATS : (MODE == 2 ? SP_GNA_PARTIAL_FLOATS : SP_GN_PARTIAL_FLOATS);
@@ -1122,7 +1107,7 @@ static __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 
     if (w >= n_spans) return;
     int owner;                              // index of the span's pair in `pairs` / `phase` (a slot, in a queue run)
     int4 span;                              // {first chunk, number of chunks, points, pair}
-    if (MODE == 1 && FUSED == 0 && f.phase && vspans > 0) {
+    if (MODE == 1 && f.phase && vspans > 0) {
         // QUEUE RUN (SpQueue): the launch is over virtual spans, `vspans` per slot; virtual span j of a slot is span tile0 + j of the
         // pair the slot works on right now (its descriptor carries the pair's own span range of the batch's list), or nothing
         owner = w / vspans;
@@ -1163,28 +1148,9 @@ static __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 
     c.start = 0; c.count = 0;
     // (RD: the pair's table starts a multiple of 64 points into the flat array: its group 0)
     const SpRunDesc* rd = RD ? f.rd_desc + ((const uint32_t*)pr.pix - f.rd_pix) / 64 : nullptr;
-    if (MODE == 2) run_span_gn<DT, FUSED != 0, true>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds);
-    else if (MODE == 1) run_span_gn<DT, FUSED != 0, false, W64, RD>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds, rd);
-    else run_span_grad<DT, FUSED != 0, W64, RD>(c, pr, chunks, span.x, span.y, span.z, partials + (size_t)w * NV, seg_partials, lds, rd);
-    if (FUSED != 0) {
-        __shared__ int is_last;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int old = __hip_atomic_fetch_add(f.arrivals + span.w, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = old == pr.n_tiles - 1;
-            if (last) {
-                __hip_atomic_store(f.arrivals + span.w, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-            is_last = last;
-        }
-        __syncthreads();
-        if (is_last) {
-            if (FUSED == 1) solve_adam(pairs, span.w, partials, seg_partials, f.adam);
-            else solve_gn(pairs, span.w, partials, seg_partials, f.gn);
-        }
-    }
+    if (MODE == 2) run_span_gn<DT, true>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds);
+    else if (MODE == 1) run_span_gn<DT, false, W64, RD>(c, pr, chunks, span.x, span.y, span.z, irls_eps, partials + (size_t)w * NV, seg_partials, lds, rd);
+    else run_span_grad<DT, W64, RD>(c, pr, chunks, span.x, span.y, span.z, partials + (size_t)w * NV, seg_partials, lds, rd);
 }
 };  // CostFrom
 
@@ -1192,13 +1158,12 @@ static __global__ __launch_bounds__(SP_BLOCK, FUSED != 0 ? 1 : (MODE == 2 ? 2 : 
 struct CostVariant {
     int mode;                  // 0 cost + gradient, 1 Gauss-Newton, 2 Gauss-Newton with the target's affine pair
     bool dt, w64, rd;          // depth tables, wave spans, pixel words from run descriptors
-    int fused;                 // 0, or the solver the last workgroup of a pair runs: 1 Adam, 2 Gauss-Newton
 };
-using CostKernel = void (*)(const SpPair*, const int4*, const int4*, int, float, float*, float*, FuseArgs);
+using CostKernel = void (*)(const SpPair*, const int4*, const int4*, int, float, float*, float*, CostArgs);
 CostKernel cost_kernel(const CostVariant& v) {             // nullptr: no such variant
-    enum { DT = 4, W64 = 8, RD = 16, ADAM = 32, GN = 2 * ADAM };       // (ADAM, GN: fused 1, 2)
-    if (v.mode < 0 || v.mode > 2 || v.fused < 0 || v.fused > 2) return nullptr;
-    switch (v.mode | (v.dt ? DT : 0) | (v.w64 ? W64 : 0) | (v.rd ? RD : 0) | v.fused * ADAM) {
+    enum { DT = 4, W64 = 8, RD = 16 };
+    if (v.mode < 0 || v.mode > 2) return nullptr;
+    switch (v.mode | (v.dt ? DT : 0) | (v.w64 ? W64 : 0) | (v.rd ? RD : 0)) {
         case 0:                 return CostFrom<Pix>::k_cost_pairs<0>;
         case 1:                 return CostFrom<Pix>::k_cost_pairs<1>;
         case 2:                 return CostFrom<Pix>::k_cost_pairs<2>;
@@ -1210,8 +1175,6 @@ CostKernel cost_kernel(const CostVariant& v) {             // nullptr: no such v
         case 1 | DT | W64:      return CostFrom<Pix>::k_cost_pairs<1, FORM_DEPTH, 0, true>;
         case 0 | DT | W64 | RD: return CostFrom<RunDesc>::k_cost_pairs<0, FORM_DEPTH, 0, true>;
         case 1 | DT | W64 | RD: return CostFrom<RunDesc>::k_cost_pairs<1, FORM_DEPTH, 0, true>;
-        case 0 | ADAM:          return CostFrom<Pix>::k_cost_pairs<0, FORM_LOG_DEPTH, 1>;
-        case 1 | GN:            return CostFrom<Pix>::k_cost_pairs<1, FORM_LOG_DEPTH, 2>;
         default:                return nullptr;
     }
 }
@@ -1221,7 +1184,7 @@ int cost_blocks(int n_spans, bool w64) { return (((w64 ? (n_spans + 3) / 4 : n_s
 
 // SP_EINVAL (before any HIP call) if the variant does not exist
 int launch_cost(const CostVariant& v, int blocks, hipStream_t s, const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans,
-                float irls_eps, float* partials, float* seg_partials, const FuseArgs& f) {
+                float irls_eps, float* partials, float* seg_partials, const CostArgs& f) {
     const CostKernel k = cost_kernel(v);
     if (!k) return SP_EINVAL;
     const int4* c4 = reinterpret_cast<const int4*>(chunks);
@@ -1379,8 +1342,8 @@ int sp_pairs_cost_opt(const SpPair* pairs, const int32_t* chunks, const int32_t*
     if (!pairs || !chunks || !spans || !partials || !seg_partials || n_spans <= 0 || (pix_base == nullptr) != (desc == nullptr)) return SP_EINVAL;
     // (what remains of `mode` must be 0, 1 or 2; mode 2 has no flags, run descriptors are for wave-span depth tables: cost_kernel)
     const CostVariant v{mode & ~(SP_COST_WAVE_SPANS | SP_COST_DEPTH_TABLE), (mode & SP_COST_DEPTH_TABLE) != 0, (mode & SP_COST_WAVE_SPANS) != 0,
-                        desc != nullptr, 0};
-    FuseArgs f{};
+                        desc != nullptr};
+    CostArgs f{};
     f.done = done;
     f.rd_pix = pix_base;
     f.rd_desc = desc;
@@ -1398,9 +1361,9 @@ int sp_pairs_cost(const SpPair* pairs, const int32_t* chunks, const int32_t* spa
 // the cost pass (mode 2: the window optimiser's, or 0 / 1) over n_lists work lists of different batches in ONE launch
 int cost_pairs_multi(const MultiList* lists_dev, int n_lists, int total_blocks, int mode, float irls_eps, void* stream) {
     if (!lists_dev || n_lists <= 0 || total_blocks <= 0) return SP_EINVAL;
-    FuseArgs f{};
+    CostArgs f{};
     f.multi = lists_dev; f.n_multi = n_lists;
-    return launch_cost(CostVariant{mode, false, false, false, 0}, total_blocks, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, 0, irls_eps,
+    return launch_cost(CostVariant{mode, false, false, false}, total_blocks, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, 0, irls_eps,
                        nullptr, nullptr, f);
 }
 
@@ -1413,8 +1376,8 @@ int sp_pairs_schedule_cost(const SpSchedule* sched, const int32_t* phase, void* 
 namespace {
 // the Gauss-Newton pass of a schedule over the work list of phase `ph` (f.sched.n_lists > 0: over several lists of its kind -- wave
 // spans or workgroup spans, depth tables or log-depth tables)
-int launch_phase(const SpPhase& ph, int n_spans, int blocks, hipStream_t s, const FuseArgs& f) {
-    const CostVariant v{1, (ph.flags & SP_PHASE_DEPTH_TABLE) != 0, (ph.flags & SP_PHASE_WAVE_SPANS) != 0, false, 0};
+int launch_phase(const SpPhase& ph, int n_spans, int blocks, hipStream_t s, const CostArgs& f) {
+    const CostVariant v{1, (ph.flags & SP_PHASE_DEPTH_TABLE) != 0, (ph.flags & SP_PHASE_WAVE_SPANS) != 0, false};
     return launch_cost(v, blocks, s, ph.pairs, ph.chunks, ph.spans, n_spans, ph.irls_eps, ph.span_partials, ph.seg_partials, f);
 }
 }  // namespace
@@ -1435,7 +1398,7 @@ int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stre
     Lead leads[SP_MAX_PHASES];
     int n_leads = 0;
     uint32_t seen = 0;
-    FuseArgs f{};
+    CostArgs f{};
     f.phase = phase;
     if (queue && from.active && from.n_active > 0) { f.active = from.active; n_slots = from.n_active; }
     for (int p = 0; p < sched->n_phases; ++p) {
@@ -1487,33 +1450,3 @@ int schedule_cost_from(const SpSchedule* sched, const int32_t* phase, void* stre
     }
     return 0;
 }
-
-extern "C" {
-
-int sp_pairs_adam_iterate(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int n_pairs, int max_N,
-                          float* partials, float* seg_partials, int32_t* arrivals, float lr_kld, float lr_pose, float lr_aff, float* state,
-                          float* losses, void* stream) {
-    if (!pairs || !chunks || !spans || !partials || !seg_partials || !arrivals || !state || !losses || n_spans <= 0 || n_pairs <= 0 ||
-        max_N <= 0)
-        return SP_EINVAL;
-    FuseArgs f{};
-    f.arrivals = arrivals;
-    f.adam = AdamArgs{max_N, lr_kld, lr_pose, lr_aff, state, losses};
-    return launch_cost(CostVariant{0, false, false, false, 1}, cost_blocks(n_spans, false), static_cast<hipStream_t>(stream), pairs, chunks, spans, n_spans,
-                       0.f, partials, seg_partials, f);
-}
-
-int sp_pairs_gn_iterate(const SpPair* pairs, const int32_t* chunks, const int32_t* spans, int n_spans, int n_pairs, int max_N,
-                        float irls_eps, float* partials, float* seg_partials, int32_t* arrivals, float lm_up, float lm_down,
-                        float lm_min, float* lm_state, float* backup, float* costs, void* stream) {
-    if (!pairs || !chunks || !spans || !partials || !seg_partials || !arrivals || !lm_state || !backup || !costs || n_spans <= 0 || n_pairs <= 0 ||
-        max_N <= 0)
-        return SP_EINVAL;
-    FuseArgs f{};
-    f.arrivals = arrivals;
-    f.gn = gn_args(max_N, lm_up, lm_down, lm_min, lm_state, backup, costs);
-    return launch_cost(CostVariant{1, false, false, false, 2}, cost_blocks(n_spans, false), static_cast<hipStream_t>(stream), pairs, chunks, spans, n_spans,
-                       irls_eps, partials, seg_partials, f);
-}
-
-}  // extern "C"

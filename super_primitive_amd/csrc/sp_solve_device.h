@@ -1,5 +1,4 @@
-// Device-side solver bodies shared by the stand-alone solver kernels (sp_solver.hip) and the fused
-// cost+solve kernels (sp_cost.hip): per-pair tile-partial reduction (fixed order, fp64), Adam step with SE(3)
+// Device-side solver bodies of the stand-alone solver kernels (sp_solver.hip, and the window and chain files): per-pair tile-partial reduction (fixed order, fp64), Adam step with SE(3)
 // retraction, Gauss-Newton / Levenberg-Marquardt step.  See sp_solver.hip for the reference lines they replace.
 #pragma once
 #include "sp_device.h"

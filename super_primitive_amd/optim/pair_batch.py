@@ -255,11 +255,11 @@ class PairBatch:
         ``timer``: a ``batch_prepare._Timer`` that collects per-pass HIP-event times of the set-up.
         ``granule`` = 64: WAVE SPANS (include/sp_hip.h SP_COST_WAVE_SPANS) -- segments are padded to multiples of 64 instead of
         256 points, a span belongs to one wave, one segment record per chunk.  For batches of many small ragged segments: 1200
-        SAM-like masks of ~280 pixels pad 40 % at 256 and 11 % at 64.  The single-launch forms (``fused=True``) are not available.
+        SAM-like masks of ~280 pixels pad 40 % at 256 and 11 % at 64.
         ``depth_table`` (default): the batch's tables hold exp(L) in ``src4[..., 3]`` instead of L and the cost passes run in their
         depth-table form (include/sp_hip.h SP_COST_DEPTH_TABLE: one multiply per point instead of add + multiply + v_exp_f32, the
         exponential of the segment's shift taken once per chunk; -1.8 % kernel time).  ``False``: log-depth tables, as the per-keyframe
-        path (``segment_table``) keeps them; the single-launch forms (``fused=True``) need that.
+        path (``segment_table``) keeps them.
         ``run_desc`` (default; wave-span depth tables only): RUN DESCRIPTORS of the all-points table (include/sp_hip.h SpRunDesc, 0.5 B
         per point) -- ``cost_pass`` / ``gn_step`` / ``adam_step`` rebuild every point's pixel word from its 64-point group's record instead
         of reading pix (4 B per point), with bitwise the same results.  Only for tables none of whose groups has more than two runs
@@ -453,11 +453,10 @@ class PairBatch:
         self.adam_state = state_f[cuts[1]: cuts[1] + M * widths[1]].view(M, widths[1])
         self.lm_state = state_f[cuts[2]: cuts[2] + M * widths[2]].view(M, widths[2])
         self.backup = state_f[cuts[3]: cuts[3] + M * widths[3]].view(M, widths[3])
-        state_i = torch.zeros(4, M, dtype=torch.int32, device=dev)
-        self.arrivals = state_i[0]        # per-pair tile-arrival counters (fused launch)
-        self.done = state_i[1]            # per-pair convergence flags (gn_step(conv_tol=...))
-        self.phase = state_i[2]           # per-pair position in a device-side schedule (run_scheduled)
-        self.phase_iters = state_i[3]
+        state_i = torch.zeros(3, M, dtype=torch.int32, device=dev)
+        self.done = state_i[0]            # per-pair convergence flags (gn_step(conv_tol=...))
+        self.phase = state_i[1]           # per-pair position in a device-side schedule (run_scheduled)
+        self.phase_iters = state_i[2]
         mark('workspaces')
         self.reset_lm()
         self._graphs = {}
@@ -530,20 +529,10 @@ class PairBatch:
                                               _lib.ptr(self.seg_partials), _lib.ptr(done), _lib.ptr(self.pix if rd else None),
                                               _lib.ptr(self.run_desc if rd else None), _lib.stream_ptr()), "sp_pairs_cost_opt")
 
-    def gn_step(self, level=0, irls_eps=1e-3, lm_up=8.0, lm_down=0.5, lm_min=1e-7, fused=False, conv_tol=0.0):
+    def gn_step(self, level=0, irls_eps=1e-3, lm_up=8.0, lm_down=0.5, lm_min=1e-7, conv_tol=0.0):
         """One Gauss-Newton/LM iteration of every pair at pyramid ``level``.  Returns the (M,) device tensor of costs
-        (= the reference's residual) evaluated at the parameters BEFORE this step.  Default: two launches (cost
-        pass, then one workgroup per pair).  ``fused=True``: a single launch in which the workgroup finishing a
-        pair's last tile also solves that pair -- bitwise the same results; measured 0-4 % slower on MI355X (the
-        solver's register/LDS footprint costs the cost kernel one wave per SIMD), kept for launch-bound hosts."""
-        if fused:
-            assert not self.wave_flag and not self.table_flag, "the single-launch form has no wave-span / depth-table variant (PairBatch(depth_table=False))"
-            _lib.check(self.lib.sp_pairs_gn_iterate(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, self.M,
-                                                    self.max_N, float(irls_eps), _lib.ptr(self.partials), _lib.ptr(self.seg_partials), _lib.ptr(self.arrivals),
-                                                    float(lm_up), float(lm_down), float(lm_min), _lib.ptr(self.lm_state),
-                                                    _lib.ptr(self.backup), _lib.ptr(self._costs), _lib.stream_ptr()),
-                       "sp_pairs_gn_iterate")
-            return self._costs
+        (= the reference's residual) evaluated at the parameters BEFORE this step.  Two launches: the cost pass,
+        then one workgroup per pair."""
         if conv_tol > 0.0:
             # per-pair convergence on the device: pairs in self.done are skipped by both launches (``run(conv_tol=...)``)
             self.cost_pass(level, 1, irls_eps, done=self.done)
@@ -563,15 +552,8 @@ class PairBatch:
                    "sp_pairs_gn_step")
         return self._costs
 
-    def adam_step(self, level=0, lr_kld=1e-3, lr_pose=1e-2, lr_aff=5e-3, fused=False):
+    def adam_step(self, level=0, lr_kld=1e-3, lr_pose=1e-2, lr_aff=5e-3):
         """One Adam iteration (reset-tangent flavour of the reference's tracking/mapping loops) of every pair."""
-        if fused:
-            assert not self.wave_flag and not self.table_flag, "the single-launch form has no wave-span / depth-table variant (PairBatch(depth_table=False))"
-            _lib.check(self.lib.sp_pairs_adam_iterate(_lib.ptr(self.desc[level]), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, self.M,
-                                                      self.max_N, _lib.ptr(self.partials), _lib.ptr(self.seg_partials), _lib.ptr(self.arrivals),
-                                                      float(lr_kld), float(lr_pose), float(lr_aff), _lib.ptr(self.adam_state),
-                                                      _lib.ptr(self._costs), _lib.stream_ptr()), "sp_pairs_adam_iterate")
-            return self._costs
         self.cost_pass(level, 0)
         return self.solve_adam(level, lr_kld, lr_pose, lr_aff)
 

@@ -34,7 +34,7 @@ def _call(arr, n):
 
 def test_multi_symbol_and_abi():
     L, lib = _lib()
-    assert L.SP_ABI_VERSION == 18 and lib.sp_abi_version() == 18
+    assert L.SP_ABI_VERSION == 19 and lib.sp_abi_version() == 19
     assert hasattr(ctypes.CDLL(L.LIB_PATH), "sp_chain_step_multi")
     assert not hasattr(ctypes.CDLL(L.LIB_PATH), "sp_chain_step")             # (since ABI 17: one sequence is the multi call at n_steps = 1)
     assert lib.sp_chain_multi_bytes() > 0

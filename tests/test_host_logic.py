@@ -21,9 +21,9 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == 18
-    # (ABI 18: sp_pairs_cost_opt is the one extended cost entry point)
-    for retired in ("sp_pairs_cost_active", "sp_pairs_cost_rd", "sp_pairs_cost_rd_active"):
+    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == 19
+    # (ABI 18: sp_pairs_cost_opt is the one extended cost entry point; ABI 19: no single-launch iterate forms)
+    for retired in ("sp_pairs_cost_active", "sp_pairs_cost_rd", "sp_pairs_cost_rd_active", "sp_pairs_adam_iterate", "sp_pairs_gn_iterate"):
         assert not hasattr(lib, retired), retired
     # argument counts of the ctypes table match the prototypes
     for name in declared:

@@ -9,7 +9,6 @@ from super_primitive_amd import _lib
 ap = argparse.ArgumentParser(); ap.add_argument("--pairs", type=int, default=96); ap.add_argument("--distinct", type=int, default=4)
 ap.add_argument("--tile-points", type=int, default=8192); ap.add_argument("--segments", type=int, default=64); a = ap.parse_args()
 dev = torch.device("cuda:0")
-a.no_depth_table = True          # (the single-launch forms timed below read log-depth tables)
 batch, _ = bench.build_batch(a, 0, dev)
 for _ in range(5): batch.gn_step(0)
 E = lambda: torch.cuda.Event(enable_timing=True)
@@ -35,8 +34,7 @@ c = np.median([r[0].elapsed_time(r[1]) for r in rows]) * 1e3; s = np.median([r[1
 print(f"Adam: cost kernel {c:.1f} us, solver {s:.1f} us")
 
 import itertools
-variants = (("GN fused", lambda: batch.gn_step(0, fused=True)), ("GN 2-launch", lambda: batch.gn_step(0, fused=False)),
-            ("Adam fused", lambda: batch.adam_step(0, fused=True)), ("Adam 2-launch", lambda: batch.adam_step(0, fused=False)))
+variants = (("GN", lambda: batch.gn_step(0)), ("Adam", lambda: batch.adam_step(0)))
 res = {n: [] for n, _ in variants}
 for rnd in range(4):
     for name, fn in variants:
