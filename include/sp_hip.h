@@ -1197,6 +1197,28 @@ typedef struct SpMapKeyframe {
 int sp_map_points(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int stride, const SpTrajAlign* align, int n_align, float* points,
                   float* colours, int32_t* kf_index, int32_t* seg_ids, long long total_rows, void* stream);
 
+/* sp_map_normals (sp_surfel.hip): the surface normal of every row of sp_map_points, in ONE launch, from the keyframes' own tables.  The
+ * records, the walk and the argument rules are sp_map_points': the caller passes the very records it built for that call, and row j of
+ * normals belongs to row j of points.  image, kld and kp_L are not read: a constant added to log-depth scales the surface about the
+ * camera centre, so the normal does not depend on the keypoint log-depth shift.
+ *     normals : (total_rows, 3) float32, unit length in the world, facing the keyframe's camera; (0, 0, 0) means "no normal"
+ * PRECONDITION on the tables: within a segment's table range seg_off[n] .. (n + 1 < N ? seg_off[n + 1] : P) the words pix & 0x7fffffff
+ * (row << 16 | col) are strictly increasing -- row-major order, the reference's nonzero order, what sp_table_fill writes.
+ * All arithmetic in float64 from the float32 inputs, every operation rounded on its own (no fma, no reciprocal), rounded to float32 once.
+ *   - Table point i = row * stride lies on pixel (r, c) of pix[i], in segment n; L(k) = float64(baseL[k]).
+ *   - Neighbours are looked up at stride 1 in segment n's range only: left / right are i - 1 / i + 1 if inside the range and on
+ *     (r, c - 1) / (r, c + 1); up / down are the table points of the range on (r - 1, c) / (r + 1, c) (a binary search each).
+ *   - Lu = (L(right) - L(left)) / 2 with both, L(right) - L(i) or L(i) - L(left) with one, 0 with none; Lv likewise from down and up.
+ *   - m = (-(fx Lu), -(fy Lv), (1 + (c - cx) Lu) + (r - cy) Lv): fx fy / d^2 times dp/du x dp/dv of p = d ((c - cx) / fx, (r - cy) / fy, 1),
+ *     d = exp(L + shift).  n_cam = -m / sqrt((m0 m0 + m1 m1) + m2 m2); m . ray = 1, so n_cam faces the camera.  If a component of m is
+ *     not finite the row is (0, 0, 0).
+ *   - n_w = R' n_cam, each row as (R'0 n0 + R'1 n1) + R'2 n2; R' is the pose's rotation, or with alignment record a the float64 product
+ *     a.rot_reanchor R, each entry as (a0 R0 + a1 R1) + a2 R2, never rounded to float32.  The scale does not enter.
+ * No atomics; two runs give the same bits.  Null kfs / normals, and sp_map_points' conditions on n_kf, stride, total_blocks, align /
+ * n_align and total_rows: SP_EINVAL. */
+int sp_map_normals(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int stride, const SpTrajAlign* align, int n_align, float* normals,
+                   long long total_rows, void* stream);
+
 /* sp_keyframe_depths: what each of n_kf keyframes of ONE size claims to see -- its own depth image and segment map, straight from its
  * table (the renderer cannot deliver them: x fx / z + cx does not give back the integer column exactly, and the truncation can land one
  * pixel to the left).
@@ -1261,6 +1283,34 @@ int sp_render_views(const float* points, const float* colours, long long Q, cons
  * SP_EINVAL.  Q > 2^31 - 2, V > 65535, V H W >= 2^31: SP_ELIMIT. */
 int sp_render_splats(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, float z_min,
                      const float* radii, int max_px, unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream);
+
+/* sp_render_surfels (sp_surfel.hip): sp_render_splats' depth buffer with an ORIENTED footprint per point: the depth of every covered
+ * pixel is taken on the point's tangent plane, so a slanted surface renders at its true depth.  The arguments, limits and error codes of
+ * sp_render_splats, plus
+ *     normals : (Q,3) float32 in the frame of the points (sp_map_normals'), required
+ *     cull    : 0 (two-sided) or 1 (a surfel seen from behind is dropped)
+ * Per (point, view) x, y, z (= p_c), u, v, ru, rv, the keep test and the clipped rectangle r0 .. r1 x c0 .. c1 exactly as sp_render_splats
+ * has them (the same device functions: coverage is identical).  Then, in float64, every operation rounded on its own:
+ *   - A normal is USABLE iff its three floats are finite and not all zero.  An unusable normal makes the point sp_render_splats' flat
+ *     splat: the key of float32(z) on every pixel of the rectangle, nothing more is tested.
+ *   - n_c = R^T n, each row as (a + b) + c (an exact identity pose leaves n_c = n, as it leaves p_c = p);  s = (n_c0 x + n_c1 y) + n_c2 z.
+ *   - cull = 1: a usable normal with s >= 0 drops the (point, view).  t below does not change with the sign of n.
+ *   - Pixel (r, c) of the rectangle: a = ((c + 0.5) - cx) / fx, b = ((r + 0.5) - cy) / fy -- the ray through the pixel's centre (the
+ *     renderer truncates: pixel c is [c, c + 1)) --, den = (n_c0 a + n_c1 b) + n_c2, t = s / den; a NaN t becomes z; then if t < z - h,
+ *     t = z - h, and if t > z + h, t = z + h, with h = 2 rad, rad = float64(radius) if that is >= 0, else 0 (a disc that reaches the
+ *     square's corners has radius sqrt(2) rad and cannot leave that depth range however it is tilted; a grazing plane cannot shoot a
+ *     pixel to infinity).  The pixel is contested iff t > z_min and t < inf, with mode 1's key of float32(t): the smallest float32(t)
+ *     wins, equal float32(t) goes to the highest index.
+ * keys are zeroed by the call; outputs as sp_render_splats (depth = the winner's float32(t)).  Consequences:
+ *   - all normals zero (or otherwise unusable): sp_render_splats, bit for bit on every pixel;
+ *   - all radii 0 (h = 0, t = z, the one pixel (trunc v, trunc u)): sp_render_views in mode 1, bit for bit on every pixel, for points
+ *     of finite z (a point at z = inf with a usable normal fails t < inf; the two other calls keep it).
+ * Integer atomic maxima: two runs give the same bits.
+ * Null points / views / keys / radii / normals (or colours with an image), Q, V, H or W <= 0, z_min negative or NaN, max_px outside
+ * 0 .. 16, cull outside {0, 1}: SP_EINVAL.  Q > 2^31 - 2, V > 65535, V H W >= 2^31: SP_ELIMIT.  Invalid beats too large. */
+int sp_render_surfels(const float* points, const float* colours, const float* normals, long long Q, const SpView* views, int V, int H, int W,
+                      float z_min, const float* radii, int max_px, int cull, unsigned long long* keys, uint8_t* image, float* depth,
+                      int32_t* index, void* stream);
 
 /* sp_map_consistency: every point of a map tested against V depth images -- the other keyframes' own (sp_keyframe_depths), or ground
  * truth -- in ONE launch: does the surface a view claims at the point's pixel agree with the point, does the view look straight

@@ -96,10 +96,12 @@ SIGNATURES = {
     "sp_depth_ingest": [P, I, I, I, F, F, I, I, I, I, I, I, P, P],
     "sp_traj_align": [P, P, P, I, I, I, P, P, P, P],
     "sp_map_points": [P, I, I, I, P, I, P, P, P, P, ctypes.c_longlong, P],
+    "sp_map_normals": [P, I, I, I, P, I, P, ctypes.c_longlong, P],
     "sp_keyframe_depths": [P, I, I, I, I, P, P, P, P],
     "sp_map_consistency": [P, P, ctypes.c_longlong, P, P, I, P, I, I, F, I, F, P, P],
     "sp_render_views": [P, P, ctypes.c_longlong, P, I, I, I, I, F, P, P, P, P, P],
     "sp_render_splats": [P, P, ctypes.c_longlong, P, I, I, I, F, P, I, P, P, P, P, P],
+    "sp_render_surfels": [P, P, P, ctypes.c_longlong, P, I, I, I, F, P, I, I, P, P, P, P, P],
     "sp_image_metrics": [P, P, P, I, I, I, P, P],
     "sp_depth_lift_blocks": [I, I, I],
     "sp_depth_lift": [P, P, P, P, I, I, I, F, P, P, P, P, P, P, P],

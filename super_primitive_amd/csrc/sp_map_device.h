@@ -1,4 +1,4 @@
-// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip): each idiom has its one definition here.
+// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip): each idiom has its one definition here.
 #pragma once
 #include "sp_device.h"
 
@@ -74,3 +74,89 @@ __device__ __forceinline__ int keyframe_of_block(const SpMapKeyframe* __restrict
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (kfs[mid].first_block <= block) lo = mid; else hi = mid; }
     return lo;
 }
+
+// the segment of table point i: the last one whose offset is at or before it
+__device__ __forceinline__ int map_point_segment(const SpMapKeyframe& kf, int i) {
+    int s0 = 0, s1 = kf.N;
+    while (s1 - s0 > 1) { const int mid = (s0 + s1) >> 1; if (kf.seg_off[mid] <= i) s0 = mid; else s1 = mid; }
+    while (s0 + 1 < kf.N && kf.seg_off[s0 + 1] <= i) ++s0;              // (empty segments share an offset with their successor)
+    return s0;
+}
+
+// ---- views: one record per view in float64, the projection, a footprint's half-width (sp_views.hip and sp_surfel.hip; the arithmetic
+// carries its own contraction pragma: every operation is rounded on its own whatever the including file allows) ----------------------
+constexpr int VIEW_CHUNK = 16;
+
+struct ViewD {
+    double Rt[9], t[3];                // R^T row major, t: p_c = R^T (p - t)
+    double fx, fy, cx, cy;
+    int ident, pad_;
+};
+
+__device__ __forceinline__ void view_setup(const SpView& v, ViewD& o) {
+    bool ident = true;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float e = v.pose[4 * c + r];
+            o.Rt[3 * r + c] = (double)e;
+            ident = ident && e == (r == c ? 1.f : 0.f);
+        }
+        const float t = v.pose[4 * r + 3];
+        o.t[r] = (double)t;
+        ident = ident && t == 0.f;
+    }
+    o.fx = (double)v.K[0]; o.fy = (double)v.K[4]; o.cx = (double)v.K[2]; o.cy = (double)v.K[5];
+    o.ident = ident ? 1 : 0;
+    o.pad_ = 0;
+}
+
+// The projection of one point into one view, shared by every kernel that projects (the contract of sp_render_views in include/sp_hip.h):
+// p_c = R^T (p - t), the three-term sums as (a + b) + c; an exact identity pose leaves the point untouched.
+__device__ __forceinline__ void camera_point(const ViewD& w, double px, double py, double pz, double& x, double& y, double& z) {
+#pragma clang fp contract(off)
+    x = px; y = py; z = pz;
+    if (!w.ident) {
+        const double d0 = px - w.t[0], d1 = py - w.t[1], d2 = pz - w.t[2];
+        x = (w.Rt[0] * d0 + w.Rt[1] * d1) + w.Rt[2] * d2;
+        y = (w.Rt[3] * d0 + w.Rt[4] * d1) + w.Rt[5] * d2;
+        z = (w.Rt[6] * d0 + w.Rt[7] * d1) + w.Rt[8] * d2;
+    }
+}
+
+// u = x fx / z + cx, v = y fy / z + cy: two IEEE divisions
+__device__ __forceinline__ void pixel_of(const ViewD& w, double x, double y, double z, double& u, double& v) {
+#pragma clang fp contract(off)
+    u = (x * w.fx) / z + w.cx;
+    v = (y * w.fy) / z + w.cy;
+}
+
+// the half-width of a footprint in pixels: anything that is not >= 0 (a negative or NaN radius, inf / inf) is a point
+__device__ __forceinline__ double half_width(double h, double cap) { return !(h >= 0.0) ? 0.0 : (h < cap ? h : cap); }
+
+// ---- the resolve pass of every depth buffer of keys (sp_render_views, sp_render_splats, sp_render_surfels): one definition here, one
+// static copy in every file that launches it and says so by defining SP_MAP_DEVICE_RESOLVE before this header ----------------------
+#ifdef SP_MAP_DEVICE_RESOLVE
+// grid ceil(V H W / 256), block SP_BLOCK
+static __global__ __launch_bounds__(SP_BLOCK) void k_render_resolve(const unsigned long long* __restrict__ keys, const float* __restrict__ colours,
+                                                             int n_pix, int mode, uint8_t* __restrict__ image, float* __restrict__ depth,
+                                                             int32_t* __restrict__ index) {
+    const long long at = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (at >= n_pix) return;
+    const unsigned long long k = keys[at];
+    const int idx = mode == 1 ? key_nearest_id(k) : key_highest_id_id(k);
+    const float d = mode == 1 ? key_nearest_z(k) : key_highest_id_z(k);
+    if (index) index[at] = idx;
+    if (depth) depth[at] = d;
+    if (image) {
+        uint8_t rgb[3] = {0, 0, 0};
+        if (idx >= 0) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) rgb[ch] = colour_u8(colours[3 * (size_t)idx + ch]);
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) image[3 * (size_t)at + ch] = rgb[ch];
+    }
+}
+#endif

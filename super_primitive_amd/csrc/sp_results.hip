@@ -213,14 +213,6 @@ __global__ __launch_bounds__(SP_BLOCK) void k_traj_align(const float* __restrict
     if (tid == 0) { rec.ate_scaled = sqrt(sq[0] / nd); rec.ate = sqrt(sq[1] / nd); }
 }
 
-// the segment of table point i: the last one whose offset is at or before it
-__device__ __forceinline__ int map_point_segment(const SpMapKeyframe& kf, int i) {
-    int s0 = 0, s1 = kf.N;
-    while (s1 - s0 > 1) { const int mid = (s0 + s1) >> 1; if (kf.seg_off[mid] <= i) s0 = mid; else s1 = mid; }
-    while (s0 + 1 < kf.N && kf.seg_off[s0 + 1] <= i) ++s0;              // (empty segments share an offset with their successor)
-    return s0;
-}
-
 // the camera-frame depth of table point i of segment n: one function for sp_map_points and sp_keyframe_depths
 __device__ __forceinline__ float map_point_depth(const SpMapKeyframe& kf, int i, int n) {
     return expf(kf.baseL[i] + (kf.kld[n] - kf.kp_L[n]));

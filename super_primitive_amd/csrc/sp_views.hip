@@ -23,7 +23,7 @@
 // Resolve pass: one thread per pixel decodes the winner: index (or -1), depth = float32 z (or 0), image = trunc(c * 255) from the exact
 // float64 product, clamped to 0 .. 255, NaN -> 0 (or 0, 0, 0).  Integer maxima commute: two runs give the same bits.
 //
-// sp_map_consistency.  The same projection (camera_point / pixel_of below, one pair of functions for every kernel here), no keys: one
+// sp_map_consistency.  The same projection (camera_point / pixel_of of sp_map_device.h, one pair of functions for every kernel), no keys: one
 // lane per point, 32 views per workgroup in LDS, and per seen (point, view) a gather of the (2 window + 1)^2 depths around its pixel
 // from the V depth images, which every workgroup re-reads (they stay in L2 / the Infinity Cache).  Each pair is one of agree, in front,
 // behind or unseen; three integer counters per point in registers, stored plainly when V fits one chunk, else added by integer
@@ -39,6 +39,7 @@
 // at block offset + rank: row-major order, image after image.  Point arithmetic in float64, every operation rounded on its own, rounded
 // to float32 once at the end:
 //     x = ((c - cx) d) / fx;   y = ((r - cy) d) / fy;   z = d;   world = ((T0 x + T1 y) + T2 z) + T3 per row (no pose: the point itself).
+#define SP_MAP_DEVICE_RESOLVE                       // this file launches k_render_resolve
 #include "sp_map_device.h"
 
 #pragma clang fp contract(off)
@@ -46,54 +47,6 @@
 static_assert(sizeof(SpView) == 100, "view records are part of the ABI");
 
 namespace {
-
-constexpr int VIEW_CHUNK = 16;
-
-struct ViewD {
-    double Rt[9], t[3];                // R^T row major, t: p_c = R^T (p - t)
-    double fx, fy, cx, cy;
-    int ident, pad_;
-};
-
-__device__ __forceinline__ void view_setup(const SpView& v, ViewD& o) {
-    bool ident = true;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float e = v.pose[4 * c + r];
-            o.Rt[3 * r + c] = (double)e;
-            ident = ident && e == (r == c ? 1.f : 0.f);
-        }
-        const float t = v.pose[4 * r + 3];
-        o.t[r] = (double)t;
-        ident = ident && t == 0.f;
-    }
-    o.fx = (double)v.K[0]; o.fy = (double)v.K[4]; o.cx = (double)v.K[2]; o.cy = (double)v.K[5];
-    o.ident = ident ? 1 : 0;
-    o.pad_ = 0;
-}
-
-// The projection of one point into one view, shared by every kernel of this file (the contract of sp_render_views in include/sp_hip.h):
-// p_c = R^T (p - t), the three-term sums as (a + b) + c; an exact identity pose leaves the point untouched.
-__device__ __forceinline__ void camera_point(const ViewD& w, double px, double py, double pz, double& x, double& y, double& z) {
-    x = px; y = py; z = pz;
-    if (!w.ident) {
-        const double d0 = px - w.t[0], d1 = py - w.t[1], d2 = pz - w.t[2];
-        x = (w.Rt[0] * d0 + w.Rt[1] * d1) + w.Rt[2] * d2;
-        y = (w.Rt[3] * d0 + w.Rt[4] * d1) + w.Rt[5] * d2;
-        z = (w.Rt[6] * d0 + w.Rt[7] * d1) + w.Rt[8] * d2;
-    }
-}
-
-// u = x fx / z + cx, v = y fy / z + cy: two IEEE divisions
-__device__ __forceinline__ void pixel_of(const ViewD& w, double x, double y, double z, double& u, double& v) {
-    u = (x * w.fx) / z + w.cx;
-    v = (y * w.fy) / z + w.cy;
-}
-
-// the half-width of a footprint in pixels: anything that is not >= 0 (a negative or NaN radius, inf / inf) is a point
-__device__ __forceinline__ double half_width(double h, double cap) { return !(h >= 0.0) ? 0.0 : (h < cap ? h : cap); }
 
 // the radii of a workgroup's points: LDS that only the footprint instantiation of k_view_keys has
 template <bool FOOTPRINT>
@@ -272,28 +225,6 @@ __global__ __launch_bounds__(SP_BLOCK) void k_image_metrics(const uint8_t* __res
     if (tid < 3) {
         const uint32_t sum = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
         if (sum) atomicAdd(out + 3 * (size_t)view + tid, (unsigned long long)sum);
-    }
-}
-
-// grid ceil(V H W / 256), block SP_BLOCK
-__global__ __launch_bounds__(SP_BLOCK) void k_render_resolve(const unsigned long long* __restrict__ keys, const float* __restrict__ colours,
-                                                             int n_pix, int mode, uint8_t* __restrict__ image, float* __restrict__ depth,
-                                                             int32_t* __restrict__ index) {
-    const long long at = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
-    if (at >= n_pix) return;
-    const unsigned long long k = keys[at];
-    const int idx = mode == 1 ? key_nearest_id(k) : key_highest_id_id(k);
-    const float d = mode == 1 ? key_nearest_z(k) : key_highest_id_z(k);
-    if (index) index[at] = idx;
-    if (depth) depth[at] = d;
-    if (image) {
-        uint8_t rgb[3] = {0, 0, 0};
-        if (idx >= 0) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) rgb[ch] = colour_u8(colours[3 * (size_t)idx + ch]);
-        }
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) image[3 * (size_t)at + ch] = rgb[ch];
     }
 }
 

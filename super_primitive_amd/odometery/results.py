@@ -10,6 +10,8 @@
 ``point_radii``       the size of the source pixels every map point stands for: the footprints that ``render_map`` / ``score_map`` /
                       ``score_map_images`` splat through the depth buffer (``sp_render_splats``), so a sparse map has no holes.
 ``score_map_images``  the map's rendered views against real images: PSNR, L1 and coverage from ``sp_image_metrics``' integer sums.
+                      With ``normals=True`` -- on a map made with ``normals=True``: one ``sp_map_normals`` launch over the same records --
+                      the three render every point as an oriented surfel (``sp_render_surfels``): slanted surfaces at their true depth.
 ``map_consistency``   every map point against V depth images -- the other keyframes' own, or ground truth: per point the views it
                       agrees with, floats in front of, is hidden behind (ONE ``sp_map_consistency`` launch); ``sequence_consistency`` is
                       the self-check of a sequence's map without ground truth, ``segment_consistency`` the verdict per (keyframe,
@@ -17,7 +19,7 @@
 ``fuse_map``          the map as a map: one averaged point per occupied voxel (ONE ``sp_map_fuse`` call), a world dict every function
                       above accepts; ``pool_map`` sums per-input-point integers (consistency counts) per fused point.
 ``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``.
-``write_ply``         the map's points and 8-bit colours as a binary PLY file."""
+``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -30,13 +32,15 @@ from ..lie.lie_algebra import pose_to_tq
 from ..tool import pose_utils
 
 
-def keyframe_points(kfs, klds, poses, stride=1, align=None, align_index=None):
+def keyframe_points(kfs, klds, poses, stride=1, align=None, align_index=None, normals=False):
     """kfs: keyframes (``KeyFrame`` with segments); klds: their keypoint log-depths; poses: their camera-to-world poses ((n,4,4) or a
     list); every ``stride``-th table point of each keyframe is reported, i.e. ``unproject_kf(kf, kld)['src_pts'][::stride]`` in the
     world.  ``align``: what ``pose_utils.align_trajectories`` returns (or its (S,32) record tensor); ``align_index``: per keyframe the
     record that moves it into the aligned frame, or -1 for none (default: record 0 for all when ``align`` is given).
     Returns dict(points (Q,3), colours (Q,3) float32, kf_index (Q,), seg_ids (Q,) int32 on the device, offsets: (n+1,) host integers --
-    keyframe k owns rows offsets[k] .. offsets[k+1])."""
+    keyframe k owns rows offsets[k] .. offsets[k+1]).  ``normals=True``: also ``normals`` (Q,3) float32, the unit surface normal of
+    every row in the world, facing its keyframe's camera, (0, 0, 0) where the table gives none -- a second launch (``sp_map_normals``)
+    over the same records."""
     from ..tool import viz
     n = len(kfs)
     if n == 0 or len(klds) != n or len(poses) != n:
@@ -61,17 +65,20 @@ def keyframe_points(kfs, klds, poses, stride=1, align=None, align_index=None):
                kf_index=torch.empty(total, dtype=torch.int32, device=dev), seg_ids=torch.empty(total, dtype=torch.int32, device=dev))
     _lib.check(lib.sp_map_points(_lib.ptr(recs_d), n, blocks, stride, _lib.ptr(record), n_align, _lib.ptr(out['points']), _lib.ptr(out['colours']),
                                  _lib.ptr(out['kf_index']), _lib.ptr(out['seg_ids']), total, _lib.stream_ptr()), "sp_map_points")
+    if normals:
+        out['normals'] = viz.keyframe_normals(recs_d, n, blocks, stride, total, record)
     out['offsets'] = np.asarray(offsets, dtype=np.int64)
     return out
 
 
-def sequence_map(result, stride, gt_poses=None, anchor_rotation=True):
+def sequence_map(result, stride, gt_poses=None, anchor_rotation=True, normals=False):
     """The world map of every keyframe a sequence created: ``result`` is what ``run_sequence`` / ``run_sequences`` returned with
     ``keep_keyframes=True``; the keyframes appear in frame order, each at its archived pose and log-depths.  ``gt_poses``: ground-truth
     camera-to-world poses indexed by frame id ((n_frames,4,4), a list or a dict): the keyframe trajectory is aligned against them at
     its own ids (``transfer_scale``'s alignment) and the map is moved into the ground truth's frame.
     Returns ``keyframe_points``' dict plus ``ids`` (frame id per keyframe) and, with ``gt_poses``, ``align`` (what
-    ``align_trajectories`` returns, one trajectory), ``traj_ids``, ``ate_scaled`` and ``ate`` (0-dim device tensors)."""
+    ``align_trajectories`` returns, one trajectory), ``traj_ids``, ``ate_scaled`` and ``ate`` (0-dim device tensors).  ``normals``: as in
+    ``keyframe_points``."""
     archive = result['kf_archive']
     ids = sorted(archive)
     if any(archive[i]['kf'] is None for i in ids):
@@ -85,7 +92,7 @@ def sequence_map(result, stride, gt_poses=None, anchor_rotation=True):
         align = pose_utils.align_trajectories(pred[None], gt[None], anchor_rotation=anchor_rotation)
         extra = dict(align=align, traj_ids=traj_ids, ate_scaled=align['ate_scaled'][0], ate=align['ate'][0])
     out = keyframe_points([archive[i]['kf'] for i in ids], [archive[i]['kld'] for i in ids], [archive[i]['pose'] for i in ids],
-                          stride=stride, align=align)
+                          stride=stride, align=align, normals=normals)
     out['ids'] = ids
     out.update(extra)
     return out
@@ -139,13 +146,24 @@ def point_radii(world, result, footprint=1.0):
     return ((float(footprint) / (2.0 * fx))[k] * depth).float()
 
 
-def render_map(world, Ks, poses, size, depth_buffer=True, radii=None, max_px=8):
+def _surfel_normals(world, normals, radii, what):
+    """``world['normals']`` for a render with ``normals=True`` (``ValueError`` if the world has none or ``radii`` is missing), else None."""
+    if not normals:
+        return None
+    if world.get('normals') is None or radii is None:
+        raise ValueError(f"{what}: normals=True needs world['normals'] (keyframe_points / sequence_map with normals=True) and radii")
+    return world['normals']
+
+
+def render_map(world, Ks, poses, size, depth_buffer=True, radii=None, max_px=8, normals=False, cull=False):
     """The map seen from V cameras in ONE ``sp_render_views`` launch (``tool.viz.render_views``): ``world`` is what ``keyframe_points`` or
     ``sequence_map`` returned (its ``points`` and ``colours``), ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world in the map's
     frame, ``size`` = (H, W).  ``depth_buffer=True``: the nearest point in front of the camera wins a pixel; False: the reference's
     ``render_pcd`` (the highest index wins, nothing is tested against z).  ``radii`` ((Q,) float32, ``point_radii``): every point is a
     square footprint of that half side, at most ``max_px`` pixels to either side (ONE ``sp_render_splats`` launch): a map sparser than
-    the view leaves no holes and the nearer surface hides the farther one.
+    the view leaves no holes and the nearer surface hides the farther one.  ``normals=True`` (with ``radii``; ``world['normals']``
+    must exist): every point is an oriented surfel (ONE ``sp_render_surfels`` launch), the depth of each covered pixel taken on its
+    tangent plane; ``cull=True`` drops surfels seen from behind.
     Returns dict(image (V,H,W,3) uint8, depth (V,H,W) float32 -- 0 where nothing landed --, index (V,H,W) int32 -- the winning row of
     ``world['points']``, -1 where nothing landed).  Per-pixel keyframe and segment maps follow from it:
     ``torch.where(index >= 0, world['kf_index'][index.clamp(min=0).long()], -1)``, and the same with ``world['seg_ids']``.
@@ -153,12 +171,13 @@ def render_map(world, Ks, poses, size, depth_buffer=True, radii=None, max_px=8):
     from ..tool import viz
     Ks, poses = _view_cameras(Ks, poses, "render_map")
     H, W = size
-    return viz.render_views(world['points'], world['colours'], Ks, poses, H, W, depth_buffer=depth_buffer, radii=radii, max_px=max_px)
+    return viz.render_views(world['points'], world['colours'], Ks, poses, H, W, depth_buffer=depth_buffer, radii=radii, max_px=max_px,
+                            normals=_surfel_normals(world, normals, radii, "render_map"), cull=cull)
 
 
-def score_map_images(world, images, Ks, poses, radii=None, max_px=8):
+def score_map_images(world, images, Ks, poses, radii=None, max_px=8, normals=False, cull=False):
     """The map's rendered views against real images: ``images`` (V,3,H,W) float32 in 0..1, ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4)
-    camera-to-world in the map's frame; ``radii`` / ``max_px`` as in ``render_map``.  One render launch (depth buffer) plus ONE
+    camera-to-world in the map's frame; ``radii`` / ``max_px`` / ``normals`` / ``cull`` as in ``render_map``.  One render launch (depth buffer) plus ONE
     ``sp_image_metrics`` launch; only pixels something landed on are compared, at 8 bits per channel.
     Returns dict(sums (V,3) int64 -- n, sum |a - b|, sum (a - b)^2 over the compared pixels' three channels --, psnr (V,) float64 =
     10 log10(255^2 3n / sum d^2) (NaN for n = 0, inf for identical pixels), l1 (V,) float64 in 0..255 = sum |a - b| / 3n (NaN for
@@ -170,13 +189,14 @@ def score_map_images(world, images, Ks, poses, radii=None, max_px=8):
                          f"{tuple(images.shape) if torch.is_tensor(images) else type(images).__name__}")
     H, W = int(images.shape[2]), int(images.shape[3])
     _lib.require_device(images, world['points'])
-    out = viz.render_views(world['points'], world['colours'], Ks, poses, H, W, depth_buffer=True, depth=False, radii=radii, max_px=max_px)
+    out = viz.render_views(world['points'], world['colours'], Ks, poses, H, W, depth_buffer=True, depth=False, radii=radii, max_px=max_px,
+                           normals=_surfel_normals(world, normals, radii, "score_map_images"), cull=cull)
     sums = viz.image_metrics(out['image'], images, out['index'])
     n3, s1, s2 = 3.0 * sums[:, 0].double(), sums[:, 1].double(), sums[:, 2].double()
     return dict(sums=sums, psnr=10.0 * torch.log10(255.0 ** 2 * n3 / s2), l1=s1 / n3, coverage=sums[:, 0].double() / float(H * W))
 
 
-def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size=None, radii=None, max_px=8):
+def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size=None, radii=None, max_px=8, normals=False, cull=False):
     """The map against ground-truth depth images: its depth buffer is rendered into each of the V ground-truth views (``render_map``'s
     launch, depth only) and scored where it landed.  ``gt_depths`` (V,H,W) float32, ``Ks`` (V,3,3) or (3,3), ``gt_poses`` (V,4,4)
     camera-to-world; the map should already be in the ground truth's frame, as ``sequence_map(gt_poses=...)`` delivers it.
@@ -184,7 +204,8 @@ def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size
     Returns dict(metrics (V,12) float64 on the device, columns: the names of its columns (``depth_completion.void``: n, rmse, mae, absrel
     in mm, inv_rmse, inv_mae, inv_absrel in 1/km, delta105, delta110, delta1, delta2, delta3), coverage (V,) float64 = scored pixels /
     pixels with ``min_depth <= gt <= max_depth`` (NaN for a view without any)).  ``size``: an (H, W) the depths must have, if given.
-    ``radii`` / ``max_px``: the footprints of ``render_map``, so that a sparse map is scored on every pixel its surfaces cover.
+    ``radii`` / ``max_px``: the footprints of ``render_map``, so that a sparse map is scored on every pixel its surfaces cover;
+    ``normals`` / ``cull``: its oriented surfels, so that the score carries no error of a flat splat on a slanted surface.
     No synchronisation."""
     from ..depth_completion import void
     from ..tool import viz
@@ -199,7 +220,7 @@ def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size
         raise ValueError(f"score_map: size {tuple(size)} against ground-truth depths of {H}x{W}")
     _lib.require_device(gt_depths, world['points'])
     depth = viz.render_views(world['points'], None, Ks, gt_poses, H, W, depth_buffer=True, image=False, index=False, radii=radii,
-                             max_px=max_px)['depth']
+                             max_px=max_px, normals=_surfel_normals(world, normals, radii, "score_map"), cull=cull)['depth']
     in_range = (gt_depths >= min_depth) & (gt_depths <= max_depth)
     scored = in_range & (depth > 0)
     metrics = void.depth_metrics(depth, gt_depths, scored)
@@ -281,6 +302,7 @@ def segment_consistency(world, consistency, n_segments=None):
 
 
 _PER_POINT = ('points', 'colours', 'kf_index', 'seg_ids')
+_NORMAL_SCALE = 2.0 ** 20          # fuse_map: member normals are summed as int32 round(n * 2^20)
 
 
 def _check_world(world, what):
@@ -293,12 +315,16 @@ def _check_world(world, what):
     if any(int(world[k].shape[0]) != Q for k in _PER_POINT) or int(np.asarray(world['offsets'])[-1]) != Q:
         raise ValueError(f"{what}: {[(k, int(world[k].shape[0])) for k in _PER_POINT]} rows and offsets ending at "
                          f"{int(np.asarray(world['offsets'])[-1])} for {Q} points")
+    nrm = world.get('normals')
+    if nrm is not None and (not torch.is_tensor(nrm) or nrm.dtype != torch.float32 or tuple(nrm.shape) != (Q, 3)):
+        raise ValueError(f"{what}: world['normals'] must be a float32 tensor ({Q},3)")
     return Q
 
 
 def filter_map(world, consistency, min_agree=1, max_in_front=None):
     """The map a user would export: the rows of ``world`` with ``agree >= min_agree`` -- and ``in_front <= max_in_front`` if given --,
-    in their order.  Returns a new dict: ``points``, ``colours``, ``kf_index``, ``seg_ids`` compacted, ``offsets`` recomputed (host
+    in their order.  Returns a new dict: ``points``, ``colours``, ``kf_index``, ``seg_ids`` (and ``normals``, if the world has them)
+    compacted, ``offsets`` recomputed (host
     integers, as ``keyframe_points`` returns them), ``kept`` (int64, on the device: the surviving rows of ``world``); every other entry
     (``ids``, ``align``, the ATE fields) is carried over.  ``world`` must hold all four per-point tensors, of one length, and ``offsets``
     ending at that length (``ValueError`` otherwise).  Sizing the output takes ONE host read -- the new offsets, n_kf + 1 integers;
@@ -320,7 +346,7 @@ def filter_map(world, consistency, min_agree=1, max_in_front=None):
     dest = torch.where(keep, rank - 1, torch.full_like(rank, total))                   # (dropped rows all go to one spare slot)
     kept = torch.empty(total + 1, dtype=torch.int64, device=dev).scatter_(0, dest, torch.arange(Q, dtype=torch.int64, device=dev))[:total]
     out = {k: v for k, v in world.items() if k not in _PER_POINT and k != 'offsets'}
-    for k in _PER_POINT:
+    for k in _PER_POINT + (('normals',) if world.get('normals') is not None else ()):
         out[k] = world[k][kept]
     out['offsets'] = offsets
     out['kept'] = kept
@@ -338,7 +364,9 @@ def fuse_map(world, voxel, origin=None):
     2^20 voxels from the origin) and ``offsets`` recomputed (host integers); every other entry (``ids``, ``align``, the ATE fields) is
     carried over.  ``render_map``, ``score_map``, ``score_map_images``, ``map_consistency`` and ``filter_map`` accept the result as it
     is (``filter_map`` compacts the four per-point tensors; ``count``, ``first`` and ``label`` then still describe the unfiltered
-    fused map).  The footprint of a fused point is its voxel: ``radii = torch.full((M,), voxel / 2)``.  ``world`` is validated as
+    fused map).  With ``world['normals']`` the result has ``normals`` (M,3): per fused point the normalised sum of its members' normals
+    (``fused_normals``: integer sums, two runs give the same bits; opposite members cancel to (0, 0, 0), "no normal").  The footprint
+    of a fused point is its voxel: ``radii = torch.full((M,), voxel / 2)``.  ``world`` is validated as
     ``filter_map`` does (``ValueError``).  Sizing the output takes ONE host read -- the new offsets, n_kf + 1 integers from
     ``torch.searchsorted(first, old_offsets)``, the last of which is M."""
     from ..tool import viz
@@ -354,7 +382,33 @@ def fuse_map(world, voxel, origin=None):
     out = {k: v for k, v in world.items() if k not in _PER_POINT and k != 'offsets'}
     out.update(points=fused['points'][:M], colours=fused['colours'][:M], kf_index=world['kf_index'][first.long()],
                seg_ids=world['seg_ids'][first.long()], count=fused['count'][:M], first=first, label=fused['label'], offsets=offsets)
+    if world.get('normals') is not None:
+        out['normals'] = fused_normals(world['normals'], fused['label'], M)
     return out
+
+
+def _pool(label, M, values):
+    """``pool_map``'s sum: ``values`` (Q,) or (Q,k) integers added per ``label`` (Q,) into int64 (M,) or (M,k); label -1 counts nowhere."""
+    lab = label.long()
+    key = torch.where(lab >= 0, lab, torch.full_like(lab, M))                          # (one row beyond the map takes the dropped rows)
+    out = torch.zeros((M + 1,) + tuple(values.shape[1:]), dtype=torch.int64, device=values.device).index_add_(0, key, values.long())
+    return out[:M]
+
+
+def fused_normals(normals, label, M):
+    """The normal of every fused point: ``normals`` (Q,3) float32 of the members, ``label`` (Q,) their fused rows (-1: dropped), ``M``
+    fused points.  Each component is quantised to int32 ``round(n * 2^20)`` (float64 product, ties to even; a non-finite component
+    counts as 0), summed per fused point by ``pool_map``'s integer ``index_add_`` -- exact in any order, so two runs give the same bits
+    --, and the sum S is normalised in float64: ``S / sqrt((S0 S0 + S1 S1) + S2 S2)``, rounded to float32 once; a zero sum stays
+    (0, 0, 0).  Runs on CPU tensors too.  No host read."""
+    if not torch.is_tensor(normals) or normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[1] != 3 \
+            or tuple(label.shape) != (normals.shape[0],):
+        raise ValueError("fused_normals: normals must be float32 (Q,3) with one label per row")
+    q = torch.round(torch.nan_to_num(normals.detach().double(), nan=0.0, posinf=0.0, neginf=0.0) * _NORMAL_SCALE).to(torch.int32)
+    S = _pool(label.to(q.device), int(M), q).double()                                  # (|S| <= members * 2^20: exact in float64)
+    length = torch.sqrt((S[:, 0] * S[:, 0] + S[:, 1] * S[:, 1]) + S[:, 2] * S[:, 2])
+    unit = S / torch.where(length > 0, length, torch.ones_like(length))[:, None]
+    return unit.float()
 
 
 def pool_map(fused, values):
@@ -368,25 +422,29 @@ def pool_map(fused, values):
             or values.shape[0] != label.shape[0]:
         raise ValueError(f"pool_map: values must be integers of shape ({label.shape[0]},) or ({label.shape[0]},k), got "
                          f"{(values.dtype, tuple(values.shape)) if torch.is_tensor(values) else type(values).__name__}")
-    lab = label.long()
-    key = torch.where(lab >= 0, lab, torch.full_like(lab, M))                          # (one row beyond the map takes the dropped rows)
-    out = torch.zeros((M + 1,) + tuple(values.shape[1:]), dtype=torch.int64, device=values.device).index_add_(0, key, values.long())
-    return out[:M]
+    return _pool(label, M, values)
 
 
 def write_ply(path, world):
     """``world['points']`` (M,3) float32 and ``world['colours']`` (M,3) float32 in 0..1 as a binary little-endian PLY file: per vertex
     ``x y z`` float32 and ``red green blue`` uchar, the colours by the renderer's 8-bit rule (trunc(c * 255) from the float64 product,
-    clamped to 0 .. 255, NaN gives 0).  Device tensors come to the host in one copy of 15 bytes per point; CPU tensors work too.
-    Returns the path."""
+    clamped to 0 .. 255, NaN gives 0).  With ``world['normals']`` (M,3) float32 the vertex is ``x y z nx ny nz`` float32 and ``red green
+    blue`` uchar; without, the file is what it always was.  Device tensors come to the host in one copy of 15 (27) bytes per point; CPU
+    tensors work too.  Returns the path."""
     points, colours = world.get('points'), world.get('colours')
     if not torch.is_tensor(points) or not torch.is_tensor(colours) or points.dtype != torch.float32 or colours.dtype != torch.float32 \
             or points.dim() != 2 or points.shape[1] != 3 or tuple(colours.shape) != tuple(points.shape) or points.device != colours.device:
         raise ValueError("write_ply: world needs float32 points (M,3) and colours (M,3) on one device")
     M = int(points.shape[0])
+    normals = world.get('normals')
+    if normals is not None and (not torch.is_tensor(normals) or normals.dtype != torch.float32 or tuple(normals.shape) != (M, 3)
+                                or normals.device != points.device):
+        raise ValueError("write_ply: world['normals'] must be float32 (M,3) on the points' device")
     rgb = torch.nan_to_num(colours.detach().double() * 255.0, nan=0.0).clamp(0.0, 255.0).to(torch.uint8)
-    rows = torch.cat((points.detach().contiguous().view(torch.uint8).reshape(M, 12), rgb), dim=1).cpu().numpy()   # the one copy
+    floats = [points] if normals is None else [points, normals]
+    rows = torch.cat([t.detach().contiguous().view(torch.uint8).reshape(M, 12) for t in floats] + [rgb], dim=1).cpu().numpy()   # the one copy
     header = ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {M}\n" + "property float x\nproperty float y\nproperty float z\n"
+              + ("" if normals is None else "property float nx\nproperty float ny\nproperty float nz\n") +
               "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
     if np.little_endian is False:                                                      # (the float bytes above are the host's)
         raise ValueError("write_ply: a big-endian host")

@@ -7,8 +7,10 @@ matplotlib is imported):
                        ``depth_scale=1, depth_trunc=100, stride=1``, then ``transform(T)``).  Returns tensors, not an Open3D object.
 ``lift_depth_images``  the batched lift without a synchronisation.
 ``render_views``       the call under ``render_pcd`` and ``odometery.results.render_map``: V posed views of one point set per launch;
-                       with ``radii`` every point is a square footprint (``sp_render_splats``): no holes where the map is sparser than the view.
+                       with ``radii`` every point is a square footprint (``sp_render_splats``): no holes where the map is sparser than the view;
+                       with ``normals`` on top an oriented surfel (``sp_render_surfels``): a slanted surface renders at its true depth.
 ``image_metrics``      rendered views against real images: exact integer sums per view (``sp_image_metrics``).
+``keyframe_normals``   the surface normal of every row of an ``sp_map_points`` launch, from the same records (``sp_map_normals``).
 ``keyframe_depths``    what each keyframe claims to see: its own depth image and segment map, from its table (``sp_keyframe_depths``).
 ``map_consistency``    every point against V depth images: agree / in front / behind counts per point (``sp_map_consistency``).
 ``fuse_points``        one averaged point per occupied voxel of a point set (``sp_map_fuse``).
@@ -79,14 +81,16 @@ def _limits(what, V, H, W, Q=0, views="views"):
 
 
 def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_MIN, image=True, depth=True, index=True, radii=None,
-                 max_px=8):
+                 max_px=8, normals=None, cull=False):
     """ONE ``sp_render_views`` launch (include/sp_hip.h has the arithmetic): ``points`` (Q,3) float32 in the world, ``colours`` (Q,3)
     float32 in 0..1 (None allowed without ``image``), ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world.  Returns the requested
     of ``image`` (V,H,W,3) uint8, ``depth`` (V,H,W) float32 (0 where nothing landed) and ``index`` (V,H,W) int32 (-1 there) as a dict.
     ``radii`` (Q,) float32 in world units: ONE ``sp_render_splats`` launch instead -- every point covers the pixels its square footprint
     of that half side touches, at most ``max_px`` (0 .. 16) pixels to either side, through the depth buffer (``depth_buffer`` must be
-    true).  No synchronisation."""
-    _on_device(points, colours, Ks, poses, radii)
+    true).  ``normals`` (Q,3) float32 in the frame of the points (``radii`` required): ONE ``sp_render_surfels`` launch -- the depth of
+    every covered pixel is taken on the point's tangent plane, clamped to ``z -+ 2 radius``; a zero or non-finite normal is a flat
+    footprint; ``cull=True`` drops surfels seen from behind.  No synchronisation."""
+    _on_device(points, colours, Ks, poses, radii, normals)
     H, W = _size(H, W)
     if poses.dim() != 3:
         raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
@@ -107,6 +111,13 @@ def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_M
         rad = _f32(radii, (Q,), "radii")
         if int(max_px) != max_px or not 0 <= int(max_px) <= 16:
             raise ValueError(f"render_views: max_px {max_px} (0 .. 16)")
+    nrm = None
+    if normals is not None:
+        if rad is None:
+            raise ValueError("render_views: normals need radii (a surfel is an oriented footprint) and depth_buffer=True")
+        nrm = _f32(normals, (Q, 3), "normals")
+    elif cull:
+        raise ValueError("render_views: cull needs normals")
     _limits("render_views", V, H, W, Q)
     lib = _lib.load()
     dev = pts.device
@@ -118,6 +129,11 @@ def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_M
         out['depth'] = torch.empty(V, H, W, dtype=torch.float32, device=dev)
     if index:
         out['index'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    if nrm is not None:
+        _lib.check(lib.sp_render_surfels(_lib.ptr(pts), _lib.ptr(cols), _lib.ptr(nrm), Q, _lib.ptr(views), V, H, W, float(z_min), _lib.ptr(rad),
+                                         int(max_px), 1 if cull else 0, _lib.ptr(keys), _lib.ptr(out.get('image')), _lib.ptr(out.get('depth')),
+                                         _lib.ptr(out.get('index')), _lib.stream_ptr()), "sp_render_surfels")
+        return out
     if rad is not None:
         _lib.check(lib.sp_render_splats(_lib.ptr(pts), _lib.ptr(cols), Q, _lib.ptr(views), V, H, W, float(z_min), _lib.ptr(rad), int(max_px),
                                         _lib.ptr(keys), _lib.ptr(out.get('image')), _lib.ptr(out.get('depth')), _lib.ptr(out.get('index')),
@@ -248,6 +264,19 @@ def keyframe_records(what, kfs, klds, stride=1, poses=None, align_index=None):
         offsets.append(offsets[k] + q)
         block += (q + _BLOCK - 1) // _BLOCK
     return torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(rows[0][1].device), [poses, rows], offsets, block
+
+
+def keyframe_normals(recs_d, n, blocks, stride, total, record=None):
+    """ONE ``sp_map_normals`` launch (include/sp_hip.h has the arithmetic) over the records of ``keyframe_records(..., poses=...)``:
+    ``recs_d`` and ``blocks`` as it returned them for ``n`` keyframes at ``stride``, ``total`` its last row offset, ``record`` the (S,32)
+    float64 alignment records or None -- the arguments of the ``sp_map_points`` launch whose rows these normals belong to.  What the
+    records point at must still be alive.  Returns (total,3) float32 on the device: unit normals in the world that face their
+    keyframe's camera, (0, 0, 0) where the table gives none.  No synchronisation."""
+    lib = _lib.load()
+    normals = torch.empty(total, 3, dtype=torch.float32, device=recs_d.device)
+    _lib.check(lib.sp_map_normals(_lib.ptr(recs_d), n, blocks, stride, _lib.ptr(record), 0 if record is None else int(record.shape[0]),
+                                  _lib.ptr(normals), total, _lib.stream_ptr()), "sp_map_normals")
+    return normals
 
 
 def keyframe_depths(kfs, klds):
