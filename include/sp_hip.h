@@ -1405,6 +1405,55 @@ int sp_map_fuse_scratch_units(long long Q);
 int sp_map_fuse(const float* points, const float* colours, long long Q, float voxel, float ox, float oy, float oz, void* scratch,
                 float* out_points, float* out_colours, int32_t* count, int32_t* first, int32_t* label, long long* n_fused, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Map distances (sp_nearest.hip): for every point of one cloud the nearest point of another within a radius, and the number of points
+ * within it.  The map against a ground-truth cloud gives accuracy, the cloud against the map completion; a cloud against itself its
+ * spacing and the neighbour count a radius outlier filter keeps points by.  sp_cloud_grid_build prepares the REFERENCE cloud once,
+ * sp_cloud_grid_nearest answers any number of query clouds from it.  Everything runs on the caller's stream without a synchronisation
+ * and without an allocation; argument checks come before any device work.
+ *     points      : (Q,3) float32, the reference cloud;  queries : (Qa,3) float32
+ *     radius      : the search radius, a finite float32 > 0;  ox, oy, oz : the origin o of the ranges below, finite float32
+ *     scratch     : sp_cloud_grid_scratch_units(Q) units of 64 bytes, aligned to 16 bytes, initialised by the build.  The query reads
+ *                   radius and origin from it: a query cannot be run with a radius other than the build's.  It is given the Q of the
+ *                   build; a scratch that was built for another Q answers "none" on every row
+ *     skip_self   : 0 or 1.  1: the queries ARE the reference cloud (the caller passes the same cloud twice, Qa == Q) and row i is
+ *                   not its own neighbour
+ *     index, count : (Qa,) int32;  dist : (Qa,) float32 -- ALL THREE WRITTEN FOR EVERY QUERY ROW
+ * In float64 from the float32 inputs, every operation rounded on its own (no fma, no reciprocal):
+ *     r = float64(radius),  r2 = r * r,  cell = r * 1.0009765625                                  (1 + 2^-10; each product rounded once)
+ *     per axis a of a point p of either cloud:  q = (p_a - o_a) / cell,  g = floor(q).
+ * A point is IN RANGE iff all three q are finite and all three g lie in -2^20 + 1 .. 2^20 - 2; the test is made on the float64 value,
+ * before any conversion to an integer.  A reference point out of range (NaN and +-inf among them) is never found as a neighbour; a
+ * query out of range gets the "none" answer.
+ *     d2(i, j) = (dx dx + dy dy) + dz dz,  dx = float64(a_x) - float64(b_x) and so on, for query a = i and reference b = j.
+ * The NEIGHBOURS of query i are the reference rows j in range with d2(i, j) <= r2; with skip_self = 1 the row j == i is left out.
+ *     count[i] = their number;
+ *     index[i] = the neighbour with the smallest (d2, j) in lexicographic order: on equal distance the lowest row wins;
+ *     dist[i]  = float32(sqrt(d2)): the square root in float64, correctly rounded, then rounded to float32;
+ *     with no neighbour index[i] = -1, dist[i] = +inf, count[i] = 0.
+ * A minimum over (d2, j) and a count do not depend on the order in which candidates are visited: two runs give the same bits.
+ * Why the search is local.  The reference rows are binned by (gx, gy, gz) and a query looks into the 27 bins around its own.  Take a
+ * query a and an in-range reference row b with computed d2 <= r2.  Per axis the computed dx dx is no larger than the computed sum (a
+ * rounded sum of non-negative terms is no smaller than any of them), so |a - b| <= r (1 + 2^-51).  t = p_a - o_a as computed lies
+ * within 2^-53 |t| of the exact difference, and |t| / cell < 2^20 + 1 in range; the computed quotient lies within 2^-33 of t / cell.
+ * So the two computed quotients differ by at most r (1 + 2^-51) / cell + 2^-31 < 1 - 2^-11 + 2^-31 < 1, because cell exceeds r by
+ * the factor 1 + 2^-10.  Two numbers less than 1 apart have floors at most 1 apart: every neighbour lies in one of the 27 bins,
+ * whatever the origin, and the bins around an in-range query have indices in -2^20 .. 2^20 - 1, which the 21-bit fields of the key hold.
+ * The prepared form: a 64-byte header (r2, cell, origin, table mask, Q); S slots of 16 bytes -- a bin's 64-bit key (sp_map_fuse's),
+ * where its members start and how many they are --, S the smallest power of two >= 2 Q, open addressing with linear probing (load <=
+ * 0.5); Q records of 16 bytes {x, y, z, row}, the members of one bin side by side; Q slot numbers and ceil(S / 256) block sums.  Five
+ * launches after the table's initialisation (count per bin, sum per 256 slots, scan, starts, scatter through an atomic cursor); the
+ * query is one launch, one lane per query.  No workgroup waits on another and every loop is bounded.
+ * Null points / queries / scratch / index / dist / count, a scratch not aligned to 16 bytes, Q or Qa <= 0, skip_self outside {0, 1},
+ * skip_self = 1 with Qa != Q, radius not finite or not > 0, a non-finite origin: SP_EINVAL.  Q > 2^28 (SP_CLOUD_GRID_MAX_POINTS: slot
+ * numbers, record places and the scratch size in units stay below 2^31) or Qa > 2^31 - 2: SP_ELIMIT.  Invalid beats too large.
+ * sp_cloud_grid_scratch_units answers Q <= 0 and Q > 2^28 with the same codes. */
+#define SP_CLOUD_GRID_MAX_POINTS (1LL << 28)
+int sp_cloud_grid_scratch_units(long long Q);
+int sp_cloud_grid_build(const float* points, long long Q, float radius, float ox, float oy, float oz, void* scratch, void* stream);
+int sp_cloud_grid_nearest(const float* queries, long long Qa, long long Q, const void* scratch, int skip_self, int32_t* index, float* dist,
+                          int32_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

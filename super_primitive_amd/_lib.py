@@ -107,6 +107,9 @@ SIGNATURES = {
     "sp_depth_lift": [P, P, P, P, I, I, I, F, P, P, P, P, P, P, P],
     "sp_map_fuse_scratch_units": [ctypes.c_longlong],
     "sp_map_fuse": [P, P, ctypes.c_longlong, F, F, F, F, P, P, P, P, P, P, P, P],
+    "sp_cloud_grid_scratch_units": [ctypes.c_longlong],
+    "sp_cloud_grid_build": [P, ctypes.c_longlong, F, F, F, F, P, P],
+    "sp_cloud_grid_nearest": [P, ctypes.c_longlong, ctypes.c_longlong, P, I, P, P, P, P],
 }
 
 SP_ABI_VERSION = 19
@@ -280,6 +283,7 @@ class SpMapKeyframe(ctypes.Structure):
 
 SP_VIEW_FLOATS = 25
 SP_MAP_FUSE_MAX_POINTS = 1 << 28
+SP_CLOUD_GRID_MAX_POINTS = 1 << 28
 
 
 class SpView(ctypes.Structure):

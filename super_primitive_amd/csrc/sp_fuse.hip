@@ -36,14 +36,7 @@ struct FuseSlot {
 };
 static_assert(sizeof(FuseSlot) == 64, "one slot is one 64-byte line");
 
-constexpr unsigned long long FUSE_EMPTY = ~0ull;
-constexpr double FUSE_HALF_RANGE = 1048576.0;              // 2^20 voxels to either side of the origin
-
-__device__ __forceinline__ unsigned long long fuse_mix(unsigned long long x) {       // splitmix64's finaliser
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
+// (the empty key, the hash, the key of three cells and the probe loop are sp_map_device.h's: sp_nearest.hip builds its table from them too)
 
 // one axis of a point: false = dropped; else the biased voxel index (0 .. 2^21 - 1) and the sub-voxel position (0 .. 65535)
 __device__ __forceinline__ bool fuse_axis(float p, double o, double voxel, unsigned long long& cell, unsigned long long& sub) {
@@ -77,17 +70,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_fuse_insert(const float* __restric
     const bool kept = in && fuse_axis(points[3 * at_i], (double)ox, vx, cx, s[0]) && fuse_axis(points[3 * at_i + 1], (double)oy, vx, cy, s[1]) &&
                       fuse_axis(points[3 * at_i + 2], (double)oz, vx, cz, s[2]);
     int32_t slot = -1;
-    if (kept) {
-        const unsigned long long key = (cx << 42) | (cy << 21) | cz;
-        unsigned int h = (unsigned int)fuse_mix(key) & mask;
-        for (unsigned int probe = 0; probe <= mask; ++probe) {                       // at most S slots
-            unsigned long long* at = &table[h].key;
-            unsigned long long cur = __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == FUSE_EMPTY) cur = atomicCAS(at, FUSE_EMPTY, key);             // (returns what it found: empty = claimed now)
-            if (cur == FUSE_EMPTY || cur == key) { slot = (int32_t)h; break; }
-            h = (h + 1u) & mask;
-        }
-    }
+    if (kept) slot = fuse_claim(table, mask, fuse_key(cx, cy, cz));
     if (in) slot_of[i] = slot;
     // what this point adds: 1, its three sub-voxel positions, its three 8-bit colours
     uint32_t v[7] = {1u, (uint32_t)s[0], (uint32_t)s[1], (uint32_t)s[2], 0u, 0u, 0u};

@@ -1,4 +1,4 @@
-// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip): each idiom has its one definition here.
+// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip): each idiom has its one definition here.
 #pragma once
 #include "sp_device.h"
 
@@ -66,6 +66,37 @@ __device__ __forceinline__ long long block_count_scan(int32_t* __restrict__ bc, 
         run += c;
     }
     return part[SP_BLOCK - 1];
+}
+
+// ---- hashed cell tables (sp_fuse.hip, sp_nearest.hip): 64-bit keys of three biased 21-bit cell indices, open addressing with linear
+// probing from a splitmix64 finaliser of the key (the cells of one surface are neighbours: the identity would cluster) ---------------
+constexpr unsigned long long FUSE_EMPTY = ~0ull;           // no key: keys use 63 bits
+constexpr double FUSE_HALF_RANGE = 1048576.0;              // 2^20 cells to either side of the origin
+
+__device__ __forceinline__ unsigned long long fuse_mix(unsigned long long x) {       // splitmix64's finaliser
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ unsigned long long fuse_key(unsigned long long cx, unsigned long long cy, unsigned long long cz) {
+    return (cx << 42) | (cy << 21) | cz;
+}
+
+// The slot of `key` in a table of mask + 1 slots whose first member is the 64-bit key (FUSE_EMPTY until claimed): found, or claimed by
+// a 64-bit atomicCAS after a relaxed load (most points find their key already there).  At most mask + 1 probes; a table that holds
+// fewer keys than slots cannot exhaust them -- should it ever, the answer is -1, not a loop.
+template <class Slot>
+__device__ __forceinline__ int32_t fuse_claim(Slot* __restrict__ table, unsigned int mask, unsigned long long key) {
+    unsigned int h = (unsigned int)fuse_mix(key) & mask;
+    for (unsigned int probe = 0; probe <= mask; ++probe) {                           // at most S slots
+        unsigned long long* at = &table[h].key;
+        unsigned long long cur = __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == FUSE_EMPTY) cur = atomicCAS(at, FUSE_EMPTY, key);                 // (returns what it found: empty = claimed now)
+        if (cur == FUSE_EMPTY || cur == key) return (int32_t)h;
+        h = (h + 1u) & mask;
+    }
+    return -1;
 }
 
 // ---- the keyframe walk: a workgroup belongs to ONE keyframe, the last record whose first_block is at or before it (uniform: scalar loads)

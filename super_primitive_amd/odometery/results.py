@@ -18,6 +18,10 @@
                       segment), ``filter_map`` the map with the unconfirmed points taken out.
 ``fuse_map``          the map as a map: one averaged point per occupied voxel (ONE ``sp_map_fuse`` call), a world dict every function
                       above accepts; ``pool_map`` sums per-input-point integers (consistency counts) per fused point.
+``map_distance``      the map against a reference CLOUD (lifted ground-truth depths) in 3D: per point the nearest point of the other cloud
+                      within a radius, both ways (``sp_cloud_grid_build`` / ``sp_cloud_grid_nearest``), and ``cloud_metrics`` of the two
+                      distance vectors: accuracy, completion, precision, recall, F-score; ``map_neighbours`` is the map against itself:
+                      its spacing and the neighbour count a radius outlier filter keeps points by.
 ``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``.
 ``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file."""
 from __future__ import annotations
@@ -423,6 +427,84 @@ def pool_map(fused, values):
         raise ValueError(f"pool_map: values must be integers of shape ({label.shape[0]},) or ({label.shape[0]},k), got "
                          f"{(values.dtype, tuple(values.shape)) if torch.is_tensor(values) else type(values).__name__}")
     return _pool(label, M, values)
+
+
+def _threshold(radius, threshold, what):
+    """(radius, threshold) as floats, the threshold defaulting to the radius; a search at ``radius`` has not seen anything farther."""
+    try:
+        radius = float(radius)
+        threshold = radius if threshold is None else float(threshold)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: radius {radius!r}, threshold {threshold!r}: {e}") from None
+    if not (radius > 0.0 and radius < float("inf")) or not threshold >= 0.0:
+        raise ValueError(f"{what}: radius {radius} (finite, > 0), threshold {threshold} (>= 0)")
+    if threshold > radius:
+        raise ValueError(f"{what}: threshold {threshold} > radius {radius}: the search has not seen neighbours beyond its radius")
+    return radius, threshold
+
+
+def cloud_metrics(dist_a, dist_b, radius, threshold):
+    """The 3D scores of a map against a reference cloud from two nearest-neighbour searches at ``radius``: ``dist_a`` (Qa,) the
+    distance of every MAP point to its nearest reference point, ``dist_b`` (Qb,) that of every REFERENCE point to its nearest map point,
+    +inf where the search found none (``nearest_points(...)['dist']``).  Returns a dict of 0-dim tensors on the distances' device.
+    Exact int64 counts: ``n_a``, ``n_b`` (rows), ``found_a``, ``found_b`` (rows with a neighbour), ``within_a``, ``within_b`` (rows
+    with ``dist <= threshold``).  Float64: ``accuracy`` = the mean of ``dist_a`` over its found rows and ``completion`` = the same for
+    ``dist_b`` (NaN when nothing was found); ``accuracy_clipped`` / ``completion_clipped`` = the mean over ALL rows, a row without a
+    neighbour counted at ``radius`` -- a hole in the map raises ``completion_clipped``, not ``completion``; ``precision`` = within_a /
+    n_a; ``recall`` = within_b / n_b, the completion ratio; ``fscore`` = 2 precision recall / (precision + recall), 0 when both are 0;
+    ``chamfer`` = accuracy + completion.  Sums are float64 ``torch.sum``s of the float32 distances.  ``threshold > radius`` raises
+    ``ValueError``.  Pure torch: runs on CPU tensors too, and makes no host read."""
+    radius, threshold = _threshold(radius, threshold, "cloud_metrics")
+    out = {}
+    for side, d in (('a', dist_a), ('b', dist_b)):
+        if not torch.is_tensor(d) or d.dtype != torch.float32 or d.dim() != 1 or d.shape[0] == 0:
+            raise ValueError(f"cloud_metrics: dist_{side} must be a non-empty float32 (Q,) tensor")
+        found = d < float("inf")
+        n = torch.tensor(int(d.shape[0]), dtype=torch.int64, device=d.device)
+        n_found = found.sum()
+        d64 = d.detach().double()
+        zero = torch.zeros((), dtype=torch.float64, device=d.device)
+        out['n_' + side], out['found_' + side], out['within_' + side] = n, n_found, (d <= threshold).sum()
+        out['mean_' + side] = torch.where(found, d64, zero).sum() / n_found.double()
+        out['clipped_' + side] = torch.where(found, d64, zero + radius).sum() / n.double()
+    precision, recall = out['within_a'].double() / out['n_a'].double(), out['within_b'].double() / out['n_b'].double()
+    both = precision + recall
+    fscore = torch.where(both > 0, 2.0 * precision * recall / torch.where(both > 0, both, torch.ones_like(both)), torch.zeros_like(both))
+    accuracy, completion = out.pop('mean_a'), out.pop('mean_b')
+    out.update(accuracy=accuracy, completion=completion, accuracy_clipped=out.pop('clipped_a'), completion_clipped=out.pop('clipped_b'),
+               precision=precision, recall=recall, fscore=fscore, chamfer=accuracy + completion)
+    return out
+
+
+def map_distance(world, reference, radius, threshold=None, origin=None):
+    """The map against a reference cloud in 3D: ``world`` is any world dict ``fuse_map`` accepts (raw, filtered or fused),
+    ``reference`` a dict with ``'points'`` or an (R,3) float32 tensor -- usually what ``viz.depth_image_lift`` / ``lift_depth_images``
+    made of the ground-truth depths, trimmed to its valid rows.  Two ``cloud_grid`` builds and two ``nearest_points`` queries at
+    ``radius`` (include/sp_hip.h has the rule): returns ``dict(to_reference, to_map, metrics)`` -- per map point its nearest reference
+    point (``index``, ``dist``, ``count``), per reference point its nearest map point, and ``cloud_metrics`` of the two distances at
+    ``threshold`` (default: ``radius``).  ``world`` is left untouched.  No synchronisation."""
+    from ..tool import viz
+    radius, threshold = _threshold(radius, threshold, "map_distance")
+    _check_world(world, "map_distance")
+    ref = reference.get('points') if isinstance(reference, dict) else reference
+    if not torch.is_tensor(ref):
+        raise ValueError("map_distance: reference must be an (R,3) float32 tensor or a dict with 'points'")
+    ref_grid = viz.cloud_grid(ref, radius, origin)
+    to_reference = viz.nearest_points(world['points'], ref_grid)
+    map_grid = viz.cloud_grid(world['points'], radius, origin)
+    to_map = viz.nearest_points(ref, map_grid)
+    return dict(to_reference=to_reference, to_map=to_map, metrics=cloud_metrics(to_reference['dist'], to_map['dist'], radius, threshold))
+
+
+def map_neighbours(world, radius, origin=None):
+    """Every map point against the other points of the map: ``index`` (Q,) int32 the nearest OTHER point within ``radius`` (-1: none),
+    ``dist`` (Q,) float32 its distance -- the map's spacing -- and ``count`` (Q,) int32 the other points within ``radius``: Open3D's
+    ``remove_radius_outlier(nb_points, radius)`` keeps the rows with ``count >= nb_points``.  One ``cloud_grid`` build and one
+    ``nearest_points`` query with ``skip_self``.  No synchronisation."""
+    from ..tool import viz
+    _check_world(world, "map_neighbours")
+    grid = viz.cloud_grid(world['points'], radius, origin)
+    return viz.nearest_points(grid['points'], grid, skip_self=True)
 
 
 def write_ply(path, world):

@@ -14,6 +14,8 @@ matplotlib is imported):
 ``keyframe_depths``    what each keyframe claims to see: its own depth image and segment map, from its table (``sp_keyframe_depths``).
 ``map_consistency``    every point against V depth images: agree / in front / behind counts per point (``sp_map_consistency``).
 ``fuse_points``        one averaged point per occupied voxel of a point set (``sp_map_fuse``).
+``cloud_grid``         a point cloud prepared for neighbour queries at one radius (``sp_cloud_grid_build``).
+``nearest_points``     per query point the nearest point of such a cloud, its distance and the count within the radius (``sp_cloud_grid_nearest``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
 from __future__ import annotations
@@ -382,4 +384,65 @@ def fuse_points(points, colours=None, voxel=0.05, origin=None):
     _lib.check(lib.sp_map_fuse(_lib.ptr(pts), _lib.ptr(cols), Q, vox, org[0], org[1], org[2], _lib.ptr(scratch), _lib.ptr(out['points']),
                                _lib.ptr(out['colours']), _lib.ptr(out['count']), _lib.ptr(out['first']), _lib.ptr(out['label']), _lib.ptr(out['n']),
                                _lib.stream_ptr()), "sp_map_fuse")
+    return out
+
+
+def cloud_grid(points, radius, origin=None):
+    """ONE ``sp_cloud_grid_build`` call (include/sp_hip.h has the rule): ``points`` (Q,3) float32, the REFERENCE cloud, prepared for
+    ``nearest_points`` at search radius ``radius`` (a finite float32 > 0); ``origin`` three finite numbers (default: 0, 0, 0) -- points
+    beyond 2^20 cells of side ``radius`` from it, or with a non-finite coordinate, are never found.  Returns the handle
+    ``dict(scratch, Q, radius, origin, points)``; the points tensor is kept alive there for ``skip_self``.  No synchronisation."""
+    _on_device(points)
+    pts = _f32(points, (None, 3), "points")
+    Q = int(pts.shape[0])
+    if Q == 0:
+        raise ValueError("cloud_grid: no points")
+    try:
+        rad = float(torch.tensor(float(radius), dtype=torch.float32))          # the float32 the kernel squares
+        org = [0.0, 0.0, 0.0] if origin is None else [float(o) for o in torch.as_tensor(origin, dtype=torch.float64).reshape(-1).float().tolist()]
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"cloud_grid: radius {radius!r}, origin {origin!r}: {e}") from None
+    if not (rad > 0.0 and rad < float("inf")):
+        raise ValueError(f"cloud_grid: radius {radius} (a finite float32 > 0)")
+    if len(org) != 3 or not all(abs(o) < float("inf") for o in org):
+        raise ValueError(f"cloud_grid: origin {origin} (three finite float32 numbers)")
+    if Q > _lib.SP_CLOUD_GRID_MAX_POINTS:
+        raise ValueError(f"cloud_grid: {Q} points are beyond the kernel's limit of {_lib.SP_CLOUD_GRID_MAX_POINTS}")
+    lib = _lib.load()
+    units = lib.sp_cloud_grid_scratch_units(Q)
+    if units < 0:
+        raise ValueError(f"cloud_grid: {Q} points are beyond the kernel's limits")
+    scratch = torch.empty(units, 8, dtype=torch.int64, device=pts.device)
+    _lib.check(lib.sp_cloud_grid_build(_lib.ptr(pts), Q, rad, org[0], org[1], org[2], _lib.ptr(scratch), _lib.stream_ptr()), "sp_cloud_grid_build")
+    return dict(scratch=scratch, Q=Q, radius=rad, origin=tuple(org), points=pts)
+
+
+def nearest_points(queries, grid, skip_self=False):
+    """ONE ``sp_cloud_grid_nearest`` call: per row of ``queries`` (Qa,3) float32 the nearest point of the cloud behind ``grid`` (what
+    ``cloud_grid`` returned) within the grid's radius -- ``index`` (Qa,) int32, the lowest row on equal distance, -1 for none; ``dist``
+    (Qa,) float32, +inf for none; ``count`` (Qa,) int32, the points within the radius.  ``skip_self``: the queries are the grid's own
+    cloud (the same number of rows) and no row finds itself.  No synchronisation."""
+    if not isinstance(grid, dict) or any(k not in grid for k in ('scratch', 'Q', 'radius', 'origin', 'points')) \
+            or not torch.is_tensor(grid['scratch']) or not torch.is_tensor(grid['points']):
+        raise ValueError("nearest_points: grid must be what cloud_grid returned")
+    Q, scratch = int(grid['Q']), grid['scratch']
+    if not 1 <= Q <= _lib.SP_CLOUD_GRID_MAX_POINTS or int(grid['points'].shape[0]) != Q:
+        raise ValueError(f"nearest_points: a grid of {Q} points over a cloud of {int(grid['points'].shape[0])}")
+    _on_device(queries, scratch, grid['points'])
+    qs = _f32(queries, (None, 3), "queries")
+    Qa = int(qs.shape[0])
+    if Qa == 0:
+        raise ValueError("nearest_points: no queries")
+    if Qa > 2 ** 31 - 2:
+        raise ValueError(f"nearest_points: {Qa} queries are beyond the kernel's limit of {2 ** 31 - 2}")
+    if skip_self and Qa != Q:
+        raise ValueError(f"nearest_points: skip_self with {Qa} queries against a grid of {Q} points (the queries must be the grid's cloud)")
+    lib = _lib.load()
+    if scratch.dtype != torch.int64 or not scratch.is_contiguous() or scratch.numel() != 8 * lib.sp_cloud_grid_scratch_units(Q):
+        raise ValueError(f"nearest_points: the grid's scratch ({scratch.dtype}, {scratch.numel()} elements) is not that of {Q} points")
+    dev = qs.device
+    out = dict(index=torch.empty(Qa, dtype=torch.int32, device=dev), dist=torch.empty(Qa, dtype=torch.float32, device=dev),
+               count=torch.empty(Qa, dtype=torch.int32, device=dev))
+    _lib.check(lib.sp_cloud_grid_nearest(_lib.ptr(qs), Qa, Q, _lib.ptr(scratch), 1 if skip_self else 0, _lib.ptr(out['index']), _lib.ptr(out['dist']),
+                                         _lib.ptr(out['count']), _lib.stream_ptr()), "sp_cloud_grid_nearest")
     return out
