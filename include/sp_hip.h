@@ -1454,6 +1454,96 @@ int sp_cloud_grid_build(const float* points, long long Q, float radius, float ox
 int sp_cloud_grid_nearest(const float* queries, long long Qa, long long Q, const void* scratch, int skip_self, int32_t* index, float* dist,
                           int32_t* count, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Map registration (sp_register.hip): the similarity x -> s R x + t that moves a QUERY cloud onto a REFERENCE cloud prepared by
+ * sp_cloud_grid_build, by Gauss-Newton ICP (iterative closest point) from a start the caller gives.  Everything runs on the caller's
+ * stream: no host synchronisation, no allocation, no host read per iteration; argument checks come before any device work.
+ *     queries      : (Qa,3) float32;  normals : (Q,3) float32 for residual 1 (the REFERENCE cloud's, one row per grid point), (Qa,3)
+ *                    float32 for residual 2 (the QUERY cloud's), NULL allowed for residual 0 (ignored there)
+ *     grid_scratch : what sp_cloud_grid_build wrote for the Q reference points (its radius r is the correspondence radius)
+ *     residual     : 0 point to point, 1 point to plane (reference normals), 2 plane to point (query normals);  with_scale : 0 or 1
+ *     huber        : 0 = every pair weighs 1, > 0 the Huber threshold;  tol : the step length at which the iteration has converged
+ *     min_pairs    : fewer pairs than this end the run (SP_CLOUD_REG_FEW);  max_iters : the iterations enqueued
+ *     state        : one SpCloudReg on the device.  THE CALLER WRITES rot, trans AND s, the start; the call owns every other field
+ *     history      : (max_iters,4) float64 {n, cost, step, status}, one row per enqueued iteration;  index : (Qa,) int32, written for
+ *                    every row;  work : sp_cloud_register_work_doubles(Qa) float64 of scratch
+ * The rest of the state is zeroed (status = SP_CLOUD_REG_RUNNING), then ONE ITERATION IS TWO LAUNCHES, and all max_iters iterations
+ * are enqueued; once the status is no longer RUNNING both passes return after one uniform load.
+ * Pass A, one lane per query row i, ceil(Qa / 256) workgroups.  Float64 from the float32 inputs, every operation rounded on its own
+ * (no fma, no reciprocal), three-term sums as (x + y) + z.  With R, t, s of the state:
+ *     a'_k = s ((R_k0 a_x + R_k1 a_y) + R_k2 a_z) + t_k                                                           (the moved point)
+ *     b    = the reference row sp_cloud_grid_nearest finds for the position a' -- the same device function: the range test on a',
+ *            the 27 cells, d2 <= r2, the smallest (d2, row) --,  d = a' - b.
+ * Unknowns omega (3), v (3), sigma (1: the log of the scale's change; its column J_sigma is 0 with with_scale = 0).  Rows of the residual:
+ *     0: three rows r = d;   row k has J_omega = row k of -[a']x = {(0, a'_z, -a'_y), (-a'_z, 0, a'_x), (a'_y, -a'_x, 0)}, J_v = e_k,
+ *        J_sigma = a'_k
+ *     1: n = normals[row of b];       r = n . d,  J_omega = a' x n,  J_v = n,  J_sigma = n . a'
+ *     2: n = R normals[i] (each row (x + y) + z);  r = n . d,  J_omega = b x n,  J_v = n,  J_sigma = n . a'  (the normal turns with the
+ *        cloud, which is part of the linearisation: hence b)
+ * Dot products as (x + y) + z, a cross product's component as u_y v_z - u_z v_y (two products, one difference).
+ *     w = 1;  with huber > 0:  w = min(1, huber / rho),  rho = sqrt((d_x d_x + d_y d_y) + d_z d_z) for residual 0, |r| for 1 and 2;
+ *     rho = 0 gives w = 1.
+ * A row CONTRIBUTES unless it has no neighbour (a non-finite a' has none: the range test), or the normal it uses or n is non-finite;
+ * then index[i] = -1, else the neighbour's row.  Sums over the rows of the residual of the contributing query rows, with wJ_a = w J_a:
+ *     H_ab = sum wJ_a J_b (a <= b),   g_a = sum wJ_a r,   cost = sum (w r) r,   n = the contributing query rows (an exact int64).
+ * Each workgroup reduces its lanes in a fixed order (a butterfly over the 64 lanes of a wave, then ((w0 + w1) + (w2 + w3))) and writes
+ * one record of 40 float64 to work (28 H, 7 g, cost, n as int64, 3 unused).  No floating-point atomics.
+ * Pass B, one workgroup: the records summed in a fixed order (25 strided running sums per entry -- record g, g + 25, ... --, then
+ * those 25 in order); then
+ *     n < min_pairs: status = SP_CLOUD_REG_FEW, no solve, the transform stays bitwise as it was;
+ *     a non-finite sum, a pivot of the LDL^T factorisation of H (6 x 6, or 7 x 7 with scale; float64) that is not > 0, or a solution
+ *     whose length is not finite: status = SP_CLOUD_REG_DEGENERATE, the transform stays bitwise as it was;
+ *     else H delta = -g is solved and the transform moves on the left.  theta2 = (w_x w_x + w_y w_y) + w_z w_z for omega = w:
+ *         theta2 < 2^-26 (SP_CLOUD_REG_SMALL_ANGLE2):  A = 1 - theta2 / 6,  B = 0.5 - theta2 / 24   (the next terms are below 2^-58)
+ *         else theta = sqrt(theta2),  A = sin(theta) / theta,  h = sin(theta / 2) / (theta / 2),  B = 0.5 h h    (no cancellation)
+ *         dR = I + A [w]x + B [w]x [w]x,   e = exp(sigma)
+ *         R <- dR R,   t <- e (dR t) + v,   s <- s e
+ *     step = sqrt of the sum of delta_k^2 in order;  step <= tol: status = SP_CLOUD_REG_CONVERGED;  else, on the last enqueued
+ *     iteration, SP_CLOUD_REG_MAX_ITERS.
+ * Pass B stores H, g, delta (0 without a solve), cost, n and step in the state, counts the iteration in state.iterations and writes
+ * history[iter] = {n, cost, step, status}.  The rows of history after the stop are {0, 0, 0, status}.
+ * The correspondences do not depend on the order in which the build scattered the grid's records (a minimum over (d2, row)) and every
+ * sum is taken in a fixed order: TWO RUNS GIVE THE SAME BITS in state, history and index; with the reference rows permuted the state is
+ * bitwise the same and index is renamed (where no two candidates tie in d2).  Permuting the QUERY rows reorders the sums: the result
+ * agrees within the rounding of the sums only.
+ * No workgroup waits on another, nothing spins, every loop is bounded.
+ * Null queries / grid_scratch / state / history / index / work, normals missing for residual 1 or 2, residual outside 0 .. 2,
+ * with_scale outside {0, 1}, huber or tol negative or non-finite, min_pairs below the number of unknowns (6, or 7 with scale),
+ * max_iters < 1, Q or Qa <= 0, a grid_scratch or work not aligned to 16 bytes, state / history not aligned to 8: SP_EINVAL.
+ * Q > 2^28, Qa > 2^31 - 2 or max_iters > SP_CLOUD_REG_ITERS_LIMIT (the launches are enqueued up front): SP_ELIMIT.  Invalid beats too
+ * large.  sp_cloud_register_work_doubles answers Qa <= 0 and Qa > 2^31 - 2 with the same codes. */
+#define SP_CLOUD_REG_RUNNING 0
+#define SP_CLOUD_REG_CONVERGED 1
+#define SP_CLOUD_REG_MAX_ITERS 2
+#define SP_CLOUD_REG_FEW 3
+#define SP_CLOUD_REG_DEGENERATE 4
+#define SP_CLOUD_REG_ITERS_LIMIT 4096
+#define SP_CLOUD_REG_WORK_DOUBLES 40
+#define SP_CLOUD_REG_SMALL_ANGLE2 1.490116119384765625e-8 /* 2^-26 */
+typedef struct SpCloudReg {
+    double rot[9];       /* R, row major */
+    double trans[3];     /* t */
+    double s;
+    double H[28];        /* upper triangle of the 7 x 7 system, row major: (0,0) .. (0,6), (1,1) .. (1,6), ..., (6,6) */
+    double g[7];
+    double delta[7];     /* omega, v, sigma of the last solve */
+    double cost;
+    double step;
+    long long n;
+    int32_t status;      /* SP_CLOUD_REG_* */
+    int32_t iterations;  /* the iterations that ran while RUNNING */
+    double pad_[5];      /* 512 bytes: a whole number of 64-byte units */
+} SpCloudReg;
+#ifdef __cplusplus
+static_assert(sizeof(SpCloudReg) % 64 == 0 && sizeof(SpCloudReg) == 512, "SpCloudReg is padded to a multiple of 64 bytes");
+#else
+_Static_assert(sizeof(SpCloudReg) % 64 == 0 && sizeof(SpCloudReg) == 512, "SpCloudReg is padded to a multiple of 64 bytes");
+#endif
+int sp_cloud_register_work_doubles(long long Qa);
+int sp_cloud_register(const float* queries, const float* normals, long long Qa, long long Q, const void* grid_scratch, int residual,
+                      int with_scale, double huber, double tol, long long min_pairs, int max_iters, SpCloudReg* state, double* history,
+                      int32_t* index, double* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,8 @@ SIGNATURES = {
     "sp_cloud_grid_scratch_units": [ctypes.c_longlong],
     "sp_cloud_grid_build": [P, ctypes.c_longlong, F, F, F, F, P, P],
     "sp_cloud_grid_nearest": [P, ctypes.c_longlong, ctypes.c_longlong, P, I, P, P, P, P],
+    "sp_cloud_register_work_doubles": [ctypes.c_longlong],
+    "sp_cloud_register": [P, P, ctypes.c_longlong, ctypes.c_longlong, P, I, I, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, I, P, P, P, P, P],
 }
 
 SP_ABI_VERSION = 19
@@ -284,6 +286,18 @@ class SpMapKeyframe(ctypes.Structure):
 SP_VIEW_FLOATS = 25
 SP_MAP_FUSE_MAX_POINTS = 1 << 28
 SP_CLOUD_GRID_MAX_POINTS = 1 << 28
+SP_CLOUD_REG_RUNNING, SP_CLOUD_REG_CONVERGED, SP_CLOUD_REG_MAX_ITERS, SP_CLOUD_REG_FEW, SP_CLOUD_REG_DEGENERATE = range(5)
+SP_CLOUD_REG_ITERS_LIMIT = 4096
+SP_CLOUD_REG_WORK_DOUBLES = 40
+
+
+class SpCloudReg(ctypes.Structure):
+    """Mirror of ``struct SpCloudReg`` (include/sp_hip.h): the state of one registration; 512 bytes, device memory (64 float64 words:
+    rot 0..8, trans 9..11, s 12, H 13..40, g 41..47, delta 48..54, cost 55, step 56, n 57 as int64, status and iterations the two int32
+    of word 58)."""
+    _fields_ = [("rot", ctypes.c_double * 9), ("trans", ctypes.c_double * 3), ("s", ctypes.c_double), ("H", ctypes.c_double * 28),
+                ("g", ctypes.c_double * 7), ("delta", ctypes.c_double * 7), ("cost", ctypes.c_double), ("step", ctypes.c_double),
+                ("n", ctypes.c_longlong), ("status", c_int), ("iterations", c_int), ("pad_", ctypes.c_double * 5)]
 
 
 class SpView(ctypes.Structure):

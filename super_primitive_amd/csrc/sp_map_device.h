@@ -1,4 +1,4 @@
-// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip): each idiom has its one definition here.
+// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip, sp_register.hip): each idiom has its one definition here.
 #pragma once
 #include "sp_device.h"
 
@@ -97,6 +97,104 @@ __device__ __forceinline__ int32_t fuse_claim(Slot* __restrict__ table, unsigned
         h = (h + 1u) & mask;
     }
     return -1;
+}
+
+// ---- the prepared cloud of sp_cloud_grid_build (sp_nearest.hip builds and queries it, sp_register.hip queries it): its layout, the
+// cell of a point, and THE neighbour walk -- one definition, so a registration pass finds exactly the row sp_cloud_grid_nearest finds.
+// The arithmetic carries its own contraction pragma: every operation is rounded on its own whatever the including file allows. -------
+struct GridHeader {
+    double r2, cell, o[3];
+    unsigned int mask;                 // S - 1
+    int32_t Q;
+    long long pad_[2];
+};
+static_assert(sizeof(GridHeader) == 64, "the header is one 64-byte unit");
+
+struct alignas(16) GridSlot {
+    unsigned long long key;            // FUSE_EMPTY until claimed
+    int32_t start;                     // the scatter's cursor: the cell's first record before it, its end after it
+    int32_t count;
+};
+static_assert(sizeof(GridSlot) == 16, "one slot is one 16-byte load");
+
+struct alignas(16) GridRecord { float x, y, z; int32_t row; };
+static_assert(sizeof(GridRecord) == 16, "one member is one 16-byte load");
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+constexpr float GRID_INF = __builtin_huge_valf();
+
+struct GridLayout { long long slots, blocks, table_units, record_units, row_units, block_units; };
+
+// Q in 1 .. SP_CLOUD_GRID_MAX_POINTS.  The scratch: header | table | records | slot numbers | block sums, each a whole number of units
+inline GridLayout grid_layout(long long Q) {
+    GridLayout l;
+    l.slots = 2;
+    while (l.slots < 2 * Q) l.slots <<= 1;
+    l.blocks = (l.slots + SP_BLOCK - 1) / SP_BLOCK;
+    l.table_units = (l.slots + 3) / 4;                     // 16 bytes each
+    l.record_units = (Q + 3) / 4;                          // 16 bytes each
+    l.row_units = (Q + 15) / 16;                           // Q int32
+    l.block_units = (l.blocks + 15) / 16;                  // ceil(S / 256) int32
+    return l;
+}
+
+// one axis of a point (a float32 coordinate converted exactly, or a float64 one): false = out of range; else the biased cell index
+// (1 .. 2^21 - 2: the cells to either side have one too)
+__device__ __forceinline__ bool grid_axis(double p, double o, double cell, unsigned long long& c) {
+#pragma clang fp contract(off)
+    const double q = (p - o) / cell;
+    const double g = floor(q);
+    if (!(g >= 1.0 - FUSE_HALF_RANGE && g <= FUSE_HALF_RANGE - 2.0)) return false;  // NaN and +-inf fail; tested before the conversion
+    c = (unsigned long long)((long long)g + 1048576LL);
+    return true;
+}
+
+// what one query finds: d2 and row of the neighbour with the smallest (d2, row) (HUGE_VAL and -1: none), where its record lies, and
+// the number of neighbours
+struct GridNearest { double d2; int32_t row, place, count; };
+
+// The query (x, y, z) against the prepared cloud: the 27 cells around its own, each looked up (a 16-byte load per probe, until the key
+// or an empty slot), each cell's records walked; the decision is made in float64 exactly as the contract of sp_cloud_grid_nearest
+// writes it.  `self`: a row that is not a neighbour (-1: none).  A scratch built for another Q answers "none".
+__device__ __forceinline__ GridNearest grid_nearest_walk(double x, double y, double z, const GridHeader* __restrict__ header,
+                                                         const GridSlot* __restrict__ table, const GridRecord* __restrict__ records,
+                                                         unsigned int mask, int Q, int32_t self) {
+#pragma clang fp contract(off)
+    const double r2 = header->r2, cell = header->cell;     // (uniform: scalar loads)
+    const bool built = header->mask == mask && header->Q == Q;
+    unsigned long long cx = 0, cy = 0, cz = 0;
+    const bool in = built && grid_axis(x, header->o[0], cell, cx) && grid_axis(y, header->o[1], cell, cy) && grid_axis(z, header->o[2], cell, cz);
+    GridNearest f = {HUGE_VAL, -1, -1, 0};
+    if (in) {
+#pragma unroll 1
+        for (int c = 0; c < 27; ++c) {
+            const int c9 = c / 9, c3 = (c / 3) % 3, c1 = c % 3;
+            const unsigned long long key = fuse_key(cx + (unsigned long long)c9 - 1ull, cy + (unsigned long long)c3 - 1ull, cz + (unsigned long long)c1 - 1ull);
+            unsigned int h = (unsigned int)fuse_mix(key) & mask;
+            int32_t end = 0, members = 0;
+            for (unsigned int probe = 0; probe <= mask; ++probe) {                   // at most S slots
+                const i32x4 s = *reinterpret_cast<const i32x4*>(table + h);
+                const unsigned long long cur = ((unsigned long long)(uint32_t)s.y << 32) | (unsigned long long)(uint32_t)s.x;
+                if (cur == key) { end = s.z; members = s.w; break; }
+                if (cur == FUSE_EMPTY) break;
+                h = (h + 1u) & mask;
+            }
+            if (members > end) members = end;              // (cannot happen after a build: keeps the walk inside the records)
+            if (end > Q) members = 0;
+            for (int32_t m = end - members; m < end; ++m) {
+                const i32x4 raw = *reinterpret_cast<const i32x4*>(records + m);
+                const double dx = x - (double)__int_as_float(raw.x), dy = y - (double)__int_as_float(raw.y), dz = z - (double)__int_as_float(raw.z);
+                const double d2 = (dx * dx + dy * dy) + dz * dz;
+                const int32_t row = raw.w;
+                if (d2 <= r2 && row != self) {
+                    ++f.count;
+                    if (d2 < f.d2 || (d2 == f.d2 && row < f.row)) { f.d2 = d2; f.row = row; f.place = m; }
+                }
+            }
+        }
+    }
+    return f;
 }
 
 // ---- the keyframe walk: a workgroup belongs to ONE keyframe, the last record whose first_block is at or before it (uniform: scalar loads)

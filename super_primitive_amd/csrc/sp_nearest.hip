@@ -16,6 +16,7 @@
 //                   `start` is the cursor, so AFTER this pass it holds the cell's END: the members are end - count .. end - 1
 //   k_grid_nearest  one lane per query: the 27 cells around its own, each looked up (a 16-byte load per probe, until the key or an
 //                   empty slot), each cell's records walked; the decision is made in float64 exactly as the contract writes it
+//                   (grid_nearest_walk in sp_map_device.h, with the layout of the scratch: sp_register.hip walks the same way)
 // The order in which the scatter stores a cell's members differs from run to run; a minimum over (d2, row) and a count do not depend
 // on it.  No workgroup waits on another, no flags, nothing spins.  Every loop is bounded: a probe visits at most S slots, a walk at
 // most `count` records.
@@ -29,37 +30,6 @@
 #pragma clang fp contract(off)
 
 namespace {
-
-struct GridHeader {
-    double r2, cell, o[3];
-    unsigned int mask;                 // S - 1
-    int32_t Q;
-    long long pad_[2];
-};
-static_assert(sizeof(GridHeader) == 64, "the header is one 64-byte unit");
-
-struct alignas(16) GridSlot {
-    unsigned long long key;            // FUSE_EMPTY until claimed
-    int32_t start;                     // the scatter's cursor: the cell's first record before it, its end after it
-    int32_t count;
-};
-static_assert(sizeof(GridSlot) == 16, "one slot is one 16-byte load");
-
-struct alignas(16) GridRecord { float x, y, z; int32_t row; };
-static_assert(sizeof(GridRecord) == 16, "one member is one 16-byte load");
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float GRID_INF = __builtin_huge_valf();
-
-// one axis of a point: false = out of range; else the biased cell index (1 .. 2^21 - 2: the cells to either side have one too)
-__device__ __forceinline__ bool grid_axis(float p, double o, double cell, unsigned long long& c) {
-    const double q = ((double)p - o) / cell;
-    const double g = floor(q);
-    if (!(g >= 1.0 - FUSE_HALF_RANGE && g <= FUSE_HALF_RANGE - 2.0)) return false;  // NaN and +-inf fail; tested before the conversion
-    c = (unsigned long long)((long long)g + 1048576LL);
-    return true;
-}
 
 struct BlockScan { int before, total; };                   // the sum over the threads before this one in its workgroup; over all of them
 // EVERY thread of the block must call it (there is a barrier inside), once per kernel; wc: SP_WAVES ints of LDS
@@ -144,61 +114,11 @@ __global__ __launch_bounds__(SP_BLOCK) void k_grid_nearest(const float* __restri
                                                            float* __restrict__ dist, int32_t* __restrict__ count) {
     const long long i = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
     if (i >= Qa) return;
-    const double r2 = header->r2, cell = header->cell;     // (uniform: scalar loads)
-    const bool built = header->mask == mask && header->Q == Q;                       // a scratch built for another Q answers "none"
     const float ax = queries[3 * (size_t)i], ay = queries[3 * (size_t)i + 1], az = queries[3 * (size_t)i + 2];
-    unsigned long long cx = 0, cy = 0, cz = 0;
-    const bool in = built && grid_axis(ax, header->o[0], cell, cx) && grid_axis(ay, header->o[1], cell, cy) && grid_axis(az, header->o[2], cell, cz);
-    const double x = (double)ax, y = (double)ay, z = (double)az;
-    const int32_t self = skip_self ? (int32_t)i : -1;
-    double best = HUGE_VAL;
-    int32_t best_row = -1, n = 0;
-    if (in) {
-#pragma unroll 1
-        for (int c = 0; c < 27; ++c) {
-            const int c9 = c / 9, c3 = (c / 3) % 3, c1 = c % 3;
-            const unsigned long long key = fuse_key(cx + (unsigned long long)c9 - 1ull, cy + (unsigned long long)c3 - 1ull, cz + (unsigned long long)c1 - 1ull);
-            unsigned int h = (unsigned int)fuse_mix(key) & mask;
-            int32_t end = 0, members = 0;
-            for (unsigned int probe = 0; probe <= mask; ++probe) {                   // at most S slots
-                const i32x4 s = *reinterpret_cast<const i32x4*>(table + h);
-                const unsigned long long cur = ((unsigned long long)(uint32_t)s.y << 32) | (unsigned long long)(uint32_t)s.x;
-                if (cur == key) { end = s.z; members = s.w; break; }
-                if (cur == FUSE_EMPTY) break;
-                h = (h + 1u) & mask;
-            }
-            if (members > end) members = end;              // (cannot happen after a build: keeps the walk inside the records)
-            if (end > Q) members = 0;
-            for (int32_t m = end - members; m < end; ++m) {
-                const i32x4 raw = *reinterpret_cast<const i32x4*>(records + m);
-                const double dx = x - (double)__int_as_float(raw.x), dy = y - (double)__int_as_float(raw.y), dz = z - (double)__int_as_float(raw.z);
-                const double d2 = (dx * dx + dy * dy) + dz * dz;
-                const int32_t row = raw.w;
-                if (d2 <= r2 && row != self) {
-                    ++n;
-                    if (d2 < best || (d2 == best && row < best_row)) { best = d2; best_row = row; }
-                }
-            }
-        }
-    }
-    index[i] = best_row;
-    dist[i] = best_row < 0 ? GRID_INF : (float)sqrt(best);
-    count[i] = n;
-}
-
-struct GridLayout { long long slots, blocks, table_units, record_units, row_units, block_units; };
-
-// Q in 1 .. SP_CLOUD_GRID_MAX_POINTS.  The scratch: header | table | records | slot numbers | block sums, each a whole number of units
-GridLayout grid_layout(long long Q) {
-    GridLayout l;
-    l.slots = 2;
-    while (l.slots < 2 * Q) l.slots <<= 1;
-    l.blocks = (l.slots + SP_BLOCK - 1) / SP_BLOCK;
-    l.table_units = (l.slots + 3) / 4;                     // 16 bytes each
-    l.record_units = (Q + 3) / 4;                          // 16 bytes each
-    l.row_units = (Q + 15) / 16;                           // Q int32
-    l.block_units = (l.blocks + 15) / 16;                  // ceil(S / 256) int32
-    return l;
+    const GridNearest f = grid_nearest_walk((double)ax, (double)ay, (double)az, header, table, records, mask, Q, skip_self ? (int32_t)i : -1);
+    index[i] = f.row;
+    dist[i] = f.row < 0 ? GRID_INF : (float)sqrt(f.d2);
+    count[i] = f.count;
 }
 
 }  // namespace

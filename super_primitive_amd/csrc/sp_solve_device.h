@@ -204,7 +204,37 @@ __device__ bool ldlt6_solve(double S[36], double rhs[6]) {
     return true;
 }
 
-#define SP_SEG_CACHE 256     // segments whose reduced {h(6), 1/D', b_d} live in LDS; beyond that they are recomputed
+// Its sibling for 7 unknowns (a similarity: rotation, translation, log-scale; sp_register.hip): the same operations in the same order,
+// S row major 7 x 7 (the lower triangle is read), x returned in rhs.  false if a pivot is not positive.
+__device__ bool ldlt7_solve(double S[49], double rhs[7]) {
+    double dinv[7];
+    for (int j = 0; j < 7; ++j) {
+        double d = S[8 * j];
+        for (int k = 0; k < j; ++k) d -= S[7 * j + k] * S[7 * j + k] * S[8 * k];
+        if (!(d > 0.0)) return false;
+        S[8 * j] = d;
+        dinv[j] = 1.0 / d;
+        for (int i = j + 1; i < 7; ++i) {
+            double v = S[7 * i + j];
+            for (int k = 0; k < j; ++k) v -= S[7 * i + k] * S[7 * j + k] * S[8 * k];
+            S[7 * i + j] = v * dinv[j];
+        }
+    }
+    for (int i = 0; i < 7; ++i) {            // L y = rhs
+        double v = rhs[i];
+        for (int k = 0; k < i; ++k) v -= S[7 * i + k] * rhs[k];
+        rhs[i] = v;
+    }
+    for (int i = 0; i < 7; ++i) rhs[i] *= dinv[i];
+    for (int i = 6; i >= 0; --i) {           // L^T x = y
+        double v = rhs[i];
+        for (int k = i + 1; k < 7; ++k) v -= S[7 * k + i] * rhs[k];
+        rhs[i] = v;
+    }
+    return true;
+}
+
+#define SP_SEG_CACHE 256    // segments whose reduced {h(6), 1/D', b_d} live in LDS; beyond that they are recomputed
 
 // {h_pd(6), D, b_d} of segment n summed over its (chunk, wave) records; lam -> {h, 1/(D(1+lam)) or 0, b_d}
 __device__ __forceinline__ void segment_system(const float* __restrict__ p, const int32_t* __restrict__ seg_tile_off, int n,

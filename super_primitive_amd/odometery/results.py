@@ -22,6 +22,8 @@
                       within a radius, both ways (``sp_cloud_grid_build`` / ``sp_cloud_grid_nearest``), and ``cloud_metrics`` of the two
                       distance vectors: accuracy, completion, precision, recall, F-score; ``map_neighbours`` is the map against itself:
                       its spacing and the neighbour count a radius outlier filter keeps points by.
+``register_map``      the map moved onto a reference cloud by ICP on the device before it is scored (``sp_cloud_register``): the 3D scores no
+                      longer hang on a similarity fitted to a handful of camera centres; ``transform_map`` applies any similarity to a map.
 ``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``.
 ``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file."""
 from __future__ import annotations
@@ -494,6 +496,59 @@ def map_distance(world, reference, radius, threshold=None, origin=None):
     map_grid = viz.cloud_grid(world['points'], radius, origin)
     to_map = viz.nearest_points(ref, map_grid)
     return dict(to_reference=to_reference, to_map=to_map, metrics=cloud_metrics(to_reference['dist'], to_map['dist'], radius, threshold))
+
+
+def _mat3(x, d):
+    """Rows of ``x`` (Q,3) times the rows of ``d`` (3,3), each sum as (x + y) + z: the three-term order of the kernels' contracts."""
+    return torch.stack([(x[:, 0] * d[k, 0] + x[:, 1] * d[k, 1]) + x[:, 2] * d[k, 2] for k in range(3)], dim=1)
+
+
+def transform_map(world, rot, trans, s=1.0):
+    """``world`` moved by the similarity x -> s R x + t (``rot`` (3,3), ``trans`` (3,), ``s`` a number or 0-dim tensor -- what
+    ``register_map`` / ``viz.register_clouds`` return, or any numbers): a NEW world dict whose ``points`` are computed in float64 from
+    the float32 rows -- ``s ((R_k0 x + R_k1 y) + R_k2 z) + t_k``, rounded to float32 once -- and whose ``normals`` (when the world has
+    them) are rotated the same way, ``(R_k0 n_x + R_k1 n_y) + R_k2 n_z``, rounded once; every other entry is carried over.  ``world`` is
+    left untouched.  Pure torch: runs on CPU tensors too, and makes no host read."""
+    pts = world.get('points') if isinstance(world, dict) else None
+    if not torch.is_tensor(pts) or pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError("transform_map: world['points'] must be a float32 (Q,3) tensor")
+    dev = pts.device
+    f64 = lambda x: torch.as_tensor(x, dtype=torch.float64).detach().to(dev)          # (numbers and lists become float64 directly)
+    R, t, sc = f64(rot), f64(trans).reshape(-1), f64(s)
+    if tuple(R.shape) != (3, 3) or tuple(t.shape) != (3,) or sc.dim() != 0:
+        raise ValueError(f"transform_map: rot {tuple(R.shape)}, trans {tuple(t.shape)}, s {tuple(sc.shape)} (want (3,3), (3,), a scalar)")
+    out = dict(world)
+    out['points'] = (sc * _mat3(pts.detach().double(), R) + t).float()
+    nrm = world.get('normals')
+    if nrm is not None:
+        if not torch.is_tensor(nrm) or nrm.dtype != torch.float32 or tuple(nrm.shape) != tuple(pts.shape):
+            raise ValueError(f"transform_map: world['normals'] must be a float32 tensor {tuple(pts.shape)}")
+        out['normals'] = _mat3(nrm.detach().double(), R).float()
+    return out
+
+
+def register_map(world, reference, radius, residual=None, **kw):
+    """The map moved onto a reference cloud by ICP before it is scored: ``reference`` is a dict with ``'points'`` (and maybe
+    ``'normals'``) or an (R,3) float32 tensor, ``radius`` the correspondence radius.  ONE ``cloud_grid`` build over the reference and
+    ONE ``viz.register_clouds`` call (``sp_cloud_register``; include/sp_hip.h has the rule) with the map's points as the queries.
+    ``residual`` defaults to ``'query_plane'`` when the map has normals, else ``'plane'`` when the reference has them, else
+    ``'point'``; ``**kw`` goes to ``register_clouds`` (``T0``, ``s0``, ``scale``, ``huber``, ``tol``, ``min_pairs``, ``max_iters``).
+    Returns ``dict(transform=<what register_clouds returned>, world=transform_map(world, rot, trans, s))``; pass ``['world']`` to
+    ``map_distance``.  ``world`` is left untouched.  No synchronisation, no host read."""
+    from ..tool import viz
+    _check_world(world, "register_map")
+    ref = reference.get('points') if isinstance(reference, dict) else reference
+    if not torch.is_tensor(ref):
+        raise ValueError("register_map: reference must be an (R,3) float32 tensor or a dict with 'points'")
+    ref_normals = reference.get('normals') if isinstance(reference, dict) else None
+    if residual is None:
+        residual = 'query_plane' if world.get('normals') is not None else ('plane' if ref_normals is not None else 'point')
+    normals = {'point': None, 'plane': ref_normals, 'query_plane': world.get('normals')}.get(residual)
+    if residual in ('plane', 'query_plane') and normals is None:
+        raise ValueError(f"register_map: residual {residual!r} needs normals of the {'reference' if residual == 'plane' else 'map'}")
+    grid = viz.cloud_grid(ref, radius)
+    transform = viz.register_clouds(world['points'], grid, normals=normals, residual=residual, **kw)
+    return dict(transform=transform, world=transform_map(world, transform['rot'], transform['trans'], transform['s']))
 
 
 def map_neighbours(world, radius, origin=None):

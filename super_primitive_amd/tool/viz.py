@@ -16,6 +16,7 @@ matplotlib is imported):
 ``fuse_points``        one averaged point per occupied voxel of a point set (``sp_map_fuse``).
 ``cloud_grid``         a point cloud prepared for neighbour queries at one radius (``sp_cloud_grid_build``).
 ``nearest_points``     per query point the nearest point of such a cloud, its distance and the count within the radius (``sp_cloud_grid_nearest``).
+``register_clouds``    the similarity that moves a query cloud onto such a cloud, by Gauss-Newton ICP on the device (``sp_cloud_register``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
 from __future__ import annotations
@@ -417,17 +418,32 @@ def cloud_grid(points, radius, origin=None):
     return dict(scratch=scratch, Q=Q, radius=rad, origin=tuple(org), points=pts)
 
 
+def _grid_handle(grid, what):
+    """(Q, scratch) of what ``cloud_grid`` returned; ``ValueError`` for anything else, before any tensor is touched."""
+    if not isinstance(grid, dict) or any(k not in grid for k in ('scratch', 'Q', 'radius', 'origin', 'points')) \
+            or not torch.is_tensor(grid['scratch']) or not torch.is_tensor(grid['points']):
+        raise ValueError(f"{what}: grid must be what cloud_grid returned")
+    Q = int(grid['Q'])
+    if not 1 <= Q <= _lib.SP_CLOUD_GRID_MAX_POINTS or int(grid['points'].shape[0]) != Q:
+        raise ValueError(f"{what}: a grid of {Q} points over a cloud of {int(grid['points'].shape[0])}")
+    return Q, grid['scratch']
+
+
+def _grid_scratch(grid, what):
+    """The library, once the handle's scratch has the size ``sp_cloud_grid_build`` wrote for its Q points (the last check: it needs the library)."""
+    lib = _lib.load()
+    Q, scratch = int(grid['Q']), grid['scratch']
+    if scratch.dtype != torch.int64 or not scratch.is_contiguous() or scratch.numel() != 8 * lib.sp_cloud_grid_scratch_units(Q):
+        raise ValueError(f"{what}: the grid's scratch ({scratch.dtype}, {scratch.numel()} elements) is not that of {Q} points")
+    return lib
+
+
 def nearest_points(queries, grid, skip_self=False):
     """ONE ``sp_cloud_grid_nearest`` call: per row of ``queries`` (Qa,3) float32 the nearest point of the cloud behind ``grid`` (what
     ``cloud_grid`` returned) within the grid's radius -- ``index`` (Qa,) int32, the lowest row on equal distance, -1 for none; ``dist``
     (Qa,) float32, +inf for none; ``count`` (Qa,) int32, the points within the radius.  ``skip_self``: the queries are the grid's own
     cloud (the same number of rows) and no row finds itself.  No synchronisation."""
-    if not isinstance(grid, dict) or any(k not in grid for k in ('scratch', 'Q', 'radius', 'origin', 'points')) \
-            or not torch.is_tensor(grid['scratch']) or not torch.is_tensor(grid['points']):
-        raise ValueError("nearest_points: grid must be what cloud_grid returned")
-    Q, scratch = int(grid['Q']), grid['scratch']
-    if not 1 <= Q <= _lib.SP_CLOUD_GRID_MAX_POINTS or int(grid['points'].shape[0]) != Q:
-        raise ValueError(f"nearest_points: a grid of {Q} points over a cloud of {int(grid['points'].shape[0])}")
+    Q, scratch = _grid_handle(grid, "nearest_points")
     _on_device(queries, scratch, grid['points'])
     qs = _f32(queries, (None, 3), "queries")
     Qa = int(qs.shape[0])
@@ -437,12 +453,81 @@ def nearest_points(queries, grid, skip_self=False):
         raise ValueError(f"nearest_points: {Qa} queries are beyond the kernel's limit of {2 ** 31 - 2}")
     if skip_self and Qa != Q:
         raise ValueError(f"nearest_points: skip_self with {Qa} queries against a grid of {Q} points (the queries must be the grid's cloud)")
-    lib = _lib.load()
-    if scratch.dtype != torch.int64 or not scratch.is_contiguous() or scratch.numel() != 8 * lib.sp_cloud_grid_scratch_units(Q):
-        raise ValueError(f"nearest_points: the grid's scratch ({scratch.dtype}, {scratch.numel()} elements) is not that of {Q} points")
+    lib = _grid_scratch(grid, "nearest_points")
     dev = qs.device
     out = dict(index=torch.empty(Qa, dtype=torch.int32, device=dev), dist=torch.empty(Qa, dtype=torch.float32, device=dev),
                count=torch.empty(Qa, dtype=torch.int32, device=dev))
     _lib.check(lib.sp_cloud_grid_nearest(_lib.ptr(qs), Qa, Q, _lib.ptr(scratch), 1 if skip_self else 0, _lib.ptr(out['index']), _lib.ptr(out['dist']),
                                          _lib.ptr(out['count']), _lib.stream_ptr()), "sp_cloud_grid_nearest")
     return out
+
+
+_RESIDUALS = {'point': 0, 'plane': 1, 'query_plane': 2}
+
+
+def register_clouds(queries, grid, normals=None, residual='point', T0=None, s0=1.0, scale=False, huber=None, tol=1e-6, min_pairs=None, max_iters=30):
+    """ONE ``sp_cloud_register`` call (include/sp_hip.h has the rule): the similarity x -> s R x + t that moves ``queries`` (Qa,3)
+    float32 onto the cloud behind ``grid`` (what ``cloud_grid`` returned; its radius is the correspondence radius), by Gauss-Newton ICP
+    from the start ``T0`` ((4,4), rotation and translation; default the identity) and ``s0``.  ``residual``: ``'point'`` (point to
+    point), ``'plane'`` (point to plane: ``normals`` (Q,3) float32, one row per GRID point) or ``'query_plane'`` (``normals`` (Qa,3)
+    float32, one row per QUERY: a map with normals against a cloud without).  ``scale``: the scale is an unknown too; ``huber``: the
+    Huber threshold (None or 0: every pair weighs 1); ``tol``: the step length at which it stops; ``min_pairs``: fewer pairs end it
+    (default: the number of unknowns); ``max_iters`` iterations are enqueued and the stop is decided on the device.
+    Returns ``dict(rot (3,3), trans (3,), s (), T (4,4) = [[s R, t], [0, 1]]`` float64, ``status`` () int32 (``_lib.SP_CLOUD_REG_*``),
+    ``iterations`` () int32, ``n`` () int64 (pairs of the last iteration), ``cost`` () float64, ``history`` (max_iters,4) float64 rows
+    {n, cost, step, status}, ``index`` (Qa,) int32 the last correspondences (-1: none))``, all on the device (views of one record).  No synchronisation, no host read."""
+    Q, scratch = _grid_handle(grid, "register_clouds")
+    if residual not in _RESIDUALS:
+        raise ValueError(f"register_clouds: residual {residual!r} (one of {sorted(_RESIDUALS)})")
+    kind = _RESIDUALS[residual]
+    if kind != 0 and normals is None:
+        raise ValueError(f"register_clouds: residual {residual!r} needs normals")
+    _on_device(queries, scratch, grid['points'], normals if kind != 0 else None)
+    qs = _f32(queries, (None, 3), "queries")
+    Qa = int(qs.shape[0])
+    if Qa == 0:
+        raise ValueError("register_clouds: no queries")
+    if Qa > 2 ** 31 - 2:
+        raise ValueError(f"register_clouds: {Qa} queries are beyond the kernel's limit of {2 ** 31 - 2}")
+    nrm = None
+    if kind != 0:
+        rows = Q if kind == 1 else Qa
+        nrm = _f32(normals, (rows, 3), f"normals (one row per {'grid point' if kind == 1 else 'query'})")
+    unknowns = 7 if scale else 6
+    try:
+        huber = 0.0 if huber is None else float(huber)
+        tol, s0 = float(tol), float(s0)
+        min_pairs = unknowns if min_pairs is None else int(min_pairs)
+        max_iters = int(max_iters)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"register_clouds: huber {huber!r}, tol {tol!r}, s0 {s0!r}, min_pairs {min_pairs!r}, max_iters {max_iters!r}: {e}") from None
+    if not (0.0 <= huber < float("inf")) or not (0.0 <= tol < float("inf")) or not (0.0 < s0 < float("inf")):
+        raise ValueError(f"register_clouds: huber {huber}, tol {tol} (finite, >= 0), s0 {s0} (finite, > 0)")
+    if min_pairs < unknowns or not 1 <= max_iters <= _lib.SP_CLOUD_REG_ITERS_LIMIT:
+        raise ValueError(f"register_clouds: min_pairs {min_pairs} (>= {unknowns} unknowns), max_iters {max_iters} (1 .. {_lib.SP_CLOUD_REG_ITERS_LIMIT})")
+    dev = qs.device
+    try:
+        start = torch.eye(4, dtype=torch.float64) if T0 is None else torch.as_tensor(T0, dtype=torch.float64).detach()
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"register_clouds: T0 {T0!r}: {e}") from None
+    if tuple(start.shape) != (4, 4):
+        raise ValueError(f"register_clouds: T0 must be (4,4), got {tuple(start.shape)}")
+    lib = _grid_scratch(grid, "register_clouds")
+    start = start.to(dev)
+    state = torch.zeros(64, dtype=torch.float64, device=dev)
+    state[:9] = start[:3, :3].reshape(9)
+    state[9:12] = start[:3, 3]
+    state[12] = s0
+    history = torch.empty(max_iters, 4, dtype=torch.float64, device=dev)
+    index = torch.empty(Qa, dtype=torch.int32, device=dev)
+    work = torch.empty(lib.sp_cloud_register_work_doubles(Qa), dtype=torch.float64, device=dev)
+    _lib.check(lib.sp_cloud_register(_lib.ptr(qs), _lib.ptr(nrm), Qa, Q, _lib.ptr(scratch), kind, 1 if scale else 0, huber, tol, min_pairs, max_iters,
+                                     _lib.ptr(state), _lib.ptr(history), _lib.ptr(index), _lib.ptr(work), _lib.stream_ptr()), "sp_cloud_register")
+    rot, trans, s = state[:9].view(3, 3), state[9:12], state[12]
+    T = torch.zeros(4, 4, dtype=torch.float64, device=dev)
+    T[:3, :3] = s * rot
+    T[:3, 3] = trans
+    T[3, 3] = 1.0
+    words = state.view(torch.int32)
+    return dict(rot=rot, trans=trans, s=s, T=T, status=words[2 * 58], iterations=words[2 * 58 + 1], n=state.view(torch.int64)[57], cost=state[55],
+                history=history, index=index)
