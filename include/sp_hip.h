@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SP_ABI_VERSION 19
+#define SP_ABI_VERSION 20
 
 #define SP_EINVAL (-1)   /* bad argument (null pointer, non-positive size, ...) */
 #define SP_ELIMIT (-2)   /* size outside what the kernels support (H or W > 32767, N > 65535, ...) */
@@ -90,7 +90,7 @@ int sp_pack_rgb(const float* chw, int B, int H, int W, float* hwc3, void* stream
 /* One pyramid step of image/gaussian_pyramid.py:53-85: reflect-pad 1, 3x3 binomial /16, keep even rows and
  * columns.  in: planar (C,H,W); out: planar (C,ceil(H/2),ceil(W/2)).  A dimension of ONE pixel has nothing to
  * reflect onto (torch refuses that padding): the pixel itself is taken, so a 1 x 1 level blurs to itself --
- * here and in the batched passes (sp_prepare_blur, sp_prepare_blur_pack). */
+ * here and in the batched pass (sp_prepare_blur_pack). */
 int sp_blur_decimate(const float* in, int C, int H, int W, float* out, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
@@ -103,9 +103,8 @@ int sp_blur_decimate(const float* in, int C, int H, int W, float* out, void* str
  *                      words (SpPrepTable.bits)                                                     [masks read once]
  *   -- host: reads counts, lays the segments out (runs padded to multiples of 256), allocates pix / baseL, uploads seg_off --
  *   sp_prepare_fill  : pix / baseL at seg_off[n] + rank inside the segment; kp_L[N] where kp_L != NULL
- *   sp_prepare_blur  : one pyramid step (sp_blur_decimate) of every job image
  *   sp_prepare_pack  : planar (3,H,W) -> HWC3 of every job image
- *   sp_prepare_blur_pack: both at once for three-channel images (the target frames)
+ *   sp_prepare_blur_pack: one pyramid step (sp_blur_decimate) of every three-channel job image (the target frames) and the packing at once
  *   sp_prepare_gather: n small float vectors, one DEVICE pointer each (src[i], off[i + 1] - off[i] floats), into one flat array
  *                      (out + off[i]); src and off are device arrays.  What the host side otherwise does with one torch.cat /
  *                      torch.stack over hundreds of per-pair tensors (the intrinsics and initial log-depths of a batch: 0.7 us of
@@ -168,7 +167,7 @@ typedef struct SpPrepSample {    /* one table, sampled at up to SP_PREP_MAX_LEVE
 #define SP_PREP_DENSE_L 0x20000
 typedef struct SpPrepImage {
     const float* in;             /* (C,H,W) planar */
-    float* out;                  /* blur: (C,ceil(H/2),ceil(W/2)); pack: (H,W,3) */
+    float* out;                  /* (H,W,3) */
     int32_t H, W;
 } SpPrepImage;                   /* 24 bytes */
 int sp_prepare_count(const SpPrepTable* tables, int n_tables, int max_rows, int max_N, void* stream);
@@ -183,9 +182,9 @@ int sp_prepare_sample(const SpPrepSample* jobs, int n_jobs, int max_P, void* str
  * take consecutive workgroups, so that a source image both tables gather from (the all-points table and the stride-2 lattice, both sampled at
  * level 0) is fetched from memory once.  Same outputs as two sp_prepare_sample calls, bit for bit. */
 int sp_prepare_sample_pairs(const SpPrepSample* jobs_a, int max_P_a, const SpPrepSample* jobs_b, int max_P_b, int n_jobs, void* stream);
-int sp_prepare_blur(const SpPrepImage* jobs, int n_jobs, int C, int max_out_pixels, void* stream);
+/* (ABI 20) retired: sp_prepare_blur, the planar-only pyramid step of a batch -- the set-up uses sp_prepare_blur_pack. */
 int sp_prepare_pack(const SpPrepImage* jobs, int n_jobs, int max_pixels, void* stream);
-/* One pyramid step of THREE-CHANNEL images together with their packed forms (ABI 14): what sp_prepare_blur followed by sp_prepare_pack
+/* One pyramid step of THREE-CHANNEL images together with their packed forms (ABI 14): what sp_blur_decimate followed by sp_pack_rgb
  * computes, bit for bit, without the packing pass's re-read of the planar levels.  out (planar level l + 1), packed_out (level l + 1 as
  * HWC3) and packed_in (level l as HWC3) may each be NULL. */
 typedef struct SpPrepImagePack {
@@ -827,18 +826,15 @@ int sp_segment_reinit(const uint32_t* pix, const float* baseL, const int32_t* se
  *   - a covering segment counts iff it is visible and its depth d > 1e-6 (a NaN or a vanishing depth is skipped);
  *   - out_depth = sum / (count + 1e-6), the reference's divisor: about 1e-6 below the plain mean for count 1, and 0 / 1e-6 = 0
  *     where nothing counts;
- *   - out_invalid = (count == 0). */
-int sp_depth_average(const uint32_t* pix, const float* baseL, const int32_t* seg_off, const float* kp_L,
-                     const float* kld, const uint8_t* visible, int N, int P, int H, int W, void* acc,
-                     float* out_depth, uint8_t* out_invalid, void* stream);
-
-/* The two halves of sp_depth_average, for SEGMENT-SHARDED depth completion (BASELINE.json configs[3], SURVEY.md
- * section 8(e)): every rank accumulates its own segments into acc = {sums[H*W] uint64 (32.32 fixed point), counts[H*W]
+ *   - out_invalid = (count == 0).
+ * Two calls, sp_depth_accumulate then sp_depth_average_finish, so that SEGMENT-SHARDED depth completion (BASELINE.json configs[3],
+ * SURVEY.md section 8(e)) uses the calls a single GPU uses: every rank accumulates its own segments into acc = {sums[H*W] uint64 (32.32 fixed point), counts[H*W]
  * uint32}, the ranks all_reduce(SUM) the two integer arrays (exact and order independent, so the result is bitwise the
  * single-GPU one; a pixel is invalid iff its summed count is 0, i.e. the OR of the per-rank validity), rank-local finish. */
 int sp_depth_accumulate(const uint32_t* pix, const float* baseL, const int32_t* seg_off, const float* kp_L,
                         const float* kld, const uint8_t* visible, int N, int P, int H, int W, void* acc, void* stream);
 int sp_depth_average_finish(const void* acc, int H, int W, float* out_depth, uint8_t* out_invalid, void* stream);
+/* (ABI 20) retired: sp_depth_average, the wrapper that made the two calls above. */
 
 /* The pose parameter of the reference's drivers, T[b] = Exp(a[b]) * X[b]  (a = [tau, phi] (n,6); X, T (n,4,4)):
  * lietorch's LieGroupParameter.retr().matrix() at odometery/two_frame_sfm.py:83-84, odometery/odometery.py:224-228.
@@ -1029,14 +1025,12 @@ int sp_depth_ingest(const uint16_t* raw, int B, int H, int W, float scale, float
                     int Wo, float* out, void* stream);
 
 /* odometery/kf_criteria.py:7-21 translation_difference, :23-34 rotation_difference and the depth-validity ratio of
- * odometery/odometery.py:1003-1004, in one launch without a host sync.  depth: n floats (the rendered depth of the
+ * odometery/odometery.py:1003-1004, without a host sync.  depth: n floats (the rendered depth of the
  * latest keyframe); poses row-major 4x4.  out[4] = {#(depth > thresh)/n, scale = lower median of the valid depths
  * (torch.median; NaN when none is valid), |t_src - t_trg| / (scale + 1e-6), rotation angle of
- * inv(pose_src) pose_trg in degrees}. */
-int sp_kf_criterion(const float* depth, int n, float thresh, const float* pose_src, const float* pose_trg, float* out,
-                    void* stream);
-/* The same four values -- bit for bit -- from a grid of workgroups instead of one (one launch per radix pass; 102 -> 17 us on a 640 x 480
- * render): ws = sp_kf_criterion_ws_words() uint32 of scratch, any content. */
+ * inv(pose_src) pose_trg in degrees}, from a grid of workgroups (one launch per radix pass; 17 us on a 640 x 480 render):
+ * ws = sp_kf_criterion_ws_words() uint32 of scratch, any content. */
+/* (ABI 20) retired: sp_kf_criterion, the one-workgroup form (102 us on that render). */
 int sp_kf_criterion_ws_words(void);
 int sp_kf_criterion_ws(const float* depth, int n, float thresh, const float* pose_src, const float* pose_trg, uint32_t* ws, float* out,
                        void* stream);

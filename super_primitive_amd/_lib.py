@@ -40,7 +40,6 @@ SIGNATURES = {
     "sp_prepare_fill": [P, I, I, I, P],
     "sp_prepare_sample": [P, I, I, P],
     "sp_prepare_sample_pairs": [P, I, P, I, I, P],
-    "sp_prepare_blur": [P, I, I, I, P],
     "sp_prepare_pack": [P, I, I, P],
     "sp_prepare_blur_pack": [P, I, I, P],
     "sp_prepare_gather": [P, P, I, P, P],
@@ -64,10 +63,8 @@ SIGNATURES = {
     "sp_depth_splat_mean": [P, P, P, P, P, I, I, I, I, P, P, P, P, P],
     "sp_depth_splat": [P, P, P, P, P, I, I, I, I, P, P, P, P, P],
     "sp_segment_reinit": [P, P, P, P, I, I, I, I, P, I, P, P, P, P],
-    "sp_depth_average": [P, P, P, P, P, P, I, I, I, I, P, P, P, P],
     "sp_depth_accumulate": [P, P, P, P, P, P, I, I, I, I, P, P],
     "sp_depth_average_finish": [P, I, I, P, P, P],
-    "sp_kf_criterion": [P, I, F, P, P, P, P],
     "sp_chain_multi_bytes": [],
     "sp_chain_step_multi": [P, I, P, P, P, P],
     "sp_kf_criterion_ws_words": [],
@@ -114,7 +111,7 @@ SIGNATURES = {
     "sp_cloud_register": [P, P, ctypes.c_longlong, ctypes.c_longlong, P, I, I, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, I, P, P, P, P, P],
 }
 
-SP_ABI_VERSION = 19
+SP_ABI_VERSION = 20
 SP_GRAD_PARTIAL_FLOATS = 16
 SP_GN_PARTIAL_FLOATS = 32
 SP_GNA_PARTIAL_FLOATS = 48

@@ -4,24 +4,6 @@
 
 namespace {
 
-__device__ __forceinline__ int segment_of(const int32_t* __restrict__ seg_off, int N, int i) {
-    int lo = 0, hi = N;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_off[mid] <= i) lo = mid; else hi = mid; }
-    while (lo + 1 < N && seg_off[lo + 1] <= i) ++lo;
-    return lo;
-}
-
-__device__ __forceinline__ float keypoint_L(const float* __restrict__ logdepth, const float* __restrict__ keypoints,
-                                            int n, int H, int W) {
-    int r = (int)rintf(0.5f * (float)(H - 1) * (keypoints[2 * n] + 1.f));
-    int c = (int)rintf(0.5f * (float)(W - 1) * (keypoints[2 * n + 1] + 1.f));
-    if (r < 0) r += H;
-    if (c < 0) c += W;
-    r = min(max(r, 0), H - 1);
-    c = min(max(c, 0), W - 1);
-    return logdepth[((size_t)n * H + r) * W + c];
-}
-
 // core/dense_optim.py:38-86,164-174: out = exp((L + (kld[n] - L[n,kp])) * mask), dense
 __global__ __launch_bounds__(SP_BLOCK) void k_depth_expand(const uint8_t* __restrict__ masks, const float* __restrict__ logdepth,
                                                            const float* __restrict__ keypoints, const float* __restrict__ kld,
@@ -45,7 +27,7 @@ __device__ __forceinline__ void table_point(const uint32_t* __restrict__ pix, co
     n = segment_of(seg_off, N, i);
     const uint32_t pw = pix[i] & 0x7fffffffu;
     const float col = (float)(pw & 0xffffu), row = (float)(pw >> 16);
-    d = expf(baseL[i] + (kld[n] - kp_L[n]));
+    d = table_point_depth(baseL, kld, kp_L, i, n);
     x = __fdiv_rn(__fmul_rn(col - K9[2], d), K9[0]);
     y = __fdiv_rn(__fmul_rn(row - K9[5], d), K9[4]);
 }
@@ -246,7 +228,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_average_scatter(const uint32_t* __
     if (i >= P) return;
     const int n = segment_of(seg_off, N, i);
     if (visible && !visible[n]) return;
-    const float d = expf(baseL[i] + (kld[n] - kp_L[n]));
+    const float d = table_point_depth(baseL, kld, kp_L, i, n);
     if (!(d > 1e-6f)) return;
     const uint32_t pw = pix[i] & 0x7fffffffu;
     const size_t o = (size_t)(pw >> 16) * W + (pw & 0xffffu);
@@ -266,75 +248,14 @@ __global__ __launch_bounds__(SP_BLOCK) void k_average_finish(const unsigned long
 }
 
 // ---------------------------------------------------------------------------------------------------
-// odometery/kf_criteria.py:7-34 + the validity ratio of odometery/odometery.py:1003-1004, one launch, no host sync:
+// odometery/kf_criteria.py:7-34 + the validity ratio of odometery/odometery.py:1003-1004, no host sync:
 //   out[0] = #(depth > thresh) / n            out[1] = scale = lower median of the valid depths (torch.median)
 //   out[2] = |t_src - t_trg| / (scale + 1e-6) out[3] = rotation angle of inv(pose_src) pose_trg in degrees
-// Single workgroup: one counting pass + 4 radix passes over an image that sits in L2.
 // ---------------------------------------------------------------------------------------------------
-constexpr int KF_BLOCK = 1024;
-__global__ __launch_bounds__(KF_BLOCK) void k_kf_criterion(const float* __restrict__ depth, int n, float thresh,
-                                                           const float* __restrict__ pose_src,
-                                                           const float* __restrict__ pose_trg, float* __restrict__ out) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t chosen, remaining;
-    if (threadIdx.x < 256) hist[threadIdx.x] = 0;
-    __syncthreads();
-    // pass 0: the valid count and the top-byte histogram together (depth > thresh > 0 => raw bits are orderable)
-    for (int i = threadIdx.x; i < n; i += KF_BLOCK) {
-        const float v = depth[i];
-        if (v > thresh) atomicAdd(&hist[__float_as_uint(v) >> 24], 1u);
-    }
-    __syncthreads();
-    uint32_t cnt = 0;
-    for (int b = 0; b < 256; ++b) cnt += hist[b];           // every thread: same value, LDS broadcast reads
-    uint32_t prefix = 0, mask = 0;
-    uint32_t k = cnt ? (cnt - 1u) / 2u : 0u;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (shift != 24) {
-            __syncthreads();
-            if (threadIdx.x < 256) hist[threadIdx.x] = 0;
-            __syncthreads();
-            for (int i = threadIdx.x; i < n; i += KF_BLOCK) {
-                const float v = depth[i];
-                const uint32_t key = __float_as_uint(v);
-                if (v > thresh && (key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 0xffu], 1u);
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            uint32_t run = 0; int b = 0;
-            for (; b < 255; ++b) { if (run + hist[b] > k) break; run += hist[b]; }
-            chosen = (uint32_t)b; remaining = k - run;
-        }
-        __syncthreads();
-        prefix |= chosen << shift;
-        mask |= 0xffu << shift;
-        k = remaining;
-    }
-    if (threadIdx.x == 0) {
-        const float scale = cnt ? __uint_as_float(prefix) : __builtin_nanf("");     // torch.median of nothing raises
-        out[0] = (float)cnt / (float)n;
-        out[1] = scale;
-        const float dx = pose_src[3] - pose_trg[3], dy = pose_src[7] - pose_trg[7], dz = pose_src[11] - pose_trg[11];
-        out[2] = sqrtf(dx * dx + dy * dy + dz * dz) / (scale + 1e-6f);
-        // rotation part of inv(pose_src) @ pose_trg = R_s^T R_t; angle = atan2(|axis part|, (trace - 1) / 2), in fp64
-        double D[9];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double a = 0.0;
-                for (int m = 0; m < 3; ++m) a += (double)pose_src[4 * m + i] * (double)pose_trg[4 * m + j];
-                D[3 * i + j] = a;
-            }
-        const double ax = D[7] - D[5], ay = D[2] - D[6], az = D[3] - D[1];
-        const double sn = 0.5 * sqrt(ax * ax + ay * ay + az * az), cs = 0.5 * (D[0] + D[4] + D[8] - 1.0);
-        out[3] = (float)(atan2(sn, cs) * 57.29577951308232);
-    }
-}
-
-// The same four values from a GRID of workgroups (sp_kf_criterion_ws): one launch per radix pass -- every workgroup histograms its slice
+// A GRID of workgroups (sp_kf_criterion_ws): one launch per radix pass -- every workgroup histograms its slice
 // of the image in LDS and adds it to the pass's global histogram; the workgroup that finishes last picks the digit (and, after the last
 // pass, writes out[]).  ws: KF_WS_WORDS uint32, zeroed by the entry point: [pass * 256 + bin] histograms, then {prefix, k, count, -} and
-// the four passes' tickets.  Exactly k_kf_criterion's selection -- the k-th smallest key -- so the same bits come out.
+// the four passes' tickets.  The selection is the k-th smallest key, k = (count - 1) / 2: depth > thresh >= 0, so the raw bits are orderable.
 constexpr int KF_WS_WORDS = 4 * 256 + 8;
 constexpr int KF_GRID_BLOCK = 256, KF_PER_THREAD = 16;
 // (the body of k_kf_select_pass; n_groups = the workgroups of ONE criterion -- the last of them to arrive finishes the pass)
@@ -382,11 +303,12 @@ __device__ __forceinline__ void kf_select_pass_body(const float* __restrict__ de
     const uint32_t pre = prefix | ((uint32_t)b << shift);
     st[0] = pre; st[1] = k - run;
     if (pass != 3) return;
-    const float scale = cnt ? __uint_as_float(pre) : __builtin_nanf("");
+    const float scale = cnt ? __uint_as_float(pre) : __builtin_nanf("");            // torch.median of nothing raises
     out[0] = (float)cnt / (float)n;
     out[1] = scale;
     const float dx = pose_src[3] - pose_trg[3], dy = pose_src[7] - pose_trg[7], dz = pose_src[11] - pose_trg[11];
     out[2] = sqrtf(dx * dx + dy * dy + dz * dz) / (scale + 1e-6f);
+    // rotation part of inv(pose_src) @ pose_trg = R_s^T R_t; angle = atan2(|axis part|, (trace - 1) / 2), in fp64
     double D[9];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) {
@@ -520,24 +442,6 @@ int sp_depth_average_finish(const void* acc, int H, int W, float* out_depth, uin
     const uint32_t* counts = reinterpret_cast<const uint32_t*>(sums + HW);
     hipLaunchKernelGGL(k_average_finish, dim3((unsigned)((HW + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0,
                        static_cast<hipStream_t>(stream), sums, counts, (int)HW, out_depth, out_invalid);
-    SP_CHECK_LAUNCH();
-    return 0;
-}
-
-int sp_depth_average(const uint32_t* pix, const float* baseL, const int32_t* seg_off, const float* kp_L,
-                     const float* kld, const uint8_t* visible, int N, int P, int H, int W, void* acc,
-                     float* out_depth, uint8_t* out_invalid, void* stream) {
-    if (!out_depth || !out_invalid) return SP_EINVAL;
-    const int rc = sp_depth_accumulate(pix, baseL, seg_off, kp_L, kld, visible, N, P, H, W, acc, stream);
-    if (rc != 0) return rc;
-    return sp_depth_average_finish(acc, H, W, out_depth, out_invalid, stream);
-}
-
-int sp_kf_criterion(const float* depth, int n, float thresh, const float* pose_src, const float* pose_trg, float* out,
-                    void* stream) {
-    if (!depth || !pose_src || !pose_trg || !out || n <= 0 || !(thresh >= 0.f)) return SP_EINVAL;
-    hipLaunchKernelGGL(k_kf_criterion, dim3(1), dim3(KF_BLOCK), 0, static_cast<hipStream_t>(stream), depth, n, thresh,
-                       pose_src, pose_trg, out);
     SP_CHECK_LAUNCH();
     return 0;
 }

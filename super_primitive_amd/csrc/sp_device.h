@@ -104,6 +104,16 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 // Reduce NV per-thread accumulators over the block; thread k < NV ends up holding the total of value k.
 //
@@ -202,6 +212,32 @@ struct PointGeom {
     float ix, iy;       // sampling position in LEVEL pixels
     bool  valid;        // target validity & source validity
 };
+
+// the segment of table point i: the last one whose offset is at or before it
+__device__ __forceinline__ int segment_of(const int32_t* __restrict__ seg_off, int N, int i) {
+    int lo = 0, hi = N;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_off[mid] <= i) lo = mid; else hi = mid; }
+    while (lo + 1 < N && seg_off[lo + 1] <= i) ++lo;       // (empty segments share an offset with their successor)
+    return lo;
+}
+
+// tool/point_utils.py:37-40 + core/dense_optim.py:51-59: L of segment n at its rounded keypoint pixel
+__device__ __forceinline__ float keypoint_L(const float* __restrict__ logdepth, const float* __restrict__ keypoints, int n, int H, int W) {
+    int r = (int)rintf(0.5f * (float)(H - 1) * (keypoints[2 * n] + 1.f));           // rintf = half-to-even
+    int c = (int)rintf(0.5f * (float)(W - 1) * (keypoints[2 * n + 1] + 1.f));
+    // torch advanced indexing wraps negative indices once; anything else is an error upstream -- clamp here
+    if (r < 0) r += H;
+    if (c < 0) c += W;
+    r = min(max(r, 0), H - 1);
+    c = min(max(c, 0), W - 1);
+    return logdepth[((size_t)n * H + r) * W + c];
+}
+
+// core/dense_optim.py:38-86: the depth of table point i of segment n, d = exp(L + (kld[n] - L[n,kp])).  (Plain pointers on purpose:
+// callers pass record members as well as kernel arguments, and __restrict__ here perturbs k_keyframe_depth_keys' machine code.)
+__device__ __forceinline__ float table_point_depth(const float* baseL, const float* kld, const float* kp_L, int i, int n) {
+    return expf(baseL[i] + (kld[n] - kp_L[n]));
+}
 
 // pix word: bit31 source validity, bits 30..16 row, bits 15..0 col
 __device__ __forceinline__ void decode_pix(uint32_t w, float& col, float& row, bool& src_ok) {

@@ -25,12 +25,6 @@ constexpr int16_t OFF_NONE = -32768;
 constexpr int MT_VALUES = 12;
 constexpr int MT_PIXELS = 8 * SP_BLOCK;       // pixels of one image per workgroup of the first stage
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- fill ---------------------------------------------------------------------------------------------------------
 // grid (ceil(W / FC_COLS), B), block (FC_COLS, FC_SEGS): thread = one of FC_SEGS runs of rows of one column of one image.  A run first
 // finds its own first and last valid row; the nearest valid row above (below) the run is then the last (first) one of the nearest run
@@ -56,7 +50,7 @@ __global__ __launch_bounds__(FC_COLS * FC_SEGS) void k_fill_columns(const uint8_
     }
     first_valid[seg][lane] = first;
     last_valid[seg][lane] = last;
-    n_valid = wave_sum_int(n_valid);                              // a wave is one run of the block's 64 columns
+    n_valid = wave_sum(n_valid);                                  // a wave is one run of the block's 64 columns
     if (lane == 0) n_valid_of[seg] = n_valid;
     __syncthreads();
     if (c < W) {

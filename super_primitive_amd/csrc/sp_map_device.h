@@ -204,13 +204,8 @@ __device__ __forceinline__ int keyframe_of_block(const SpMapKeyframe* __restrict
     return lo;
 }
 
-// the segment of table point i: the last one whose offset is at or before it
-__device__ __forceinline__ int map_point_segment(const SpMapKeyframe& kf, int i) {
-    int s0 = 0, s1 = kf.N;
-    while (s1 - s0 > 1) { const int mid = (s0 + s1) >> 1; if (kf.seg_off[mid] <= i) s0 = mid; else s1 = mid; }
-    while (s0 + 1 < kf.N && kf.seg_off[s0 + 1] <= i) ++s0;              // (empty segments share an offset with their successor)
-    return s0;
-}
+// the segment of table point i of a keyframe
+__device__ __forceinline__ int map_point_segment(const SpMapKeyframe& kf, int i) { return segment_of(kf.seg_off, kf.N, i); }
 
 // ---- views: one record per view in float64, the projection, a footprint's half-width (sp_views.hip and sp_surfel.hip; the arithmetic
 // carries its own contraction pragma: every operation is rounded on its own whatever the including file allows) ----------------------

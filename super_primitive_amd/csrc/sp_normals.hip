@@ -38,16 +38,10 @@ __host__ __device__ inline long long ni_len(int bh, int bw) {
     return bh > 0 ? ((bh * S + 2 * S + 15) & ~15LL) : 0;
 }
 
-__device__ __forceinline__ float ni_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);       // x + y == y + x: every lane ends with the same bits
-    return v;
-}
-
 // Sum over the workgroup, the same bits in every thread (fixed order: lanes by butterfly, then waves 0..15).  `red` is
 // one of two LDS rows used alternately: the barrier of call k+1 separates the reads of call k from the writes of k+2.
 __device__ __forceinline__ float ni_block_sum(float v, float* red) {
-    v = ni_wave_sum(v);
+    v = wave_sum(v);                                          // x + y == y + x: every lane ends with the same bits
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     float s = 0.f;

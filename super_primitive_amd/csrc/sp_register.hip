@@ -10,7 +10,7 @@
 //                      g, g + 25, ..., its lanes one 16-byte pair of a record each, eight loads in flight; then the 25 running sums in
 //                      order -- a 256-thread form with 8-byte loads took 203 us for the 4096 records of 2^20 queries, more than half
 //                      a pass over the cloud: profiles/cloud_register.txt), thread 0 solves H delta = -g by LDL^T
-//                      (ldlt6_solve / ldlt7_solve of sp_solve_device.h), moves the transform on the left, decides the status and writes
+//                      (ldlt_solve<6> / ldlt_solve<7> of sp_solve_device.h), moves the transform on the left, decides the status and writes
 //                      the state and the iteration's row of the history.
 // The stop is decided on the device: both kernels begin with one uniform load of state->status and return when it is not RUNNING (the
 // solve kernel then still writes its history row).  No floating-point atomics, no workgroup waits on another, every loop is bounded.
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(REG_SOLVE_BLOCK) void k_register_solve(const double
             for (int a = 0; a < 7; ++a)
                 for (int b = a; b < 7; ++b) { S[7 * a + b] = sums[e]; S[7 * b + a] = sums[e]; ++e; }
             for (int a = 0; a < 7; ++a) rhs[a] = -sums[REG_H + a];
-            ok = ldlt7_solve(S, rhs);
+            ok = ldlt_solve<7>(S, rhs);
             for (int a = 0; a < 7; ++a) delta[a] = ok ? rhs[a] : 0.0;
         } else {
             double S[36], rhs[6];
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(REG_SOLVE_BLOCK) void k_register_solve(const double
                     ++e;
                 }
             for (int a = 0; a < 6; ++a) rhs[a] = -sums[REG_H + a];
-            ok = ldlt6_solve(S, rhs);
+            ok = ldlt_solve<6>(S, rhs);
             for (int a = 0; a < 6; ++a) delta[a] = ok ? rhs[a] : 0.0;
         }
         if (!ok) status = SP_CLOUD_REG_DEGENERATE;

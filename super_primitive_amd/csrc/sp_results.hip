@@ -22,18 +22,12 @@ static_assert(sizeof(SpTrajAlign) == 256 && sizeof(SpMapKeyframe) == 96, "result
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // every thread ends up with the block's totals of its NV accumulators; red: SP_WAVES * NV doubles of LDS
 template <int NV>
 __device__ __forceinline__ void block_sum_d(double (&acc)[NV], double* red) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < NV; ++k) acc[k] = wave_sum_d(acc[k]);
+    for (int k = 0; k < NV; ++k) acc[k] = wave_sum(acc[k]);
     __syncthreads();                                       // (the previous totals have been read)
     if (lane == 0) {
 #pragma unroll
@@ -213,11 +207,6 @@ __global__ __launch_bounds__(SP_BLOCK) void k_traj_align(const float* __restrict
     if (tid == 0) { rec.ate_scaled = sqrt(sq[0] / nd); rec.ate = sqrt(sq[1] / nd); }
 }
 
-// the camera-frame depth of table point i of segment n: one function for sp_map_points and sp_keyframe_depths
-__device__ __forceinline__ float map_point_depth(const SpMapKeyframe& kf, int i, int n) {
-    return expf(kf.baseL[i] + (kf.kld[n] - kf.kp_L[n]));
-}
-
 // grid total_blocks, block SP_BLOCK
 __global__ __launch_bounds__(SP_BLOCK) void k_map_points(const SpMapKeyframe* __restrict__ kfs, int n_kf, int stride,
                                                          const SpTrajAlign* __restrict__ align, int n_align, float* __restrict__ points,
@@ -262,7 +251,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_map_points(const SpMapKeyframe* __
         const int n = map_point_segment(kf, i);
         float col, row; bool src_ok;
         decode_pix(kf.pix[i], col, row, src_ok);
-        const float d = map_point_depth(kf, i, n);
+        const float d = table_point_depth(kf.baseL, kf.kld, kf.kp_L, i, n);
         Cam Ks;
         load_cam(kf.K, Ks);
         float x, y;
@@ -299,7 +288,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_keyframe_depth_keys(const SpMapKey
     const int n = map_point_segment(kf, i);
     float col, row; bool src_ok;
     decode_pix(kf.pix[i], col, row, src_ok);
-    const float z = map_point_depth(kf, i, n);
+    const float z = table_point_depth(kf.baseL, kf.kld, kf.kp_L, i, n);
     if (!(z > 0.f && z < HUGE_VALF)) return;               // NaN, 0 (underflow), inf: no surface
     const int r = (int)row, c = (int)col;
     if (r >= H || c >= W) return;                          // (a table of another size: never written beyond the image)

@@ -81,6 +81,35 @@ __device__ void se3_retract_left(const double xi[6], float* T16) {
     T16[12] = 0.f; T16[13] = 0.f; T16[14] = 0.f; T16[15] = 1.f;
 }
 
+// Exp(xi) for xi = [tau, phi] as a 3x4 double matrix: the closed form of se3_retract_left, kept in double
+__device__ void se3_exp_d(const double xi[6], double E[12]) {
+    const double wx = xi[3], wy = xi[4], wz = xi[5];
+    const double th2 = wx * wx + wy * wy + wz * wz;
+    double A, B, C;
+    if (th2 < 1e-4) {
+        A = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0);
+        B = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0);
+        C = 1.0 / 6.0 - th2 / 120.0 * (1.0 - th2 / 42.0);
+    } else {
+        const double th = sqrt(th2);
+        const double sn = sin(th), cs = cos(th);
+        A = sn / th; B = (1.0 - cs) / th2; C = (th - sn) / (th2 * th);
+    }
+    const double W[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
+    double W2[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) W2[3 * i + j] = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
+    for (int i = 0; i < 3; ++i) {
+        double Vrow[3];
+        for (int j = 0; j < 3; ++j) {
+            const double I = (i == j) ? 1.0 : 0.0;
+            E[4 * i + j] = I + A * W[3 * i + j] + B * W2[3 * i + j];
+            Vrow[j] = I + B * W[3 * i + j] + C * W2[3 * i + j];
+        }
+        E[4 * i + 3] = Vrow[0] * xi[0] + Vrow[1] * xi[1] + Vrow[2] * xi[2];
+    }
+}
+
 // torch.optim.Adam (betas 0.9/0.999, eps 1e-8, no weight decay, no amsgrad) on one fp32 scalar, in torch's operation
 // order: exp_avg.lerp_(g, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, value=1-b2); denom = sqrt(v)/sqrt(bc2) + eps;
 // p.addcdiv_(m, denom, value=-lr/bc1).  The bias corrections are Python doubles there, cast to fp32 at the op:
@@ -174,61 +203,33 @@ __device__ __forceinline__ void solve_adam(const SpPair* __restrict__ pairs, int
 // lm_state per pair (8 floats): [0] lambda  [1] cost of the last accepted point (<0: none yet)
 //                               [2] #accepted  [3] #rejected  [4] 1 if the previous call rejected  [5] last cost seen
 
-// Solve the symmetric positive definite 6x6 system S x = rhs by LDL^T (no square roots, six reciprocals);
-// x is returned in rhs.  false if a pivot is not positive.
-__device__ bool ldlt6_solve(double S[36], double rhs[6]) {
-    double dinv[6];
-    for (int j = 0; j < 6; ++j) {
-        double d = S[7 * j];
-        for (int k = 0; k < j; ++k) d -= S[6 * j + k] * S[6 * j + k] * S[7 * k];
+// Solve the symmetric positive definite N x N system S x = rhs by LDL^T (no square roots, N reciprocals); S row major (the lower
+// triangle is read), x is returned in rhs.  false if a pivot is not positive.  N = 6: a pose; N = 7: a similarity (rotation,
+// translation, log-scale; sp_register.hip) -- the same operations in the same order.
+template <int N>
+__device__ bool ldlt_solve(double S[N * N], double rhs[N]) {
+    double dinv[N];
+    for (int j = 0; j < N; ++j) {
+        double d = S[(N + 1) * j];
+        for (int k = 0; k < j; ++k) d -= S[N * j + k] * S[N * j + k] * S[(N + 1) * k];
         if (!(d > 0.0)) return false;
-        S[7 * j] = d;
+        S[(N + 1) * j] = d;
         dinv[j] = 1.0 / d;
-        for (int i = j + 1; i < 6; ++i) {
-            double v = S[6 * i + j];
-            for (int k = 0; k < j; ++k) v -= S[6 * i + k] * S[6 * j + k] * S[7 * k];
-            S[6 * i + j] = v * dinv[j];
+        for (int i = j + 1; i < N; ++i) {
+            double v = S[N * i + j];
+            for (int k = 0; k < j; ++k) v -= S[N * i + k] * S[N * j + k] * S[(N + 1) * k];
+            S[N * i + j] = v * dinv[j];
         }
     }
-    for (int i = 0; i < 6; ++i) {            // L y = rhs
+    for (int i = 0; i < N; ++i) {            // L y = rhs
         double v = rhs[i];
-        for (int k = 0; k < i; ++k) v -= S[6 * i + k] * rhs[k];
+        for (int k = 0; k < i; ++k) v -= S[N * i + k] * rhs[k];
         rhs[i] = v;
     }
-    for (int i = 0; i < 6; ++i) rhs[i] *= dinv[i];
-    for (int i = 5; i >= 0; --i) {           // L^T x = y
+    for (int i = 0; i < N; ++i) rhs[i] *= dinv[i];
+    for (int i = N - 1; i >= 0; --i) {       // L^T x = y
         double v = rhs[i];
-        for (int k = i + 1; k < 6; ++k) v -= S[6 * k + i] * rhs[k];
-        rhs[i] = v;
-    }
-    return true;
-}
-
-// Its sibling for 7 unknowns (a similarity: rotation, translation, log-scale; sp_register.hip): the same operations in the same order,
-// S row major 7 x 7 (the lower triangle is read), x returned in rhs.  false if a pivot is not positive.
-__device__ bool ldlt7_solve(double S[49], double rhs[7]) {
-    double dinv[7];
-    for (int j = 0; j < 7; ++j) {
-        double d = S[8 * j];
-        for (int k = 0; k < j; ++k) d -= S[7 * j + k] * S[7 * j + k] * S[8 * k];
-        if (!(d > 0.0)) return false;
-        S[8 * j] = d;
-        dinv[j] = 1.0 / d;
-        for (int i = j + 1; i < 7; ++i) {
-            double v = S[7 * i + j];
-            for (int k = 0; k < j; ++k) v -= S[7 * i + k] * S[7 * j + k] * S[8 * k];
-            S[7 * i + j] = v * dinv[j];
-        }
-    }
-    for (int i = 0; i < 7; ++i) {            // L y = rhs
-        double v = rhs[i];
-        for (int k = 0; k < i; ++k) v -= S[7 * i + k] * rhs[k];
-        rhs[i] = v;
-    }
-    for (int i = 0; i < 7; ++i) rhs[i] *= dinv[i];
-    for (int i = 6; i >= 0; --i) {           // L^T x = y
-        double v = rhs[i];
-        for (int k = i + 1; k < 7; ++k) v -= S[7 * k + i] * rhs[k];
+        for (int k = i + 1; k < N; ++k) v -= S[N * k + i] * rhs[k];
         rhs[i] = v;
     }
     return true;
@@ -420,7 +421,7 @@ __device__ __forceinline__ void solve_gn(const SpPair* __restrict__ pairs, int p
                 ++k;
             }
         for (int i = 0; i < 6; ++i) rhs[i] = -(sums[22 + i] - schur[21 + i]);
-        const bool ok = ldlt6_solve(S, rhs);
+        const bool ok = ldlt_solve<6>(S, rhs);
         for (int i = 0; i < 6; ++i) dxi[i] = ok ? rhs[i] : 0.0;
         ls[0] = lambda; ls[1] = (float)cost; ls[2] += 1.f; ls[4] = 0.f;
     }

@@ -2,7 +2,7 @@
 // from the float32 inputs, every operation rounded on its own (contraction is switched off for this file: the reference is NumPy in
 // float64), rounded to float32 once.
 //
-// sp_map_normals.  sp_map_points' walk (keyframe_of_block, map_point_segment: sp_map_device.h), one thread per output row, a workgroup
+// sp_map_normals.  sp_map_points' walk (keyframe_of_block: sp_map_device.h; segment_of: sp_device.h), one thread per output row, a workgroup
 // belongs to ONE keyframe.  The rotation -- composed with the alignment's rot_reanchor where there is one -- goes through LDS as 9 float64;
 // the (row, 3) outputs are staged in LDS and written as runs of consecutive floats.  A row's neighbours are looked up at stride 1 in the
 // row's own segment: left and right are the adjacent table points, up and down two binary searches of the segment's range (pix is

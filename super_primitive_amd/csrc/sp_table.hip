@@ -106,31 +106,10 @@ __global__ __launch_bounds__(SP_BLOCK) void k_table_fill(const uint8_t* __restri
     fill_row(masks, logdepth, row_id, H, W, 1, seg_off, row_off, pix, baseL);
 }
 
-// tool/point_utils.py:37-40 + core/dense_optim.py:51-59: L at the rounded keypoint pixel
-__device__ __forceinline__ void keypoint_L(const float* __restrict__ logdepth, const float* __restrict__ keypoints, int n, int H,
-                                           int W, float* __restrict__ kp_L) {
-    const float kr = rintf(0.5f * (float)(H - 1) * (keypoints[2 * n] + 1.f));      // rintf = half-to-even
-    const float kc = rintf(0.5f * (float)(W - 1) * (keypoints[2 * n + 1] + 1.f));
-    int r = (int)kr, c = (int)kc;
-    // torch advanced indexing wraps negative indices once; anything else is an error upstream -- clamp here
-    if (r < 0) r += H;
-    if (c < 0) c += W;
-    r = min(max(r, 0), H - 1);
-    c = min(max(c, 0), W - 1);
-    kp_L[n] = logdepth[((size_t)n * H + r) * W + c];
-}
-
 __global__ void k_keypoint_L(const float* __restrict__ logdepth, const float* __restrict__ keypoints, int N, int H,
                              int W, float* __restrict__ kp_L) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n < N) keypoint_L(logdepth, keypoints, n, H, W, kp_L);
-}
-
-__device__ __forceinline__ int segment_of(const int32_t* __restrict__ seg_off, int N, int i) {
-    int lo = 0, hi = N;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_off[mid] <= i) lo = mid; else hi = mid; }
-    while (lo + 1 < N && seg_off[lo + 1] <= i) ++lo;
-    return lo;
+    if (n < N) kp_L[n] = keypoint_L(logdepth, keypoints, n, H, W);
 }
 
 struct SourceGeom { float xn, yn, L; bool ok; uint32_t pw; };
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_pack_rgb(const float* __restrict__
 
 // (a dimension of ONE pixel has nothing to reflect onto: indices -1 and 1 would land outside it -- the pixel itself is taken,
 //  so a 1-pixel level blurs to itself; torch's reflect padding refuses that size)
-__device__ __forceinline__ int reflect1(int i, int n) { return n == 1 ? 0 : (i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i)); }
+__device__ __forceinline__ int reflect1_or_self(int i, int n) { return n == 1 ? 0 : (i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i)); }
 
 // image/gaussian_pyramid.py:53-85: reflect pad 1, depthwise [1 2 1;2 4 2;1 2 1]/16, keep [::2, ::2]
 __device__ __forceinline__ float blur_decimate_at(const float* __restrict__ p, int H, int W, int Wo, int i) {
@@ -258,10 +237,10 @@ __device__ __forceinline__ float blur_decimate_at(const float* __restrict__ p, i
     float acc = 0.f;
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
-        const int y = reflect1(2 * yo + dy - 1, H);
+        const int y = reflect1_or_self(2 * yo + dy - 1, H);
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
-            const int x = reflect1(2 * xo + dx - 1, W);
+            const int x = reflect1_or_self(2 * xo + dx - 1, W);
             acc = fmaf(wgt[dy] * wgt[dx] * (1.f / 16.f), p[(size_t)y * W + x], acc);
         }
     }
@@ -1125,7 +1104,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_prep_fill(const SpPrepTable* __res
 __global__ void k_prep_keypoint_L(const SpPrepTable* __restrict__ tables) {
     const PrepTable& t = table_of(tables, blockIdx.y);
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n < t.N && t.kp_L) keypoint_L(generic(t.logdepth), generic(t.keypoints), n, t.H, t.W, generic(t.kp_L));
+    if (n < t.N && t.kp_L) t.kp_L[n] = keypoint_L(generic(t.logdepth), generic(t.keypoints), n, t.H, t.W);
 }
 
 // every pyramid level of one table in one pass: segment search, depth and validity once per point.  Padding positions of a
@@ -1232,50 +1211,17 @@ __global__ __launch_bounds__(SP_BLOCK) void k_prep_sample(const SpPrepSample* __
         if (in_table[k]) pix[idx[k]] = live[k] ? (g[k].pw | (g[k].ok ? 0x80000000u : 0u)) : 0u;
 }
 
-// One pyramid step of a batch of planar images.  Rows of W = 4 k pixels (16-byte aligned): a thread makes TWO neighbouring outputs
-// from one 16-byte load and one 4-byte load (the column left of it) of each of the three input rows -- 6 loads per 2 outputs, the
-// wide ones contiguous over the wave; one output per thread is 9 four-byte loads 8 bytes apart, and the pass sat in the load
-// issue (issue stalls 43 % of the wave cycles, 0.43 of the HBM roofline).  Same products and summation order as
-// blur_decimate_at().  The grid covers max_out_pixels / 2 threads per plane: other shapes take two outputs per thread, one at a time.
-__global__ __launch_bounds__(SP_BLOCK) void k_prep_blur(const SpPrepImage* __restrict__ jobs) {
-    const PrepImage& j = reinterpret_cast<const PrepImage*>(jobs)[blockIdx.z];
-    const int Ho = (j.H + 1) / 2, Wo = (j.W + 1) / 2;
-    const int i = blockIdx.x * SP_BLOCK + threadIdx.x;
-    const SP_GLOBAL float* in = j.in + (size_t)blockIdx.y * j.H * j.W;
-    SP_GLOBAL float* out = j.out + (size_t)blockIdx.y * Ho * Wo;
-    if ((j.W & 3) == 0 && ((uintptr_t)j.in & 15) == 0 && ((uintptr_t)j.out & 7) == 0) {
-        const int half = Wo >> 1;
-        if (i >= Ho * half) return;
-        const int yo = i / half, t = i - yo * half;
-        const float wgt[3] = {1.f, 2.f, 1.f};
-        float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            const SP_GLOBAL float* row = in + (size_t)reflect1(2 * yo + dy - 1, j.H) * j.W;
-            const float4 v = load4((const SP_GLOBAL f32x4*)(row + 4 * t));
-            const float left = row[max(4 * t - 1, 0)];
-            const float c0 = t > 0 ? left : v.y;            // column -1 reflects onto column 1
-            const float w0 = wgt[dy] * wgt[0] * (1.f / 16.f), w1 = wgt[dy] * wgt[1] * (1.f / 16.f), w2 = wgt[dy] * wgt[2] * (1.f / 16.f);
-            a0 = fmaf(w0, c0, a0);  a0 = fmaf(w1, v.x, a0);  a0 = fmaf(w2, v.y, a0);
-            a1 = fmaf(w0, v.y, a1); a1 = fmaf(w1, v.z, a1);  a1 = fmaf(w2, v.w, a1);
-        }
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const f32x2 o = {a0, a1};
-        *(SP_GLOBAL f32x2*)(out + (size_t)yo * Wo + 2 * t) = o;
-        return;
-    }
-    const int n_threads = gridDim.x * SP_BLOCK;
-    for (int o = i; o < Ho * Wo; o += n_threads) out[o] = blur_decimate_at(generic(in), j.H, j.W, Wo, o);
-}
-
 // One pyramid step of a batch of THREE-CHANNEL images AND their packed (HWC3) forms in the same pass (round 6): the target frames of a
 // batch are blurred level by level and every level is also packed for the cost kernel -- as two passes the packing re-reads what the pyramid
-// step has just had in registers (12 B per pixel and level of the set-up's traffic, one launch).  A thread makes two neighbouring outputs of
-// all three channels exactly like k_prep_blur (same loads, products and summation order) and, from the same registers, writes
+// step has just had in registers (12 B per pixel and level of the set-up's traffic, one launch).  Rows of W = 4 k pixels (16-byte aligned): a
+// thread makes TWO neighbouring outputs of all three channels from one 16-byte load and one 4-byte load (the column left of it) of each of
+// the three input rows -- one output per thread is 9 four-byte loads 8 bytes apart, and such a pass sat in the load issue -- with the
+// products and summation order of blur_decimate_at() and, from the same registers, writes
 //   out        planar level l + 1 (may be NULL: nobody blurs the last level further)
 //   packed_out level l + 1 packed (or NULL)
 //   packed_in  level l packed (or NULL): rows 2 yo, 2 yo + 1, columns 4 t .. 4 t + 3 -- the 2 x 4 pixels of its 3 x 5 window that no other thread owns
-// Pure copies and the same fused multiply-adds: bit-identical to sp_prepare_blur followed by sp_prepare_pack.
+// Pure copies and the same fused multiply-adds: bit-identical to sp_blur_decimate followed by sp_pack_rgb.  Other shapes take two
+// outputs per thread, one at a time.
 struct PrepImagePack {
     const SP_GLOBAL float* in;
     SP_GLOBAL float* out;
@@ -1302,7 +1248,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_prep_blur_pack(const SpPrepImagePa
             const SP_GLOBAL float* in = j.in + c * HW;
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
-                const SP_GLOBAL float* row = in + (size_t)reflect1(2 * yo + dy - 1, H) * W;
+                const SP_GLOBAL float* row = in + (size_t)reflect1_or_self(2 * yo + dy - 1, H) * W;
                 const float4 v = load4((const SP_GLOBAL f32x4*)(row + 4 * t));
                 const float left = row[max(4 * t - 1, 0)];
                 const float c0 = t > 0 ? left : v.y;            // column -1 reflects onto column 1
@@ -1530,14 +1476,6 @@ int sp_prepare_sample_pairs(const SpPrepSample* jobs_a, int max_P_a, const SpPre
     if (total + 7 > 0x7fffffffL) return SP_ELIMIT;
     hipLaunchKernelGGL((k_prep_sample<K>), dim3((unsigned)((total + 7) / 8 * 8)), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), jobs_a, (int)per_a, (int)total,
                        jobs_b, (int)per_b);
-    SP_CHECK_LAUNCH();
-    return 0;
-}
-
-int sp_prepare_blur(const SpPrepImage* jobs, int n_jobs, int C, int max_out_pixels, void* stream) {
-    if (!jobs || check_grid(max_out_pixels, n_jobs) || C <= 0 || C > 65535) return SP_EINVAL;
-    const int threads = (max_out_pixels + 1) / 2;          // (k_prep_blur: two outputs per thread)
-    hipLaunchKernelGGL(k_prep_blur, dim3((threads + SP_BLOCK - 1) / SP_BLOCK, C, n_jobs), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream), jobs);
     SP_CHECK_LAUNCH();
     return 0;
 }

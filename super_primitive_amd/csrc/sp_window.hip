@@ -97,36 +97,6 @@ struct WinArgs {
     int compose_only;
 };
 
-// Exp(xi) for xi = [tau, phi] as a 3x4 double matrix
-__device__ void se3_exp_d(const double xi[6], double E[12]) {
-    // the closed form of se3_retract_left (sp_solve_device.h), kept in double
-    const double wx = xi[3], wy = xi[4], wz = xi[5];
-    const double th2 = wx * wx + wy * wy + wz * wz;
-    double A, B, C;
-    if (th2 < 1e-4) {
-        A = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0);
-        B = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0);
-        C = 1.0 / 6.0 - th2 / 120.0 * (1.0 - th2 / 42.0);
-    } else {
-        const double th = sqrt(th2);
-        const double sn = sin(th), cs = cos(th);
-        A = sn / th; B = (1.0 - cs) / th2; C = (th - sn) / (th2 * th);
-    }
-    const double W[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-    double W2[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) W2[3 * i + j] = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-    for (int i = 0; i < 3; ++i) {
-        double Vrow[3];
-        for (int j = 0; j < 3; ++j) {
-            const double I = (i == j) ? 1.0 : 0.0;
-            E[4 * i + j] = I + A * W[3 * i + j] + B * W2[3 * i + j];
-            Vrow[j] = I + B * W[3 * i + j] + C * W2[3 * i + j];
-        }
-        E[4 * i + 3] = Vrow[0] * xi[0] + Vrow[1] * xi[1] + Vrow[2] * xi[2];
-    }
-}
-
 #define SP_WIN_LDS_DIRECT 32     // persistent-tangent nodes whose dExp is evaluated in parallel (6 lanes each)
 
 // STAGED is a template parameter, not a run-time select: with it the compiler knows that every access below goes to LDS

@@ -424,35 +424,6 @@ __global__ __launch_bounds__(SP_BLOCK) void k_window_gn_schur(WGnArgs w, const W
     }
 }
 
-// Exp(xi) as a 3x4 double matrix (same closed form as sp_window.hip)
-__device__ void wgn_se3_exp(const double xi[6], double E[12]) {
-    const double wx = xi[3], wy = xi[4], wz = xi[5];
-    const double th2 = wx * wx + wy * wy + wz * wz;
-    double A, B, C;
-    if (th2 < 1e-4) {
-        A = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0);
-        B = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0);
-        C = 1.0 / 6.0 - th2 / 120.0 * (1.0 - th2 / 42.0);
-    } else {
-        const double th = sqrt(th2);
-        const double sn = sin(th), cs = cos(th);
-        A = sn / th; B = (1.0 - cs) / th2; C = (th - sn) / (th2 * th);
-    }
-    const double W[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-    double W2[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) W2[3 * i + j] = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-    for (int i = 0; i < 3; ++i) {
-        double Vrow[3];
-        for (int j = 0; j < 3; ++j) {
-            const double I = (i == j) ? 1.0 : 0.0;
-            E[4 * i + j] = I + A * W[3 * i + j] + B * W2[3 * i + j];
-            Vrow[j] = I + B * W[3 * i + j] + C * W2[3 * i + j];
-        }
-        E[4 * i + 3] = Vrow[0] * xi[0] + Vrow[1] * xi[1] + Vrow[2] * xi[2];
-    }
-}
-
 // relative pose and affine slot of edge e from the current nodes (the compose step of sp_window.hip, unstaged)
 __device__ void wgn_compose_edge(const WGnArgs& w, int e) {
     const SpWindowEdge ed = w.edges[e];
@@ -971,7 +942,7 @@ __global__ __launch_bounds__(wgn_update_threads(LDS_Y)) void k_window_gn_update(
                 // T <- T inv(Exp(d)) = T Exp(-d)   (odometery.py:400-403, 861-882), then renormalise
                 double xi[6], E[12], Tn[12];
                 for (int k = 0; k < 6; ++k) xi[k] = -d6[k];
-                wgn_se3_exp(xi, E);
+                se3_exp_d(xi, E);
                 for (int r = 0; r < 3; ++r)
                     for (int c = 0; c < 4; ++c) {
                         double s = (double)nd.T[4 * r] * E[c] + (double)nd.T[4 * r + 1] * E[4 + c] + (double)nd.T[4 * r + 2] * E[8 + c];
@@ -987,7 +958,7 @@ __global__ __launch_bounds__(wgn_update_threads(LDS_Y)) void k_window_gn_update(
                 for (int q = 0; q < 6; ++q) { ad[q].v = nd.a[q]; ad[q].d[0] = 0.f; }
                 se3_exp_times<1>(ad, nd.T, out);
                 double E[12], Tn[12];
-                wgn_se3_exp(d6, E);
+                se3_exp_d(d6, E);
                 for (int r = 0; r < 3; ++r)
                     for (int c = 0; c < 4; ++c) {
                         double s = E[4 * r] * (double)out[c].v + E[4 * r + 1] * (double)out[4 + c].v + E[4 * r + 2] * (double)out[8 + c].v;

@@ -3,7 +3,7 @@
 Pipeline per image (``:30-92``): sparse-depth pixels become keypoints -> the frontend turns (image, K, keypoints)
 into a KeyFrame (SAM masks + integrated normals; OUT OF SCOPE here, any object with ``process_to_kf`` can be
 plugged in) -> per-segment median log-depth shift (``sp_segment_reinit``) -> per-pixel average over the
-covering visible segments (``sp_depth_average``, which fuses the dense ``unproject_kf_to_depths`` expansion, the
+covering visible segments (``sp_depth_accumulate`` then ``sp_depth_average_finish``, which fuse the dense ``unproject_kf_to_depths`` expansion, the
 ``depths[mask == 0] = -1`` masking, the visible-segment filter and ``render_depth_avg``) -> rerun with larger
 masks when more than 15 % of the pixels stay uncovered.  ``depth_completion_dense`` adds the stage the reference's evaluation
 loop runs next (evaluate_void.py:122-125): every pixel that is still uncovered takes its nearest covered pixel's depth."""

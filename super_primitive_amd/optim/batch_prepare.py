@@ -109,23 +109,11 @@ def segment_boxes_of(masks):
     return torch.stack((first(rows), first(cols), last(rows, H), last(cols, W)), dim=1).to(torch.int32)
 
 
-def flat_layout(counts, n_off, granule=GRANULE, table=None):
-    """Padded layout of many tables at once.  counts: real points of every segment, all tables concatenated; n_off[t]:
-    first segment of table t.  Returns (pc, seg_pos, p_off): padded run length of every segment, its position relative to
-    its own table, and the tables' offsets into one flat array.  ``granule``: 256, or 64 for wave-span work lists."""
-    counts = np.asarray(counts, dtype=np.int64)
-    pc = (counts + granule - 1) // granule * granule
-    cum = np.concatenate(([0], np.cumsum(pc)))
-    p_off = cum[n_off]
-    if table is None:
-        table = np.repeat(np.arange(len(n_off) - 1), np.diff(n_off))
-    return pc, cum[:-1] - p_off[table], p_off
-
-
 def host_layout(counts, n_off, granule=GRANULE):
-    """``flat_layout`` of several lattices at once through ``sp_host_layout``.  counts: (lattices, segments) int32.  Returns dict(counts
-    int64, pc, seg_pos (lattices, segments), p_off (lattices, pairs + 1), points (lattices, pairs), seg_off_pinned: (lattices, 2 segments)
-    int32 in pinned memory -- positions inside the flat array, then relative to the pair)."""
+    """Padded layout of several lattices at once through ``sp_host_layout`` (its numpy statement, ``flat_layout``, is with the tests:
+    tests/work_list_ref.py).  counts: (lattices, segments) int32.  Returns dict(counts int64, pc, seg_pos (lattices, segments), p_off
+    (lattices, pairs + 1), points (lattices, pairs), seg_off_pinned: (lattices, 2 segments) int32 in pinned memory -- positions inside
+    the flat array, then relative to the pair)."""
     lib = _lib.load()
     counts = np.ascontiguousarray(counts, dtype=np.int32)
     n_off = np.ascontiguousarray(n_off, dtype=np.int64)
@@ -142,9 +130,9 @@ def host_layout(counts, n_off, granule=GRANULE):
 
 def flat_work_list(pc, seg_pos, n_off, span_points, tile_points, granule=GRANULE):
     """Chunks, spans and record offsets (include/sp_hip.h, "Work list") of all pairs at once (same chunks, same greedy spans,
-    same order as ``pair_batch.build_work_list``), built by the library's host helper ``sp_host_work_list`` -- tens of
-    microseconds where the numpy form below takes 1-2 ms per lattice.  pc / seg_pos: padded run length and pair-relative position
-    of every segment; n_off: first segment of every pair.  Returns dict(chunks (C,4), spans (S,4), seg_tile_off (sum(N)+M,),
+    same order as the per-pair ``build_work_list`` of tests/work_list_ref.py), built by the library's host helper
+    ``sp_host_work_list`` -- tens of microseconds where its numpy statement (``flat_work_list_numpy``, same file) takes 1-2 ms per
+    lattice.  pc / seg_pos: padded run length and pair-relative position of every segment; n_off: first segment of every pair.  Returns dict(chunks (C,4), spans (S,4), seg_tile_off (sum(N)+M,),
     sto_off (M+1,), c_off (M+1,), s_off (M+1,))."""
     lib = _lib.load()
     pc = np.ascontiguousarray(pc, dtype=np.int64)
@@ -210,48 +198,6 @@ def work_lists_staged(specs, tile_points, granule, dev):
         out.append(dict(chunks=i32(0, 4 * C).reshape(C, 4), spans=i32(1, 4 * ns).reshape(ns, 4), seg_tile_off=i32(2, S + M),
                         sto_off=sto_off, c_off=c_off, s_off=s_off, n_chunks=C, n_spans=ns))
     return out
-
-
-def flat_work_list_numpy(pc, seg_pos, n_off, span_points, tile_points):
-    """The same work list in vectorised numpy (kept as the independent statement the host helper is tested against)."""
-    pc = np.asarray(pc, dtype=np.int64)
-    n_off = np.asarray(n_off, dtype=np.int64)
-    M, S = len(n_off) - 1, len(pc)
-    Ns = np.diff(n_off)
-    pair_of_seg = np.repeat(np.arange(M), Ns)
-    seg_in_pair = np.arange(S) - n_off[pair_of_seg]
-    chunk_max = max(GRANULE, tile_points // GRANULE * GRANULE)
-    k = -(-pc // chunk_max)                                                     # pieces per segment (0 for an empty one)
-    per = -(-(pc // GRANULE) // np.maximum(k, 1)) * GRANULE                    # (nearly) equal, granule-aligned lengths
-    cumk = np.concatenate(([0], np.cumsum(k)))
-    C = int(cumk[-1])
-    seg_idx = np.repeat(np.arange(S), k)
-    j = np.arange(C) - cumk[:-1][seg_idx]
-    start = seg_pos[seg_idx] + j * per[seg_idx]
-    cnt = np.minimum(per[seg_idx], pc[seg_idx] - j * per[seg_idx])
-    chunks = np.stack((pair_of_seg[seg_idx], seg_in_pair[seg_idx], start, cnt), axis=1).astype(np.int32)
-    c_off = cumk[n_off]
-    # per-pair CSR of the segment records: 4 records per chunk (one per wave)
-    ext_pair = np.repeat(np.arange(M), Ns + 1)
-    sto_off = n_off + np.arange(M + 1)
-    ext_local = np.arange(S + M) - sto_off[:-1][ext_pair]
-    seg_tile_off = (4 * (cumk[n_off[ext_pair] + ext_local] - cumk[n_off[ext_pair]])).astype(np.int32)
-    # spans: greedy runs of consecutive chunks of one pair, all pairs advanced together
-    cum = np.concatenate(([0], np.cumsum(cnt)))
-    cur, end = c_off[:-1].copy(), c_off[1:]
-    parts = []
-    act = np.nonzero(cur < end)[0]
-    while act.size:
-        q0 = cur[act]
-        q1 = np.searchsorted(cum, cum[q0] + span_points, side='right') - 1
-        q1 = np.minimum(np.maximum(q1, q0 + 1), end[act])
-        parts.append(np.stack((q0, q1 - q0, cum[q1] - cum[q0], act), axis=1))
-        cur[act] = q1
-        act = act[q1 < end[act]]
-    spans = np.concatenate(parts) if parts else np.zeros((0, 4), dtype=np.int64)
-    spans = spans[np.lexsort((spans[:, 0], spans[:, 3]))].astype(np.int32)
-    s_off = np.concatenate(([0], np.cumsum(np.bincount(spans[:, 3], minlength=M))))
-    return dict(chunks=chunks, spans=spans, seg_tile_off=seg_tile_off, sto_off=sto_off, c_off=c_off, s_off=s_off)
 
 
 class PreparedTables:
@@ -501,7 +447,7 @@ def prepare_pairs(src_frames, trg_images, trg_Ks, klds, level_ids, coarse, dev, 
     tabs = {}
     kp_L = torch.empty(S, dtype=torch.float32, device=dev)
     recs['kp_L'] = kp_L.data_ptr() + 4 * n_off[:-1]
-    # padded layouts of all lattices by the library's host helper (one pass; the numpy form -- flat_layout -- took a dozen array
+    # padded layouts of all lattices by the library's host helper (one pass; its numpy form -- flat_layout, tests/work_list_ref.py -- took a dozen array
     # operations per lattice), the segment positions straight into a pinned buffer
     lay = host_layout(counts_h, n_off, granule)
     if (lay['points'][all_strides.index(1)] == 0).any():

@@ -171,42 +171,6 @@ def pad_points(x, pd):
     return out
 
 
-def build_work_list(pads, span_points, tile_points):
-    """Chunks {pair, seg, start, count}, spans {first chunk, n chunks, points, pair} and the per-pair record offsets of
-    the many-pairs cost kernels (include/sp_hip.h, "Work list") for pairs whose padded layouts are ``pads``.
-    Returns dict(chunks (C,4) int32, spans (S,4) int32, seg_rec_offs [per pair (N+1,) int32], c_off, s_off)."""
-    chunk_max = max(GRANULE, tile_points // GRANULE * GRANULE)
-    chunks, spans, seg_rec_offs, c_off, spans_per_pair = [], [], [], [0], []
-    for m, pd in enumerate(pads):
-        first = len(chunks)
-        sto = [0]
-        for n, (pc, off) in enumerate(zip(pd['pc'], pd['pseg_off'][:-1])):
-            k = int(-(-pc // chunk_max))                       # pieces of (nearly) equal, granule-aligned length
-            if k:
-                per = int(-(-(pc // GRANULE) // k)) * GRANULE
-                done = 0
-                while done < pc:
-                    cnt = int(min(per, pc - done))
-                    chunks.append((m, n, int(off + done), cnt))
-                    done += cnt
-            sto.append(4 * (len(chunks) - first))              # records: 4 per chunk (one per wave)
-        seg_rec_offs.append(np.asarray(sto, dtype=np.int32))
-        c_off.append(len(chunks))
-        # spans: greedy runs of consecutive chunks
-        ns, q = 0, first
-        while q < len(chunks):
-            q1, pts = q, 0
-            while q1 < len(chunks) and (q1 == q or pts + chunks[q1][3] <= span_points):
-                pts += chunks[q1][3]
-                q1 += 1
-            spans.append((q, q1 - q, pts, m))
-            ns += 1
-            q = q1
-        spans_per_pair.append(ns)
-    return dict(chunks=np.asarray(chunks, dtype=np.int32).reshape(-1, 4), spans=np.asarray(spans, dtype=np.int32).reshape(-1, 4),
-                seg_rec_offs=seg_rec_offs, c_off=c_off, s_off=np.concatenate(([0], np.cumsum(spans_per_pair))))
-
-
 _SIDE_STREAMS = {}           # device -> [torch.cuda.Stream]: the extra streams of run_scheduled(streams=K)
 
 

@@ -118,13 +118,20 @@ def test_kf_criteria_match_reference():
     # nothing valid: the reference's torch.median raises on an empty tensor; the kernel reports NaN without syncing
     out = npy(keyframe_criterion(a, b, torch.zeros(64, 64, device=d.device)))
     assert out[0] == 0.0 and np.isnan(out[1]) and np.isnan(out[2])
-    # the grid form (sp_kf_criterion_ws: what keyframe_criterion calls since round 6) against the one-workgroup form, bit for bit
-    from super_primitive_amd import _lib
-    lib = _lib.load()
+    # all four outputs of the grid form (sp_kf_criterion_ws: what keyframe_criterion calls) against the oracle: the median is an element of
+    # the image and the ratio one float32 division, both exact
+    want_angle = kf_oracle.rotation_difference(a.cpu(), b.cpu())
     for img in (d, T(g["even_depth"]), T(g["one_depth"]), torch.zeros(64, 64, device=d.device)):
-        one = torch.empty(4, dtype=torch.float32, device=d.device)
-        _lib.check(lib.sp_kf_criterion(_lib.ptr(img.contiguous()), img.numel(), 1e-6, _lib.ptr(a.contiguous()), _lib.ptr(b.contiguous()), _lib.ptr(one), _lib.stream_ptr()), "sp_kf_criterion")
-        np.testing.assert_array_equal(npy(one).view(np.uint32), npy(keyframe_criterion(a, b, img)).view(np.uint32))
+        out = npy(keyframe_criterion(a, b, img))
+        count = int((img > 1e-6).sum())
+        assert out[0] == np.float32(count) / np.float32(img.numel())
+        if count:
+            want_diff, want_scale = kf_oracle.translation_difference(a.cpu(), b.cpu(), img.cpu())
+            assert out[1] == float(want_scale)
+            np.testing.assert_allclose(out[2], float(want_diff), rtol=2e-6)
+        else:
+            assert out[0] == 0.0 and np.isnan(out[1]) and np.isnan(out[2])
+        np.testing.assert_allclose(out[3], want_angle, rtol=2e-5, atol=1e-4)
 
 
 def test_infer_depth_seeds_matches_oracle():
@@ -205,8 +212,9 @@ def test_idempotence_properties():
 @pytest.mark.parametrize("H,W", [(480, 640), (45, 52), (33, 50), (2, 4)])
 def test_fused_pyramid_step_and_packing_equals_the_two_passes(H, W):
     """Round 6 (set-up): ``sp_prepare_blur_pack`` -- one pyramid step of three-channel images together with the packed forms of its input and output
-    levels -- against ``sp_prepare_blur`` followed by ``sp_prepare_pack``: bit for bit, on the 16-byte fast path (W a multiple of 4, even and odd
-    H), on the general path, and with each optional output left out."""
+    levels -- against the per-image path, ``sp_blur_decimate`` followed by ``sp_pack_rgb``: bit for bit, on the 16-byte fast path (W a multiple of
+    4, even and odd H), on the general path, and with each optional output left out.  ``sp_prepare_pack`` of the same images equals ``sp_pack_rgb``
+    bit for bit too."""
     from super_primitive_amd import _lib
     from super_primitive_amd.optim.batch_prepare import stage
     lib = _lib.load()
@@ -215,19 +223,23 @@ def test_fused_pyramid_step_and_packing_equals_the_two_passes(H, W):
     imgs = [torch.rand(3, H, W, generator=g).to(dev) for _ in range(3)]
     Ho, Wo = (H + 1) // 2, (W + 1) // 2
     s = _lib.stream_ptr()
-    # the two passes
+    # the per-image path
     want_out = [torch.empty(3, Ho, Wo, device=dev) for _ in imgs]
     want_pin = [torch.empty(H, W, 3, device=dev) for _ in imgs]
     want_pout = [torch.empty(Ho, Wo, 3, device=dev) for _ in imgs]
-    jb = np.zeros(len(imgs), dtype=np.dtype(_lib.SpPrepImage))
-    jb['inp'], jb['out'], jb['H'], jb['W'] = [t.data_ptr() for t in imgs], [t.data_ptr() for t in want_out], H, W
+    for img, o, pi, po in zip(imgs, want_out, want_pin, want_pout):
+        _lib.check(lib.sp_blur_decimate(_lib.ptr(img), 3, H, W, _lib.ptr(o), s), "sp_blur_decimate")
+        _lib.check(lib.sp_pack_rgb(_lib.ptr(img), 1, H, W, _lib.ptr(pi), s), "sp_pack_rgb")
+        _lib.check(lib.sp_pack_rgb(_lib.ptr(o), 1, Ho, Wo, _lib.ptr(po), s), "sp_pack_rgb")
+    # the batched packing pass on both levels
+    prep_pin = [torch.full((H, W, 3), -1.0, device=dev) for _ in imgs]
+    prep_pout = [torch.full((Ho, Wo, 3), -1.0, device=dev) for _ in imgs]
     jp = np.zeros(2 * len(imgs), dtype=np.dtype(_lib.SpPrepImage))
     jp['inp'] = [t.data_ptr() for t in imgs] + [t.data_ptr() for t in want_out]
-    jp['out'] = [t.data_ptr() for t in want_pin] + [t.data_ptr() for t in want_pout]
+    jp['out'] = [t.data_ptr() for t in prep_pin] + [t.data_ptr() for t in prep_pout]
     jp['H'], jp['W'] = [H] * 3 + [Ho] * 3, [W] * 3 + [Wo] * 3
-    st = stage([jb, jp], dev)
-    _lib.check(lib.sp_prepare_blur(_lib.ptr(st[0]), 3, 3, Ho * Wo, s), "sp_prepare_blur")
-    _lib.check(lib.sp_prepare_pack(_lib.ptr(st[1]), 6, H * W, s), "sp_prepare_pack")
+    st = stage([jp], dev)
+    _lib.check(lib.sp_prepare_pack(_lib.ptr(st[0]), 6, H * W, s), "sp_prepare_pack")
     # the fused pass: job 0 everything, job 1 without the planar output, job 2 without the packed forms
     out = [torch.full((3, Ho, Wo), -1.0, device=dev) for _ in imgs]
     pin = [torch.full((H, W, 3), -1.0, device=dev) for _ in imgs]
@@ -244,3 +256,4 @@ def test_fused_pyramid_step_and_packing_equals_the_two_passes(H, W):
         assert torch.equal(out[k], want_out[k]) if has_out else bool((out[k] == -1.0).all())
         assert torch.equal(pin[k], want_pin[k]) if has_packed else bool((pin[k] == -1.0).all())
         assert torch.equal(pout[k], want_pout[k]) if has_packed else bool((pout[k] == -1.0).all())
+        assert torch.equal(prep_pin[k], want_pin[k]) and torch.equal(prep_pout[k], want_pout[k])

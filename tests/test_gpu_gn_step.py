@@ -22,7 +22,7 @@ Case -> branch
   test_depth_damp                SP_PHASE_DEPTH_DAMP(k), also in the recompute path
   test_clamp                     the +-0.5 trust region; backup = the point left
   test_frozen_segments           D = 0, D (1 + lambda) = 5e-13 <= 1e-12, no records
-  test_failed_pivot              ldlt6_solve returns false
+  test_failed_pivot              ldlt_solve<6> returns false
   test_accept_reject_accept      the LM state machine of sp_pairs_gn_step: reject / restore / lambda x lm_up / no lowering after a rejection
   test_converges_and_stays_done  sp_pairs_gn_step_conv: done, and the early return of a done pair
   test_schedule_bookkeeping      iters, leave_phase on the cap (accepted and rejected iteration), by convergence, SpPhase.next, a finished pair

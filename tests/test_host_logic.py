@@ -21,9 +21,10 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == 19
-    # (ABI 18: sp_pairs_cost_opt is the one extended cost entry point; ABI 19: no single-launch iterate forms)
-    for retired in ("sp_pairs_cost_active", "sp_pairs_cost_rd", "sp_pairs_cost_rd_active", "sp_pairs_adam_iterate", "sp_pairs_gn_iterate"):
+    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == 20
+    # (ABI 18: sp_pairs_cost_opt is the one extended cost entry point; ABI 19: no single-launch iterate forms; ABI 20: no test-only forms)
+    for retired in ("sp_pairs_cost_active", "sp_pairs_cost_rd", "sp_pairs_cost_rd_active", "sp_pairs_adam_iterate", "sp_pairs_gn_iterate",
+                    "sp_kf_criterion", "sp_prepare_blur", "sp_depth_average"):
         assert not hasattr(lib, retired), retired
     # argument counts of the ctypes table match the prototypes
     for name in declared:
@@ -91,7 +92,6 @@ def test_new_entry_points_validate_arguments_and_sizes():
     for fn in (lib.sp_prepare_count, lib.sp_prepare_fill):
         assert fn(None, 1, 1, 1, None) == -1
     assert lib.sp_prepare_sample(None, 1, 1, None) == -1 and lib.sp_prepare_pack(None, 1, 1, None) == -1
-    assert lib.sp_prepare_blur(None, 1, 3, 1, None) == -1
     sched = _lib.SpSchedule()
     assert lib.sp_pairs_schedule_cost(ctypes.addressof(sched), None, None) == -1 and lib.sp_pairs_schedule_cost(None, None, None) == -1
     assert lib.sp_pairs_schedule_gn_step(ctypes.addressof(sched), 1, 1, 8.0, 0.5, 1e-7, *([None] * 7)) == -1
@@ -102,7 +102,8 @@ def test_new_entry_points_validate_arguments_and_sizes():
 def test_work_list_helpers_cover_every_point_once():
     """pad_layout / build_work_list (shared by PairBatch and PoseWindow): padded runs are granule multiples, chunks tile every
     padded segment exactly once, spans tile the chunks, record offsets count 4 records per chunk."""
-    from super_primitive_amd.optim.pair_batch import GRANULE, build_work_list, pad_layout
+    from super_primitive_amd.optim.pair_batch import GRANULE, pad_layout
+    from work_list_ref import build_work_list
     rng = np.random.default_rng(3)
     pads = [pad_layout(rng.integers(0, 3000, size=n), "cpu") for n in (7, 1, 30)]
     wl = build_work_list(pads, span_points=2048, tile_points=1024)
@@ -352,11 +353,12 @@ def test_thin_helpers_match_the_reference():
 
 
 def test_vectorised_layout_and_work_list_equal_the_per_pair_ones():
-    """batch_prepare.flat_layout / flat_work_list (numpy over the whole batch, used by PairBatch) produce exactly the chunks,
+    """flat_layout / batch_prepare.flat_work_list (over the whole batch, used by PairBatch) and its numpy statement produce exactly the chunks,
     spans and record offsets of pad_layout / build_work_list (per pair, per segment), including empty segments, segments
     longer than a chunk, and pairs with different segment counts."""
     from super_primitive_amd.optim import batch_prepare
-    from super_primitive_amd.optim.pair_batch import build_work_list, pad_layout
+    from super_primitive_amd.optim.pair_batch import pad_layout
+    from work_list_ref import build_work_list, flat_layout, flat_work_list_numpy
     rng = np.random.default_rng(11)
     for tile_points, span_points in ((1024, 2048), (8192, 16384), (256, 256), (2048, 100000)):
         Ns = [7, 1, 30, 12]
@@ -366,11 +368,11 @@ def test_vectorised_layout_and_work_list_equal_the_per_pair_ones():
         pads = [pad_layout(c, "cpu") for c in counts]
         ref = build_work_list(pads, span_points, tile_points)
         n_off = np.concatenate(([0], np.cumsum(Ns)))
-        pc, seg_pos, p_off = batch_prepare.flat_layout(np.concatenate(counts), n_off)
+        pc, seg_pos, p_off = flat_layout(np.concatenate(counts), n_off)
         assert np.array_equal(pc, np.concatenate([pd['pc'] for pd in pads]))
         assert np.array_equal(seg_pos, np.concatenate([pd['pseg_off'][:-1] for pd in pads]))
         assert np.array_equal(np.diff(p_off), [pd['Ppad'] for pd in pads])
-        for build in (batch_prepare.flat_work_list, batch_prepare.flat_work_list_numpy):      # the library's host helper and its numpy statement
+        for build in (batch_prepare.flat_work_list, flat_work_list_numpy):      # the library's host helper and its numpy statement
             got = build(pc, seg_pos, n_off, span_points, tile_points)
             assert np.array_equal(got['chunks'], ref['chunks']) and np.array_equal(got['spans'], ref['spans'])
             assert np.array_equal(got['seg_tile_off'], np.concatenate(ref['seg_rec_offs']))
@@ -386,7 +388,8 @@ def test_vectorised_work_list_equals_the_loop_on_random_layouts():
     pairs), chunk and span sizes, flat_layout / flat_work_list reproduce pad_layout / build_work_list exactly."""
     from hypothesis import given, settings, strategies as st
     from super_primitive_amd.optim import batch_prepare
-    from super_primitive_amd.optim.pair_batch import build_work_list, pad_layout
+    from super_primitive_amd.optim.pair_batch import pad_layout
+    from work_list_ref import build_work_list, flat_layout, flat_work_list_numpy
 
     pair = st.lists(st.one_of(st.just(0), st.integers(1, 9000)), min_size=1, max_size=12)
 
@@ -396,8 +399,8 @@ def test_vectorised_work_list_equals_the_loop_on_random_layouts():
         pads = [pad_layout(np.asarray(c), "cpu") for c in counts]
         ref = build_work_list(pads, span_points, tile_points)
         n_off = np.concatenate(([0], np.cumsum([len(c) for c in counts])))
-        pc, seg_pos, p_off = batch_prepare.flat_layout(np.concatenate([np.asarray(c) for c in counts]), n_off)
-        for build in (batch_prepare.flat_work_list, batch_prepare.flat_work_list_numpy):
+        pc, seg_pos, p_off = flat_layout(np.concatenate([np.asarray(c) for c in counts]), n_off)
+        for build in (batch_prepare.flat_work_list, flat_work_list_numpy):
             got = build(pc, seg_pos, n_off, span_points, tile_points)
             assert np.array_equal(got['chunks'].reshape(-1, 4), ref['chunks']) and np.array_equal(got['spans'].reshape(-1, 4), ref['spans'])
             assert np.array_equal(got['seg_tile_off'], np.concatenate(ref['seg_rec_offs']))
@@ -408,12 +411,12 @@ def test_vectorised_work_list_equals_the_loop_on_random_layouts():
 
 
 def test_host_layout_helper_equals_the_numpy_layout():
-    """sp_host_layout (one pass in C over all lattices) against optim.batch_prepare.flat_layout (the numpy statement), ragged pairs, empty
+    """sp_host_layout (one pass in C over all lattices) against flat_layout (the numpy statement, work_list_ref.py), ragged pairs, empty
     segments, both granules."""
     import ctypes
     import numpy as np
     from super_primitive_amd import _lib
-    from super_primitive_amd.optim.batch_prepare import flat_layout
+    from work_list_ref import flat_layout
     lib = _lib.load()
     rng = np.random.default_rng(5)
     Ns = np.array([6, 1, 9, 4, 64], dtype=np.int64)

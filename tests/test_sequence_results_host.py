@@ -91,7 +91,7 @@ def test_result_records_and_symbols_match_the_header():
     assert _lib.SpMapKeyframe.N.offset == 64 and _lib.SpMapKeyframe.out_offset.offset == 80 and _lib.SpMapKeyframe.first_block.offset == 92
     lib = ctypes.CDLL(_lib.LIB_PATH)
     assert hasattr(lib, "sp_traj_align") and hasattr(lib, "sp_map_points")
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == 19
+    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
 
 
 def test_result_entry_points_refuse_bad_arguments_without_a_device():
