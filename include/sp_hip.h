@@ -1449,6 +1449,63 @@ int sp_cloud_grid_nearest(const float* queries, long long Qa, long long Q, const
                           int32_t* count, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------
+ * Map neighbourhoods (sp_knn.hip): for every query its k nearest points of a cloud prepared by sp_cloud_grid_build, and a surface
+ * normal from such a list.  Normals for a cloud that has none (a lifted depth image, a fused map, a scan), the k distances a
+ * statistical outlier filter needs, the lists local descriptors start from.  Everything runs on the caller's stream without a
+ * synchronisation and without an allocation; argument checks come before any device work.
+ *
+ * sp_cloud_grid_knn: one launch, one lane per query.
+ *     queries, Qa, Q, scratch, skip_self : as for sp_cloud_grid_nearest (radius and origin are read from the scratch header)
+ *     k           : 1 .. SP_CLOUD_KNN_MAX, the length of a list
+ *     index       : (Qa,k) int32;  dist : (Qa,k) float32;  count : (Qa,) int32 -- EVERY ENTRY OF ALL THREE WRITTEN FOR EVERY QUERY ROW
+ * The NEIGHBOURS of query i are exactly those of sp_cloud_grid_nearest -- the same device function walks them: the range test on the
+ * query, the reference rows j in range with the float64 d2(i, j) = (dx dx + dy dy) + dz dz <= r2, row i left out with skip_self = 1.
+ *     count[i]           = their number (what sp_cloud_grid_nearest writes);
+ *     index[i, 0 .. m-1] = the rows of the m = min(k, count[i]) smallest pairs (d2, j), in ascending lexicographic order of (d2, j): on
+ *                          equal distance the lowest row comes first, and a cut that falls inside a tie keeps the lowest rows;
+ *     dist[i, n]         = float32(sqrt(d2)) of index[i, n]: the square root in float64, correctly rounded, then rounded to float32;
+ *     index[i, m .. k-1] = -1,  dist[i, m .. k-1] = +inf.
+ * A query out of range or non-finite, and every query against a scratch built for another Q, gets count 0, all -1 and all +inf.
+ * The k smallest members of a set under a total order do not depend on the order in which the members are met: two runs, and two
+ * builds whose member order differs, give the same bits.  At k = 1 the three outputs equal sp_cloud_grid_nearest's bit for bit.
+ * The list of a lane lives in LDS (entry n of lane l at d2[n][l], row[n][l]: 12 bytes per entry), sorted; the worst entry of a full
+ * list and the fill level are kept in registers, so a neighbour that does not make the list costs one float64 compare.  Kernels for
+ * list capacities 8, 16 and 32, chosen by k.  No atomics, no workgroup waits on another, every loop is bounded.
+ * Null queries / scratch / index / dist / count, a scratch not aligned to 16 bytes, Q or Qa <= 0, k < 1, skip_self outside {0, 1},
+ * skip_self = 1 with Qa != Q: SP_EINVAL.  k > SP_CLOUD_KNN_MAX, Q > 2^28, Qa > 2^31 - 2, Qa k > 2^31 - 2: SP_ELIMIT.  Invalid beats too
+ * large.
+ *
+ * sp_cloud_normals: one launch, one lane per query.
+ *     points      : (Q,3) float32, the cloud the lists index;  queries : (Qa,3) float32;  index : (Qa,k) int32, k in 1 .. SP_CLOUD_KNN_MAX
+ *     toward      : (V,3) float32 viewpoints, or NULL;  owner : (Qa,) int32, the viewpoint of every row, or NULL (then V must be 1)
+ *     normals     : (Qa,3) float32;  curvature : (Qa,) float32;  used : (Qa,) int32 -- all written for every row
+ * The lane walks its list in list order.  An entry outside 0 .. Q-1 is skipped (the -1 padding, and any list of the caller's stays
+ * inside the array), a listed point with a non-finite coordinate is skipped; used[i] is the number of points taken.  In float64 from
+ * the float32 inputs, every operation rounded on its own (no fma, no reciprocal), with q the query and p the listed points:
+ *     d = p - q  (relative to the query: a cloud far from the origin loses nothing);   S1_a += d_a;   S2_ab += d_a d_b  (six sums)
+ *     m_a = S1_a / used,   C_ab = S2_ab / used - m_a m_b                                        (the covariance of the neighbourhood)
+ * used < 3: normals and curvature NaN.  Else the eigenvalues l0 <= l1 <= l2 of C and the unit eigenvector n of l0 by cyclic Jacobi:
+ * SP_CLOUD_NORMALS_SWEEPS sweeps over the pairs (0,1), (0,2), (1,2); a rotation of the pair (p, q) with C_pq != 0 is
+ *     theta = (C_qq - C_pp) / (2 C_pq),  t = sgn(theta) / (|theta| + sqrt(theta theta + 1))  (sgn(0) = 1),  c = 1 / sqrt(t t + 1),  s = t c;
+ * l0 is the smallest diagonal entry after the sweeps (on a tie the lowest column), n its column divided by its length.
+ *     not l1 > 2^-30 l2  (coincident or collinear points, l2 = 0, a non-finite C):  normals and curvature NaN;
+ *     curvature = float32(max(l0, 0) / ((l0 + l1) + l2))                                   (the surface variation, 0 .. 1/3).
+ * Orientation.  First the component of n of largest magnitude is made positive (on a tie the lowest axis).  Then, with toward and a
+ * viewpoint c = toward[owner[i]] (toward[0] without owner; an owner outside 0 .. V-1 has none):  dot = (n_x e_x + n_y e_y) + n_z e_z
+ * with e = c - q, taken of n as the solver left it:  dot < 0: that n is negated;  dot > 0: it is kept, whatever the first rule said;
+ * dot = 0 or NaN: the first rule stands.  So the computed n . (c - q) is never negative, and the sign is defined on every row.
+ * n is rounded to float32 once, at the end.  A NaN normal is what sp_cloud_register ignores ("a non-finite normal contributes
+ * nothing").  Two runs give the same bits: every sum is taken in list order.
+ * Null points / queries / index / normals / curvature / used, Q or Qa <= 0, k < 1, toward with V < 1, toward without owner and V != 1:
+ * SP_EINVAL.  k > SP_CLOUD_KNN_MAX, Q > 2^28, Qa > 2^31 - 2, Qa k > 2^31 - 2: SP_ELIMIT.  Invalid beats too large. */
+#define SP_CLOUD_KNN_MAX 32
+#define SP_CLOUD_NORMALS_SWEEPS 8
+int sp_cloud_grid_knn(const float* queries, long long Qa, long long Q, const void* scratch, int skip_self, int k, int32_t* index, float* dist,
+                      int32_t* count, void* stream);
+int sp_cloud_normals(const float* points, long long Q, const float* queries, const int32_t* index, long long Qa, int k, const float* toward,
+                     int V, const int32_t* owner, float* normals, float* curvature, int32_t* used, void* stream);
+
+/* ----------------------------------------------------------------------------------------------------
  * Map registration (sp_register.hip): the similarity x -> s R x + t that moves a QUERY cloud onto a REFERENCE cloud prepared by
  * sp_cloud_grid_build, by Gauss-Newton ICP (iterative closest point) from a start the caller gives.  Everything runs on the caller's
  * stream: no host synchronisation, no allocation, no host read per iteration; argument checks come before any device work.

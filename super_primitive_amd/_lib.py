@@ -107,6 +107,8 @@ SIGNATURES = {
     "sp_cloud_grid_scratch_units": [ctypes.c_longlong],
     "sp_cloud_grid_build": [P, ctypes.c_longlong, F, F, F, F, P, P],
     "sp_cloud_grid_nearest": [P, ctypes.c_longlong, ctypes.c_longlong, P, I, P, P, P, P],
+    "sp_cloud_grid_knn": [P, ctypes.c_longlong, ctypes.c_longlong, P, I, I, P, P, P, P],
+    "sp_cloud_normals": [P, ctypes.c_longlong, P, P, ctypes.c_longlong, I, P, I, P, P, P, P, P],
     "sp_cloud_register_work_doubles": [ctypes.c_longlong],
     "sp_cloud_register": [P, P, ctypes.c_longlong, ctypes.c_longlong, P, I, I, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, I, P, P, P, P, P],
 }
@@ -283,6 +285,7 @@ class SpMapKeyframe(ctypes.Structure):
 SP_VIEW_FLOATS = 25
 SP_MAP_FUSE_MAX_POINTS = 1 << 28
 SP_CLOUD_GRID_MAX_POINTS = 1 << 28
+SP_CLOUD_KNN_MAX = 32
 SP_CLOUD_REG_RUNNING, SP_CLOUD_REG_CONVERGED, SP_CLOUD_REG_MAX_ITERS, SP_CLOUD_REG_FEW, SP_CLOUD_REG_DEGENERATE = range(5)
 SP_CLOUD_REG_ITERS_LIMIT = 4096
 SP_CLOUD_REG_WORK_DOUBLES = 40

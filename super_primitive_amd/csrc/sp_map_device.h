@@ -150,22 +150,20 @@ __device__ __forceinline__ bool grid_axis(double p, double o, double cell, unsig
     return true;
 }
 
-// what one query finds: d2 and row of the neighbour with the smallest (d2, row) (HUGE_VAL and -1: none), where its record lies, and
-// the number of neighbours
-struct GridNearest { double d2; int32_t row, place, count; };
-
-// The query (x, y, z) against the prepared cloud: the 27 cells around its own, each looked up (a 16-byte load per probe, until the key
-// or an empty slot), each cell's records walked; the decision is made in float64 exactly as the contract of sp_cloud_grid_nearest
-// writes it.  `self`: a row that is not a neighbour (-1: none).  A scratch built for another Q answers "none".
-__device__ __forceinline__ GridNearest grid_nearest_walk(double x, double y, double z, const GridHeader* __restrict__ header,
-                                                         const GridSlot* __restrict__ table, const GridRecord* __restrict__ records,
-                                                         unsigned int mask, int Q, int32_t self) {
+// The walk of one query (x, y, z) over the prepared cloud: the 27 cells around its own, each looked up (a 16-byte load per probe, until
+// the key or an empty slot), each cell's records walked; d2 is computed in float64 exactly as the contract of sp_cloud_grid_nearest
+// writes it, and visit(d2, row, place) is called for every NEIGHBOUR (d2 <= r2, row != self), in the order the records lie in.
+// `self`: a row that is not a neighbour (-1: none).  A scratch built for another Q, or a query out of range, has no neighbours.
+// Every loop is bounded: a probe visits at most S slots, a walk at most `count` records, clamped to the record array.
+template <class Visit>
+__device__ __forceinline__ void grid_walk(double x, double y, double z, const GridHeader* __restrict__ header,
+                                          const GridSlot* __restrict__ table, const GridRecord* __restrict__ records,
+                                          unsigned int mask, int Q, int32_t self, Visit visit) {
 #pragma clang fp contract(off)
     const double r2 = header->r2, cell = header->cell;     // (uniform: scalar loads)
     const bool built = header->mask == mask && header->Q == Q;
     unsigned long long cx = 0, cy = 0, cz = 0;
     const bool in = built && grid_axis(x, header->o[0], cell, cx) && grid_axis(y, header->o[1], cell, cy) && grid_axis(z, header->o[2], cell, cz);
-    GridNearest f = {HUGE_VAL, -1, -1, 0};
     if (in) {
 #pragma unroll 1
         for (int c = 0; c < 27; ++c) {
@@ -187,13 +185,25 @@ __device__ __forceinline__ GridNearest grid_nearest_walk(double x, double y, dou
                 const double dx = x - (double)__int_as_float(raw.x), dy = y - (double)__int_as_float(raw.y), dz = z - (double)__int_as_float(raw.z);
                 const double d2 = (dx * dx + dy * dy) + dz * dz;
                 const int32_t row = raw.w;
-                if (d2 <= r2 && row != self) {
-                    ++f.count;
-                    if (d2 < f.d2 || (d2 == f.d2 && row < f.row)) { f.d2 = d2; f.row = row; f.place = m; }
-                }
+                if (d2 <= r2 && row != self) visit(d2, row, m);
             }
         }
     }
+}
+
+// what one query finds: d2 and row of the neighbour with the smallest (d2, row) (HUGE_VAL and -1: none), where its record lies, and
+// the number of neighbours
+struct GridNearest { double d2; int32_t row, place, count; };
+
+// grid_walk keeping the minimum over (d2, row) and the count: what sp_cloud_grid_nearest answers and sp_cloud_register pairs with
+__device__ __forceinline__ GridNearest grid_nearest_walk(double x, double y, double z, const GridHeader* __restrict__ header,
+                                                         const GridSlot* __restrict__ table, const GridRecord* __restrict__ records,
+                                                         unsigned int mask, int Q, int32_t self) {
+    GridNearest f = {HUGE_VAL, -1, -1, 0};
+    grid_walk(x, y, z, header, table, records, mask, Q, self, [&f](double d2, int32_t row, int32_t m) {
+        ++f.count;
+        if (d2 < f.d2 || (d2 == f.d2 && row < f.row)) { f.d2 = d2; f.row = row; f.place = m; }
+    });
     return f;
 }
 

@@ -24,6 +24,10 @@
                       its spacing and the neighbour count a radius outlier filter keeps points by.
 ``register_map``      the map moved onto a reference cloud by ICP on the device before it is scored (``sp_cloud_register``): the 3D scores no
                       longer hang on a similarity fitted to a handful of camera centres; ``transform_map`` applies any similarity to a map.
+``estimate_normals``  normals for a cloud that has none -- lifted ground truth, a fused map, a scan --, from the k nearest points of every
+                      point (``sp_cloud_grid_knn`` / ``sp_cloud_normals``): ``register_map`` then reaches its ``'plane'`` residual and
+                      ``write_ply`` exports ``nx ny nz``; ``statistical_outliers`` is the mean distance to the k nearest against the
+                      cloud's mean and deviation, ``select_map`` the map reduced to the rows a mask keeps.
 ``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``.
 ``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file."""
 from __future__ import annotations
@@ -343,7 +347,13 @@ def filter_map(world, consistency, min_agree=1, max_in_front=None):
     keep = counts[:, 0] >= int(min_agree)
     if max_in_front is not None:
         keep = keep & (counts[:, 1] <= int(max_in_front))
-    dev = counts.device
+    return _select_rows(world, keep, Q)
+
+
+def _select_rows(world, keep, Q):
+    """The rows of ``world`` (validated, Q rows) where ``keep`` (Q,) bool holds, in their order: the compaction of ``filter_map`` and
+    ``select_map``.  ONE host read, the new offsets."""
+    dev = keep.device
     rank = torch.cumsum(keep.long(), dim=0)                                            # inclusive: rank[i] - 1 is row i's new place
     before = torch.cat((rank.new_zeros(1), rank))                                      # before[o] = kept rows among the first o
     old = torch.as_tensor(np.asarray(world['offsets'], dtype=np.int64)).to(dev)
@@ -357,6 +367,18 @@ def filter_map(world, consistency, min_agree=1, max_in_front=None):
     out['offsets'] = offsets
     out['kept'] = kept
     return out
+
+
+def select_map(world, keep):
+    """``world`` reduced to the rows where ``keep`` (Q,) bool holds -- ``statistical_outliers(...)['keep']``, ``map_neighbours(...)
+    ['count'] >= n``, any mask of the caller's --, in their order: what ``filter_map`` returns for its own mask (the same code): the
+    per-point tensors (and ``normals``, if the world has them) compacted, ``offsets`` recomputed, ``kept`` the surviving rows, every
+    other entry carried over.  ``world`` is validated as ``filter_map`` does.  ONE host read, the new offsets."""
+    Q = _check_world(world, "select_map")
+    if not torch.is_tensor(keep) or keep.dtype != torch.bool or tuple(keep.shape) != (Q,):
+        raise ValueError(f"select_map: keep must be a bool tensor ({Q},), got "
+                         f"{(keep.dtype, tuple(keep.shape)) if torch.is_tensor(keep) else type(keep).__name__}")
+    return _select_rows(world, keep, Q)
 
 
 def fuse_map(world, voxel, origin=None):
@@ -560,6 +582,81 @@ def map_neighbours(world, radius, origin=None):
     _check_world(world, "map_neighbours")
     grid = viz.cloud_grid(world['points'], radius, origin)
     return viz.nearest_points(grid['points'], grid, skip_self=True)
+
+
+def estimate_normals(cloud, radius, k=16, view_centres=None, owner=None):
+    """Normals for a cloud that has none: ``cloud`` is a world dict, a ``dict(points=...)`` or an (R,3) float32 tensor -- lifted ground
+    truth, a fused map whose members carried no normals, a scan, the map of another sequence.  ``viz.cloud_normals``: ONE grid build at
+    ``radius``, ONE ``sp_cloud_grid_knn`` and ONE ``sp_cloud_normals`` launch (include/sp_hip.h has the rule): per point the direction
+    of least spread of its up to ``k`` (1 .. 32) nearest points within ``radius``, itself included.  ``view_centres`` (3,) or (V,3)
+    float32 and ``owner`` (R,) int32 turn the normal of row i towards ``view_centres[owner[i]]``; without them the component of
+    largest magnitude is positive.  Returns a NEW dict: the cloud's entries and ``'normals'`` (R,3) float32 (NaN where fewer than
+    three points were in reach, or they are coincident or collinear: ``sp_cloud_register`` ignores such rows), ``'curvature'`` (R,)
+    float32 (l0 / (l0 + l1 + l2), the surface variation) and ``'normals_used'`` (R,) int32.  ``register_map`` takes the result as its
+    reference as it is and then picks the ``'plane'`` residual; ``write_ply`` and ``transform_map`` take it too.  The lifted ground
+    truth of a sequence, every point turned towards the camera that saw it, with no host read::
+
+        lifted = viz.lift_depth_images(gt_depths, Ks, gt_poses)                # points (R,3) at capacity, offsets (V+1,) on the device
+        row = torch.arange(R, device=dev)
+        owner = torch.bucketize(row, lifted['offsets'][1:], right=True).int()  # (V for the spare rows: no viewpoint)
+        points = torch.where((row < lifted['offsets'][-1])[:, None], lifted['points'], nan)    # the spare rows are uninitialised: NaN is never found
+        reference = estimate_normals(points, radius, view_centres=gt_poses[:, :3, 3].contiguous(), owner=owner)
+        moved = register_map(world, reference, radius)                         # residual 'plane'
+
+    No synchronisation."""
+    from ..tool import viz
+    pts = cloud.get('points') if isinstance(cloud, dict) else cloud
+    if not torch.is_tensor(pts):
+        raise ValueError("estimate_normals: cloud must be an (R,3) float32 tensor or a dict with 'points'")
+    try:
+        radius = float(radius)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"estimate_normals: radius {radius!r}: {e}") from None
+    found = viz.cloud_normals(pts, radius, k=k, toward=view_centres, owner=owner)
+    out = dict(cloud) if isinstance(cloud, dict) else dict(points=pts)
+    out.update(normals=found['normals'], curvature=found['curvature'], normals_used=found['used'])
+    return out
+
+
+def statistical_outliers(world, radius, k=16, std_ratio=2.0, knn=None):
+    """The project's statistical outlier rule (the idea of the well-known point-cloud filter of that name; no equality with any other
+    library's result is claimed): every map point's mean distance to its up to ``k`` (1 .. 32) nearest OTHER points within ``radius``
+    against the cloud's own mean and deviation of that figure.  One ``cloud_grid`` build and one ``viz.nearest_k`` with ``skip_self``
+    (or ``knn``: what such a call returned for this map, reused).
+        mean_dist[i] = the float64 mean of the finite entries of ``knn['dist'][i]``;  +inf where there is none (no point within radius)
+        mu, sigma    = the mean and the population deviation (divisor n) of ``mean_dist`` over its finite rows
+        threshold    = mu + std_ratio * sigma;   keep[i] = mean_dist[i] <= threshold     (a row with no neighbour is never kept)
+    Returns ``dict(mean_dist (Q,) float64, keep (Q,) bool, mu, sigma, threshold (0-dim float64), knn)``; pass ``keep`` to
+    ``select_map``.  The arithmetic is plain torch: with ``knn`` given it runs on CPU tensors too.  No synchronisation, no host read."""
+    from ..tool import viz
+    Q = _check_world(world, "statistical_outliers")
+    try:
+        std_ratio = float(std_ratio)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"statistical_outliers: std_ratio {std_ratio!r}: {e}") from None
+    if not (0.0 <= std_ratio < float("inf")):
+        raise ValueError(f"statistical_outliers: std_ratio {std_ratio} (finite, >= 0)")
+    if knn is None:
+        viz._list_length(k, "statistical_outliers")                                    # (before the build)
+        grid = viz.cloud_grid(world['points'], radius)
+        knn = viz.nearest_k(grid['points'], grid, k, skip_self=True)
+    dist = knn.get('dist') if isinstance(knn, dict) else None
+    if not torch.is_tensor(dist) or dist.dtype != torch.float32 or dist.dim() != 2 or dist.shape[0] != Q or dist.shape[1] < 1:
+        raise ValueError(f"statistical_outliers: knn['dist'] must be float32 ({Q},k)")
+    d = dist.detach().double()
+    finite = d < float("inf")
+    n = finite.sum(dim=1)
+    total = torch.where(finite, d, torch.zeros_like(d)).sum(dim=1)
+    has = n > 0
+    inf = torch.full_like(total, float("inf"))
+    mean_dist = torch.where(has, total / torch.where(has, n, torch.ones_like(n)).double(), inf)
+    rows = has.sum().double()
+    zero = torch.zeros_like(total)
+    mu = torch.where(has, mean_dist, zero).sum() / rows
+    dev2 = torch.where(has, mean_dist - mu, zero)
+    sigma = torch.sqrt((dev2 * dev2).sum() / rows)
+    threshold = mu + std_ratio * sigma
+    return dict(mean_dist=mean_dist, keep=mean_dist <= threshold, mu=mu, sigma=sigma, threshold=threshold, knn=knn)
 
 
 def write_ply(path, world):

@@ -16,6 +16,8 @@ matplotlib is imported):
 ``fuse_points``        one averaged point per occupied voxel of a point set (``sp_map_fuse``).
 ``cloud_grid``         a point cloud prepared for neighbour queries at one radius (``sp_cloud_grid_build``).
 ``nearest_points``     per query point the nearest point of such a cloud, its distance and the count within the radius (``sp_cloud_grid_nearest``).
+``nearest_k``          per query point its k nearest points of such a cloud within the radius, sorted (``sp_cloud_grid_knn``).
+``cloud_normals``      a normal and a surface variation per point of a cloud that has none, from its k nearest points (``sp_cloud_normals``).
 ``register_clouds``    the similarity that moves a query cloud onto such a cloud, by Gauss-Newton ICP on the device (``sp_cloud_register``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
@@ -459,6 +461,81 @@ def nearest_points(queries, grid, skip_self=False):
                count=torch.empty(Qa, dtype=torch.int32, device=dev))
     _lib.check(lib.sp_cloud_grid_nearest(_lib.ptr(qs), Qa, Q, _lib.ptr(scratch), 1 if skip_self else 0, _lib.ptr(out['index']), _lib.ptr(out['dist']),
                                          _lib.ptr(out['count']), _lib.stream_ptr()), "sp_cloud_grid_nearest")
+    return out
+
+
+def _list_length(k, what):
+    """``k`` as an int in 1 .. SP_CLOUD_KNN_MAX."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.SP_CLOUD_KNN_MAX:
+        raise ValueError(f"{what}: k {k!r} (an integer in 1 .. {_lib.SP_CLOUD_KNN_MAX})")
+    return k
+
+
+def nearest_k(queries, grid, k, skip_self=False):
+    """ONE ``sp_cloud_grid_knn`` call (include/sp_hip.h has the rule): per row of ``queries`` (Qa,3) float32 its ``k`` (1 .. 32) nearest
+    points of the cloud behind ``grid`` (what ``cloud_grid`` returned) within the grid's radius -- ``index`` (Qa,k) int32, in ascending
+    (distance, row) order, padded with -1; ``dist`` (Qa,k) float32, padded with +inf; ``count`` (Qa,) int32, ALL the points within the
+    radius (what ``nearest_points`` counts).  ``skip_self``: the queries are the grid's own cloud (the same number of rows) and no row
+    lists itself.  At ``k=1`` the result is ``nearest_points``' bit for bit.  No synchronisation."""
+    Q, scratch = _grid_handle(grid, "nearest_k")
+    k = _list_length(k, "nearest_k")
+    _on_device(queries, scratch, grid['points'])
+    qs = _f32(queries, (None, 3), "queries")
+    Qa = int(qs.shape[0])
+    if Qa == 0:
+        raise ValueError("nearest_k: no queries")
+    if Qa * k > 2 ** 31 - 2:
+        raise ValueError(f"nearest_k: {Qa} lists of {k} are beyond the kernel's limit of {2 ** 31 - 2} entries")
+    if skip_self and Qa != Q:
+        raise ValueError(f"nearest_k: skip_self with {Qa} queries against a grid of {Q} points (the queries must be the grid's cloud)")
+    lib = _grid_scratch(grid, "nearest_k")
+    dev = qs.device
+    out = dict(index=torch.empty(Qa, k, dtype=torch.int32, device=dev), dist=torch.empty(Qa, k, dtype=torch.float32, device=dev),
+               count=torch.empty(Qa, dtype=torch.int32, device=dev))
+    _lib.check(lib.sp_cloud_grid_knn(_lib.ptr(qs), Qa, Q, _lib.ptr(scratch), 1 if skip_self else 0, k, _lib.ptr(out['index']), _lib.ptr(out['dist']),
+                                     _lib.ptr(out['count']), _lib.stream_ptr()), "sp_cloud_grid_knn")
+    return out
+
+
+def cloud_normals(points, radius, k=16, toward=None, owner=None, grid=None, origin=None):
+    """A surface normal for every point of a cloud that has none: ``points`` (Q,3) float32 against itself -- ONE ``cloud_grid`` build at
+    ``radius`` (unless ``grid``, a handle over these very points, is handed in; its radius then rules and ``radius`` / ``origin`` are
+    ignored), ONE ``nearest_k`` with ``skip_self=False`` (the point itself is the first member of its list) and ONE ``sp_cloud_normals``
+    launch (include/sp_hip.h has the rule): the eigenvector of the smallest eigenvalue of the covariance of the up to ``k`` (1 .. 32)
+    nearest points within the radius, in float64.  ``toward``: (3,) or (V,3) float32 viewpoints; the normal of row i is turned towards
+    ``toward[owner[i]]`` (``owner`` (Q,) int32; without it ``toward`` must be ONE viewpoint).  Without ``toward`` the component of
+    largest magnitude is positive.  Returns ``dict(normals (Q,3) float32, curvature (Q,) float32, used (Q,) int32, knn)``: NaN normals
+    and curvature where fewer than three points were in reach or they are coincident or collinear; ``knn`` is what ``nearest_k``
+    returned.  No synchronisation."""
+    k = _list_length(k, "cloud_normals")
+    _on_device(points, toward, owner)
+    pts = _f32(points, (None, 3), "points")
+    Q = int(pts.shape[0])
+    if Q == 0:
+        raise ValueError("cloud_normals: no points")
+    if grid is not None and (_grid_handle(grid, "cloud_normals")[0] != Q or grid['points'].device != pts.device):
+        raise ValueError(f"cloud_normals: a grid of {int(grid['Q'])} points for a cloud of {Q}")
+    view = own = None
+    V = 0
+    if toward is not None:
+        if toward.dtype != torch.float32 or not (tuple(toward.shape) == (3,) or (toward.dim() == 2 and toward.shape[1] == 3 and toward.shape[0] >= 1)):
+            raise ValueError(f"cloud_normals: toward must be float32 (3,) or (V,3), got {toward.dtype} {tuple(toward.shape)}")
+        view = toward.detach().reshape(-1, 3).contiguous()
+        V = int(view.shape[0])
+        if owner is None and V != 1:
+            raise ValueError(f"cloud_normals: {V} viewpoints need an owner per point")
+        own = None if owner is None else _i32(owner, Q, "owner")
+    elif owner is not None:
+        raise ValueError("cloud_normals: owner without toward")
+    if grid is None:
+        grid = cloud_grid(pts, radius, origin)
+    knn = nearest_k(grid['points'], grid, k)
+    lib = _lib.load()
+    dev = pts.device
+    out = dict(normals=torch.empty(Q, 3, dtype=torch.float32, device=dev), curvature=torch.empty(Q, dtype=torch.float32, device=dev),
+               used=torch.empty(Q, dtype=torch.int32, device=dev), knn=knn)
+    _lib.check(lib.sp_cloud_normals(_lib.ptr(grid['points']), Q, _lib.ptr(grid['points']), _lib.ptr(knn['index']), Q, k, _lib.ptr(view), V, _lib.ptr(own),
+                                    _lib.ptr(out['normals']), _lib.ptr(out['curvature']), _lib.ptr(out['used']), _lib.stream_ptr()), "sp_cloud_normals")
     return out
 
 
