@@ -704,11 +704,12 @@ int sp_window_step(const SpPair* pairs, const SpWindowEdge* edges, int n_edges, 
  * nodes = 112 -- and through global scratch up to 512 = 64 nodes), the log-depths of every block with lr > 0 (eliminated by a Schur
  * complement, like the per-pair solver; a depth unknown of keyframe k only couples with the frames k is matched against, and only
  * those columns are stored and summed).  No camera unknown at all is allowed (the 'supp' mapping of odometery.py:576-648: only the
- * latest keyframe's depths are free).  flags bit 0: pose-only step (all depth blocks treated as frozen); bit 1 (ABI 13): PREDICTED EXIT --
- * with conv_tol > 0 the window also freezes right after a step that is predicted to buy less than conv_tol of the loss (the first-order
- * change b . delta along the step; lambda <= 1e-2 only), without the evaluation that would confirm it: see SP_PHASE_PREDICTED_EXIT.
- * Bit 2 (ABI 14): the caller's word that NO depth block moves (every SpWindowBlock.lr is 0: frame-to-keyframe tracking) -- like bit 0 the
- * Schur-term launch is then left out (its terms are all zero): three launches per iteration instead of four.
+ * latest keyframe's depths are free).  flags: SP_WGN_POSE_ONLY -- a pose-only step (all depth blocks treated as frozen);
+ * SP_WGN_PREDICTED_EXIT (ABI 13) -- with conv_tol > 0 the window also freezes right after a step that is predicted to buy less than
+ * conv_tol of the loss (the first-order change b . delta along the step; lambda <= 1e-2 only), without the evaluation that would
+ * confirm it: see SP_PHASE_PREDICTED_EXIT.  SP_WGN_DEPTHS_FIXED (ABI 14) -- the caller's word that NO depth block moves (every
+ * SpWindowBlock.lr is 0: frame-to-keyframe tracking); like SP_WGN_POSE_ONLY the Schur-term launch is then left out (its terms are all
+ * zero): three launches per iteration instead of four.
  * LM: lambda adapts on the device exactly like sp_pairs_gn_step (loss up -> previous step undone from nodes_backup / kld_backup,
  * lambda *= lm_up, re-evaluated next call; loss down -> lambda = max(lambda lm_down, lm_min)).  A FAILED FACTORISATION (a pivot of the
  * reduced camera system <= 0 at this damping) moves no unknown, neither camera nor log-depth: lambda *= lm_up, state[8] += 1 and the
@@ -725,6 +726,9 @@ int sp_window_step(const SpPair* pairs, const SpWindowEdge* edges, int n_edges, 
  *   rejected-last flag, iterations, converged flag, last loss, failed solves, too-many-unknowns flag, ...}; losses[max_losses]: loss of
  *   call i.  scratch: sp_window_gn_scratch_doubles(n_edges, n_blocks, sum_N, max_N, n_unknowns) doubles; nodes_backup: n_nodes nodes;
  *   kld_backup: sum_N floats (blocks in order; sum_N = total log-depths of all blocks). */
+#define SP_WGN_POSE_ONLY 1
+#define SP_WGN_PREDICTED_EXIT 2
+#define SP_WGN_DEPTHS_FIXED 4
 int sp_window_gn_scratch_doubles(int n_edges, int n_blocks, int sum_N, int max_N, int n_unknowns);
 /* where in the scratch the update kernel leaves 16 time stamps of its phases (100 MHz ticks; diagnostics, tools/window_bench.py) */
 int sp_window_gn_profile_offset(int n_edges, int n_blocks, int sum_N, int max_N, int n_unknowns);
@@ -1059,7 +1063,7 @@ typedef struct SpChainWindow {         /* a built window with its Gauss-Newton s
     SpChainPhase phase[SP_CHAIN_PHASES];
     int32_t n_phases;
     int32_t check_every;               /* sp_window_gn_run's */
-    int32_t flags;                     /* sp_window_gn_step's (bit 1: predicted exit, bit 2: no depth block moves) */
+    int32_t flags;                     /* sp_window_gn_step's (SP_WGN_PREDICTED_EXIT, SP_WGN_DEPTHS_FIXED) */
     float lam0;                        /* LM damping every frame starts from */
     float lm_up, lm_down, lm_min;
     int32_t check_first;               /* > 0: every phase looks at the state after this many iterations for the first time (a window that

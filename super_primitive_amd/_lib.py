@@ -228,6 +228,7 @@ class SpWindowGn(ctypes.Structure):
                 ("sum_N", c_int), ("max_N", c_int), ("n_unknowns", c_int), ("max_losses", c_int)]
 
 
+SP_WGN_POSE_ONLY, SP_WGN_PREDICTED_EXIT, SP_WGN_DEPTHS_FIXED = 1, 2, 4      # sp_window_gn_step's flags
 SP_CHAIN_LEVELS, SP_CHAIN_PHASES = 4, 6
 SP_CHAIN_TRACK, SP_CHAIN_SUPP, SP_CHAIN_CRITERION = 1, 2, 4
 

@@ -9,7 +9,7 @@
 //                      window is full (:594-603); every pose folded in T <- T inv(Exp(D)) and renormalised after the step (:861-882)
 //
 // but the step is a damped Newton step on the IRLS-weighted normal equations instead of Adam: ~10 iterations where Adam takes 300-500.
-// One iteration = sp_pairs_cost(mode 2) over all edges  ->  sp_window_gn_step = three launches (two when no depth may move, flags bits 0 / 2:
+// One iteration = sp_pairs_cost(mode 2) over all edges  ->  sp_window_gn_step = three launches (two when no depth may move, SP_WGN_POSE_ONLY / SP_WGN_DEPTHS_FIXED:
 // no Schur terms; one when such a window has at most SP_WGN_INLINE_EDGES edges and 64 unknowns: the update kernel reduces them itself):
 //
 //   k_window_gn_reduce (grid = edges)   fixed-order fp64 reduction of an edge's span / segment records into its local system over
@@ -35,6 +35,7 @@ namespace {
 #define SP_WGN_MAX_Y (8 * SP_WGN_MAX_NODES)      // unknowns of the reduced camera system (6 per free pose + 2 per free affine pair)
 #define SP_WGN_LDS_Y 192         // ... of which LDS holds this many (packed lower triangle, fp64); larger systems go through global scratch
 #define SP_WGN_STATE 16
+#define SP_WGN_NO_DEPTH_STEP (SP_WGN_POSE_ONLY | SP_WGN_DEPTHS_FIXED)      // no depth moves: no Schur terms, no per-segment sums
 #define SP_WGN_INLINE_REDUCE 0x100   // (internal flag bit, set by sp_window_gn_step: k_window_gn_update reduces the edges itself)
 #define SP_WGN_INLINE_EDGES 4        // ... for depth-less windows of at most this many edges
 
@@ -126,7 +127,7 @@ __device__ __forceinline__ void wgn_reduce_edge(const SpPair* __restrict__ pairs
             loc[256 + li] = t;
         }
     }
-    // (the per-segment sums feed the Schur terms only: a step in which no depth may move -- flags bits 0 / 2 -- never reads them)
+    // (the per-segment sums feed the Schur terms only: a step in which no depth may move, SP_WGN_NO_DEPTH_STEP, never reads them)
     if (!with_segments) return;
     const float* sp = seg_partials + (size_t)pr.rec0 * NS;
     for (int n = threadIdx.x; n < pr.N; n += blockDim.x) {
@@ -256,7 +257,7 @@ __device__ __forceinline__ int ltri_row(int t) {
 __global__ __launch_bounds__(SP_BLOCK) void k_window_gn_reduce_multi(const WGnArgs* __restrict__ wins) {
     const WGnArgs& w = wins[blockIdx.z];
     if ((int)blockIdx.x >= w.n_edges || (w.flags & SP_WGN_INLINE_REDUCE)) return;      // (inline: the update kernel reduces the edges itself)
-    wgn_reduce_edge(w.pairs, w.edges, w.span_partials, w.seg_partials, w.scratch, w.stride, w.Ad, w.loc, blockIdx.x, !(w.flags & 5));
+    wgn_reduce_edge(w.pairs, w.edges, w.span_partials, w.seg_partials, w.scratch, w.stride, w.Ad, w.loc, blockIdx.x, !(w.flags & SP_WGN_NO_DEPTH_STEP));
 }
 
 __global__ __launch_bounds__(SP_BLOCK) void k_window_gn_schur(WGnArgs w, const WGnArgs* __restrict__ wins) {
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_window_gn_schur(WGnArgs w, const W
     __shared__ double lam_s;
     const int tid = threadIdx.x, b = blockIdx.x, tile = blockIdx.y;
     const SpWindowBlock bk = w.blocks[b];
-    const bool frozen = (w.flags & 5) || !(bk.lr > 0.f);
+    const bool frozen = (w.flags & SP_WGN_NO_DEPTH_STEP) || !(bk.lr > 0.f);
     __shared__ int bN[SP_WGN_MAX_NODES];          // a block's N, negative if its depths are fixed
     for (int i = tid; i < w.n_nodes; i += SP_BLOCK) { aff_off[i] = wgn_node_flags(w.nodes[i]); lpose[i] = -1; laff[i] = -1; }
     for (int q = tid; q < w.n_blocks; q += SP_BLOCK) { const SpWindowBlock bq = w.blocks[q]; bN[q] = bq.lr > 0.f ? bq.N : -bq.N; }
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_window_gn_schur(WGnArgs w, const W
         for (int q = 0; q < w.n_blocks; ++q) {
             if (q == b) row0_s = off;
             off += abs(bN[q]);
-            if (!(w.flags & 5) && bN[q] > 0) free_depths += bN[q];
+            if (!(w.flags & SP_WGN_NO_DEPTH_STEP) && bN[q] > 0) free_depths += bN[q];
         }
         const WGnDecision d = wgn_decide(w, ny, SP_WGN_MAX_Y, loss, free_depths);
         dec_s = d.dec;
@@ -505,7 +506,7 @@ __global__ __launch_bounds__(wgn_update_threads(LDS_Y)) void k_window_gn_update(
         int off = 0, free_depths = 0;
         for (int b = 0; b < w.n_blocks; ++b) {
             const int N = blk_off[b];
-            if (!(w.flags & 5) && N > 0) free_depths += N;
+            if (!(w.flags & SP_WGN_NO_DEPTH_STEP) && N > 0) free_depths += N;
             blk_off[b] = off;
             off += abs(N);
         }
@@ -592,7 +593,7 @@ __global__ __launch_bounds__(wgn_update_threads(LDS_Y)) void k_window_gn_update(
     // ---- LM damping of the camera block, then minus the blocks' Schur terms (k_window_gn_schur), block after block ----
     for (int i = tid; i < n_y; i += NTHR) { H[ltri(i, i)] = H[ltri(i, i)] * (1.0 + lam) + 1e-12; g0[i] = g[i]; g[i] = -g[i]; }
     __syncthreads();
-    // (no depth may move -- a pose-only phase, or the caller's word that every block is fixed, flags bit 2: k_window_gn_schur was not launched,
+    // (no depth may move -- a pose-only phase, or the caller's word that every block is fixed, SP_WGN_DEPTHS_FIXED: k_window_gn_schur was not launched,
     //  its terms would all be zero)
     const int n_schur_blocks = free_s > 0 ? w.n_blocks : 0;
     for (int b = 0; b < n_schur_blocks; ++b) {
@@ -902,7 +903,7 @@ __global__ __launch_bounds__(wgn_update_threads(LDS_Y)) void k_window_gn_update(
     }
     WGN_STAMP(6);
     // ---- depth steps (back-substitution), clamped like the pair solver's ------------------------------------------
-    double gain = 0.0;                     // -(b . delta): what the step is predicted to buy (first-order change of the loss, flags bit 1)
+    double gain = 0.0;                     // -(b . delta): what the step is predicted to buy (first-order change of the loss, SP_WGN_PREDICTED_EXIT)
     if (!fail) {
         for (int i = tid; i < n_y; i += NTHR) gain -= g0[i] * dy[i];
         for (int b = 0; b < n_schur_blocks; ++b) {
@@ -970,7 +971,7 @@ __global__ __launch_bounds__(wgn_update_threads(LDS_Y)) void k_window_gn_update(
             }
         }
     }
-    if ((w.flags & 2) && w.conv_tol > 0.f) {
+    if ((w.flags & SP_WGN_PREDICTED_EXIT) && w.conv_tol > 0.f) {
         // PREDICTED EXIT (as SP_PHASE_PREDICTED_EXIT of the pair solver, include/sp_hip.h): the step just taken is predicted to buy less than
         // conv_tol of the loss -> the phase is over now, without the evaluation that would confirm it (on the few-edge windows of the
         // config-3 chain one evaluation is a fifth of a tracking phase).  Not under a heavy damping, not after a failed factorisation.
@@ -994,61 +995,67 @@ __global__ __launch_bounds__(wgn_update_threads(LDS_Y)) void k_window_gn_update(
 
 }  // namespace
 
+// The scratch of one window: every offset (in doubles) and the total, from the five numbers that size it; false: sizes no window can have.
+struct WgnLayout {
+    int stride, ldc, lds;                 // doubles per edge record; row length of C / Rhs / cols; packed triangle of the camera system
+    long long Ad, loc, C, Dinv, Bd, S, Rhs, cols, nc, prof, Hg, total;      // (cols / nc: ints, n_blocks x ldc doubles reserved for cols)
+};
+static bool wgn_layout(int n_edges, int n_blocks, int sum_N, int max_N, int n_unknowns, WgnLayout& L) {
+    if (n_edges <= 0 || n_blocks <= 0 || sum_N <= 0 || max_N <= 0 || n_unknowns < 0 || n_unknowns > SP_WGN_MAX_Y) return false;
+    const long long E = n_edges, B = n_blocks;
+    L.stride = SP_WGN_REC + SP_WGN_SEG * max_N; L.ldc = (n_unknowns + 1) & ~1; L.lds = n_unknowns * (n_unknowns + 1) / 2;
+    L.Ad = E * L.stride; L.loc = L.Ad + E * 36; L.C = L.loc + E * SP_WGN_LOC;                       // after the edge records: per edge
+    L.Dinv = L.C + (long long)sum_N * L.ldc; L.Bd = L.Dinv + sum_N; L.S = L.Bd + sum_N;             // per depth unknown
+    L.Rhs = L.S + B * L.lds; L.cols = L.Rhs + B * L.ldc; L.nc = L.cols + B * L.ldc;                 // per block
+    L.prof = L.nc + B + 2; L.Hg = L.prof + 16;
+    L.total = L.Hg + (n_unknowns > SP_WGN_LDS_Y ? L.lds : 0) + B + 6;      // (the global-memory triangle beyond SP_WGN_LDS_Y; n_blocks + 6 of slack)
+    return true;
+}
+
+// the argument record of one window (what sp_window_gn_step passes its kernels by value and sp_window_gn_run_multi keeps per window in device memory)
+static int wgn_fill_args(WGnArgs& w, const SpWindowGn& g, int flags, float lm_up, float lm_down, float lm_min, float conv_tol) {
+    if (!g.pairs || !g.edges || !g.nodes || !g.blocks || !g.span_partials || !g.seg_partials || !g.scratch || !g.nodes_backup || !g.kld_backup ||
+        !g.state || !g.losses)
+        return SP_EINVAL;
+    if (g.n_edges <= 0 || g.n_nodes <= 0 || g.n_blocks <= 0 || g.sum_N <= 0 || g.max_N <= 0 || g.max_losses < 0 || g.n_unknowns < 0) return SP_EINVAL;
+    if (g.n_nodes > SP_WGN_MAX_NODES || g.n_blocks > SP_WGN_MAX_NODES || g.n_unknowns > SP_WGN_MAX_Y) return SP_ELIMIT;
+    WgnLayout L;
+    if (!wgn_layout(g.n_edges, g.n_blocks, g.sum_N, g.max_N, g.n_unknowns, L)) return SP_EINVAL;
+    double* const sc = g.scratch;
+    w.span_partials = g.span_partials; w.seg_partials = g.seg_partials;
+    w.pairs = g.pairs; w.edges = g.edges; w.n_edges = g.n_edges; w.nodes = g.nodes; w.n_nodes = g.n_nodes; w.blocks = g.blocks; w.n_blocks = g.n_blocks;
+    w.max_N = g.max_N; w.scratch = sc; w.stride = L.stride; w.ldc = L.ldc; w.lds = L.lds; w.cap_y = g.n_unknowns;
+    w.Ad = sc + L.Ad; w.loc = sc + L.loc; w.C = sc + L.C; w.Dinv = sc + L.Dinv; w.Bd = sc + L.Bd; w.S = sc + L.S; w.Rhs = sc + L.Rhs;
+    w.cols = reinterpret_cast<int*>(sc + L.cols); w.nc = reinterpret_cast<int*>(sc + L.nc); w.prof = sc + L.prof; w.Hg = sc + L.Hg;
+    w.nodes_backup = g.nodes_backup; w.kld_backup = g.kld_backup; w.flags = flags;
+    w.lm_up = lm_up; w.lm_down = lm_down; w.lm_min = lm_min; w.conv_tol = conv_tol;
+    w.state = g.state; w.losses = g.losses; w.max_losses = g.max_losses;
+    return 0;
+}
+
+// the update kernel's instantiation for n_y camera unknowns, over n windows (blockIdx.z; one: `w`, several: `wins`)
+static void wgn_launch_update(int n_y, int n, hipStream_t s, const WGnArgs& w, const WGnArgs* wins) {
+    const dim3 grid(1, 1, n);
+    if (n_y <= 64) hipLaunchKernelGGL(k_window_gn_update<64>, grid, dim3(wgn_update_threads(64)), 0, s, w, wins);
+    else if (n_y <= 128) hipLaunchKernelGGL(k_window_gn_update<128>, grid, dim3(wgn_update_threads(128)), 0, s, w, wins);
+    else if (n_y <= SP_WGN_LDS_Y) hipLaunchKernelGGL(k_window_gn_update<SP_WGN_LDS_Y>, grid, dim3(wgn_update_threads(SP_WGN_LDS_Y)), 0, s, w, wins);
+    else hipLaunchKernelGGL(k_window_gn_update<0>, grid, dim3(wgn_update_threads(0)), 0, s, w, wins);
+}
+
 extern "C" {
 
 // n_unknowns: camera unknowns the window can have (6 per node with lr_pose > 0 + 2 per node with lr_aff > 0)
 int sp_window_gn_scratch_doubles(int n_edges, int n_blocks, int sum_N, int max_N, int n_unknowns) {
-    if (n_edges <= 0 || n_blocks <= 0 || sum_N <= 0 || max_N <= 0 || n_unknowns < 0 || n_unknowns > SP_WGN_MAX_Y) return 0;
-    const long long ldc = (n_unknowns + 1) & ~1;
-    const long long tri = (long long)n_unknowns * (n_unknowns + 1) / 2;
-    const long long hg = n_unknowns > SP_WGN_LDS_Y ? tri : 0;
-    const long long n = (long long)n_edges * (SP_WGN_REC + SP_WGN_SEG * max_N) + (long long)n_edges * (36 + SP_WGN_LOC) + (long long)sum_N * (ldc + 2) + (long long)n_blocks * (tri + 2 * ldc + 2) + hg + 8 + 16;
-    return n > 0x7fffffffLL ? 0 : (int)n;
+    WgnLayout L;
+    return wgn_layout(n_edges, n_blocks, sum_N, max_N, n_unknowns, L) && L.total <= 0x7fffffffLL ? (int)L.total : 0;
 }
 
 // offset (in doubles) inside the scratch of the 16 time stamps the update kernel leaves (wall_clock64 ticks, 100 MHz): [0] entry,
 // [1] decision taken, [2] backup + clear, [3] assembly, [4] Schur terms subtracted, [5] factorisation, [6] substitutions, [7] depth
 // steps, [8] poses, [9] edges recomposed
 int sp_window_gn_profile_offset(int n_edges, int n_blocks, int sum_N, int max_N, int n_unknowns) {
-    if (n_edges <= 0 || n_blocks <= 0 || sum_N <= 0 || max_N <= 0 || n_unknowns < 0 || n_unknowns > SP_WGN_MAX_Y) return -1;
-    const long long ldc = (n_unknowns + 1) & ~1;
-    const long long tri = (long long)n_unknowns * (n_unknowns + 1) / 2;
-    return (int)((long long)n_edges * (SP_WGN_REC + SP_WGN_SEG * max_N) + (long long)n_edges * (36 + SP_WGN_LOC) + (long long)sum_N * (ldc + 2) +
-                 (long long)n_blocks * (tri + 2 * ldc) + n_blocks + 2);
-}
-
-// the argument record of one window (what sp_window_gn_step passes its kernels by value and sp_window_gn_run_multi keeps per window in device memory)
-static int wgn_fill_args(WGnArgs& w, const SpPair* pairs, const SpWindowEdge* edges, int n_edges, SpWindowNode* nodes, int n_nodes,
-                         const SpWindowBlock* blocks, int n_blocks, int sum_N, int max_N, int n_unknowns, const float* span_partials,
-                         const float* seg_partials, double* scratch, SpWindowNode* nodes_backup, float* kld_backup, int flags,
-                         float lm_up, float lm_down, float lm_min, float conv_tol, float* state, float* losses, int max_losses) {
-    if (!pairs || !edges || !nodes || !blocks || !span_partials || !seg_partials || !scratch || !nodes_backup || !kld_backup || !state ||
-        !losses)
-        return SP_EINVAL;
-    if (n_edges <= 0 || n_nodes <= 0 || n_blocks <= 0 || sum_N <= 0 || max_N <= 0 || max_losses < 0 || n_unknowns < 0) return SP_EINVAL;
-    if (n_nodes > SP_WGN_MAX_NODES || n_blocks > SP_WGN_MAX_NODES || n_unknowns > SP_WGN_MAX_Y) return SP_ELIMIT;
-    const int stride = SP_WGN_REC + SP_WGN_SEG * max_N;
-    w.span_partials = span_partials; w.seg_partials = seg_partials;
-    w.pairs = pairs; w.edges = edges; w.n_edges = n_edges; w.nodes = nodes; w.n_nodes = n_nodes; w.blocks = blocks; w.n_blocks = n_blocks;
-    w.max_N = max_N; w.scratch = scratch; w.stride = stride;
-    w.ldc = (n_unknowns + 1) & ~1;
-    w.lds = n_unknowns * (n_unknowns + 1) / 2;
-    w.cap_y = n_unknowns;
-    w.Ad = scratch + (size_t)n_edges * stride;
-    w.loc = w.Ad + (size_t)n_edges * 36;
-    w.C = w.loc + (size_t)n_edges * SP_WGN_LOC;
-    w.Dinv = w.C + (size_t)sum_N * w.ldc;
-    w.Bd = w.Dinv + sum_N;
-    w.S = w.Bd + sum_N;
-    w.Rhs = w.S + (size_t)n_blocks * w.lds;
-    w.cols = reinterpret_cast<int*>(w.Rhs + (size_t)n_blocks * w.ldc);           // n_blocks x ldc ints in n_blocks x ldc / 2 doubles' room ...
-    w.nc = reinterpret_cast<int*>(w.Rhs + (size_t)n_blocks * w.ldc * 2);         // ... (a full n_blocks x ldc doubles are reserved)
-    w.prof = w.Rhs + (size_t)n_blocks * w.ldc * 2 + n_blocks + 2;
-    w.Hg = w.prof + 16;
-    w.nodes_backup = nodes_backup; w.kld_backup = kld_backup; w.flags = flags;
-    w.lm_up = lm_up; w.lm_down = lm_down; w.lm_min = lm_min; w.conv_tol = conv_tol;
-    w.state = state; w.losses = losses; w.max_losses = max_losses;
-    return 0;
+    WgnLayout L;
+    return wgn_layout(n_edges, n_blocks, sum_N, max_N, n_unknowns, L) ? (int)L.prof : -1;
 }
 
 int sp_window_gn_step(const SpPair* pairs, const SpWindowEdge* edges, int n_edges, SpWindowNode* nodes, int n_nodes,
@@ -1056,30 +1063,26 @@ int sp_window_gn_step(const SpPair* pairs, const SpWindowEdge* edges, int n_edge
                       const float* seg_partials, double* scratch, SpWindowNode* nodes_backup, float* kld_backup, int flags,
                       float lm_up, float lm_down, float lm_min, float conv_tol, float* state, float* losses, int max_losses,
                       void* stream) {
+    const SpWindowGn g{pairs, nullptr, nullptr, edges, nodes, blocks, const_cast<float*>(span_partials), const_cast<float*>(seg_partials), scratch,
+                       nodes_backup, kld_backup, state, losses, 0, n_edges, n_nodes, n_blocks, sum_N, max_N, n_unknowns, max_losses};      // (field order; no work list)
     WGnArgs w;
-    if (int rc = wgn_fill_args(w, pairs, edges, n_edges, nodes, n_nodes, blocks, n_blocks, sum_N, max_N, n_unknowns, span_partials, seg_partials, scratch,
-                               nodes_backup, kld_backup, flags, lm_up, lm_down, lm_min, conv_tol, state, losses, max_losses))
-        return rc;
+    if (int rc = wgn_fill_args(w, g, flags, lm_up, lm_down, lm_min, conv_tol)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int stride = w.stride;
     // (no depth moves and a handful of edges -- the tracker: the update kernel reduces them itself, one launch less per iteration)
-    const bool inline_reduce = (flags & 5) && n_edges <= SP_WGN_INLINE_EDGES && n_unknowns <= 64 && !getenv("SP_WGN_NO_INLINE");
+    const bool inline_reduce = (flags & SP_WGN_NO_DEPTH_STEP) && n_edges <= SP_WGN_INLINE_EDGES && n_unknowns <= 64 && !getenv("SP_WGN_NO_INLINE");
     if (inline_reduce) w.flags |= SP_WGN_INLINE_REDUCE;
     else {
-        hipLaunchKernelGGL(k_window_gn_reduce, dim3(n_edges), dim3(SP_BLOCK), 0, s, pairs, edges, span_partials, seg_partials, scratch, stride, w.Ad, w.loc,
-                           (flags & 5) ? 0 : 1);
+        hipLaunchKernelGGL(k_window_gn_reduce, dim3(n_edges), dim3(SP_BLOCK), 0, s, pairs, edges, span_partials, seg_partials, scratch, w.stride, w.Ad, w.loc,
+                           (flags & SP_WGN_NO_DEPTH_STEP) ? 0 : 1);
         SP_CHECK_LAUNCH();
     }
     const int tiles = max(1, (w.lds + SP_BLOCK * SP_WGN_PPT - 1) / (SP_BLOCK * SP_WGN_PPT));
     const WGnArgs* none = nullptr;
-    if (!(flags & 5)) {                // (flags bit 0 / bit 2: no depth moves -- every Schur term is zero and the update kernel does not read them)
+    if (!(flags & SP_WGN_NO_DEPTH_STEP)) {                // (no depth moves -- every Schur term is zero and the update kernel does not read them)
         hipLaunchKernelGGL(k_window_gn_schur, dim3(n_blocks, tiles), dim3(SP_BLOCK), 0, s, w, none);
         SP_CHECK_LAUNCH();
     }
-    if (n_unknowns <= 64) hipLaunchKernelGGL(k_window_gn_update<64>, dim3(1), dim3(wgn_update_threads(64)), 0, s, w, none);
-    else if (n_unknowns <= 128) hipLaunchKernelGGL(k_window_gn_update<128>, dim3(1), dim3(wgn_update_threads(128)), 0, s, w, none);
-    else if (n_unknowns <= SP_WGN_LDS_Y) hipLaunchKernelGGL(k_window_gn_update<SP_WGN_LDS_Y>, dim3(1), dim3(wgn_update_threads(SP_WGN_LDS_Y)), 0, s, w, none);
-    else hipLaunchKernelGGL(k_window_gn_update<0>, dim3(1), dim3(wgn_update_threads(0)), 0, s, w, none);
+    wgn_launch_update(n_unknowns, 1, s, w, none);
     SP_CHECK_LAUNCH();
     return 0;
 }
@@ -1168,10 +1171,7 @@ int wgn_multi_fill(const SpWindowGn* const* windows, int n, int flags, float lm_
     for (int i = 0; i < n; ++i) {
         const SpWindowGn& g = *windows[i];
         if (!g.chunks || !g.spans || g.n_spans <= 0) return SP_EINVAL;
-        if (int rc = wgn_fill_args(host[i], g.pairs, g.edges, g.n_edges, g.nodes, g.n_nodes, g.blocks, g.n_blocks, g.sum_N, g.max_N, g.n_unknowns,
-                                   g.span_partials, g.seg_partials, g.scratch, g.nodes_backup, g.kld_backup, flags, lm_up, lm_down, lm_min, conv_tol,
-                                   g.state, g.losses, g.max_losses))
-            return rc;
+        if (int rc = wgn_fill_args(host[i], g, flags, lm_up, lm_down, lm_min, conv_tol)) return rc;
         lists_host[i] = MultiList{g.pairs, g.chunks, g.spans, g.span_partials, g.seg_partials, g.n_spans, total_blocks};
         total_blocks += (g.n_spans + 7) / 8 * 8;
         max_edges = std::max(max_edges, g.n_edges); max_blocks = std::max(max_blocks, g.n_blocks); max_y = std::max(max_y, g.n_unknowns);
@@ -1182,7 +1182,7 @@ int wgn_multi_fill(const SpWindowGn* const* windows, int n, int flags, float lm_
         for (int i = 0; i < n; ++i) if (windows[i]->n_unknowns <= SP_WGN_LDS_Y) return SP_EINVAL;
     // the inline reduction of sp_window_gn_step, window by window under the same test (the 64-unknown instantiation is the only one that has it)
     int n_reduce = n;
-    if (allow_inline && max_y <= 64 && (flags & 5) && !getenv("SP_WGN_NO_INLINE"))
+    if (allow_inline && max_y <= 64 && (flags & SP_WGN_NO_DEPTH_STEP) && !getenv("SP_WGN_NO_INLINE"))
         for (int i = 0; i < n; ++i)
             if (host[i].n_edges <= SP_WGN_INLINE_EDGES) { host[i].flags |= SP_WGN_INLINE_REDUCE; --n_reduce; }
     *info = WgnMultiInfo{total_blocks, max_edges, max_blocks, max_y, n_reduce};
@@ -1199,11 +1199,8 @@ int wgn_multi_round(const void* args_dev, const MultiList* lists_dev, int n, con
     int rc = cost_pairs_multi(lists_dev, n, info.total_blocks, 2, irls_eps, stream);
     if (rc != 0) return rc < 0 ? rc : sp_hip_rc((hipError_t)rc);
     if (info.n_reduce > 0) hipLaunchKernelGGL(k_window_gn_reduce_multi, dim3(info.max_edges, 1, n), dim3(SP_BLOCK), 0, s, wins);
-    if (!(flags & 5)) hipLaunchKernelGGL(k_window_gn_schur, dim3(info.max_blocks, tiles, n), dim3(SP_BLOCK), 0, s, dummy, wins);
-    if (max_y <= 64) hipLaunchKernelGGL(k_window_gn_update<64>, dim3(1, 1, n), dim3(wgn_update_threads(64)), 0, s, dummy, wins);
-    else if (max_y <= 128) hipLaunchKernelGGL(k_window_gn_update<128>, dim3(1, 1, n), dim3(wgn_update_threads(128)), 0, s, dummy, wins);
-    else if (max_y <= SP_WGN_LDS_Y) hipLaunchKernelGGL(k_window_gn_update<SP_WGN_LDS_Y>, dim3(1, 1, n), dim3(wgn_update_threads(SP_WGN_LDS_Y)), 0, s, dummy, wins);
-    else hipLaunchKernelGGL(k_window_gn_update<0>, dim3(1, 1, n), dim3(wgn_update_threads(0)), 0, s, dummy, wins);
+    if (!(flags & SP_WGN_NO_DEPTH_STEP)) hipLaunchKernelGGL(k_window_gn_schur, dim3(info.max_blocks, tiles, n), dim3(SP_BLOCK), 0, s, dummy, wins);
+    wgn_launch_update(max_y, n, s, dummy, wins);
     return sp_hip_rc(hipGetLastError());
 }
 

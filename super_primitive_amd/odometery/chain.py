@@ -20,31 +20,22 @@ SUPP_CHECK_FIRST = int(_os.environ.get("SP_SUPP_CHECK_FIRST", "1"))
 TRACK, SUPP, CRITERION = _lib.SP_CHAIN_TRACK, _lib.SP_CHAIN_SUPP, _lib.SP_CHAIN_CRITERION
 
 
-def _gn_record(rec, win, level):
-    """``SpWindowGn`` of a built ``PoseWindow`` at one pyramid level (what ``PoseWindow.run_gn`` passes ``sp_window_gn_run``)."""
-    gn, d = win._gn_state(), win.desc[level]
-    rec.pairs, rec.chunks, rec.spans, rec.edges, rec.nodes, rec.blocks = d.data_ptr(), win.chunks.data_ptr(), win.spans.data_ptr(), win.edges.data_ptr(), win.nodes.data_ptr(), win.blocks.data_ptr()
-    rec.span_partials, rec.seg_partials, rec.scratch = win.partials.data_ptr(), win.seg_partials.data_ptr(), gn['scratch'].data_ptr()
-    rec.nodes_backup, rec.kld_backup, rec.state, rec.losses = gn['nodes_backup'].data_ptr(), gn['kld_backup'].data_ptr(), gn['state'].data_ptr(), gn['losses'].data_ptr()
-    rec.n_spans, rec.n_edges, rec.n_nodes, rec.n_blocks = win.n_spans, win.n_edges, win.n_nodes, win.n_sources
-    rec.sum_N, rec.max_N, rec.n_unknowns, rec.max_losses = gn['sum_N'], win.max_N, gn['n_y'], win.max_iters
-
-
 def _bind_window(cw, win, phases, check_first=0):
-    """phases: [(pyramid level, max iterations, irls_eps, conv_tol)] -- the schedule ``run_gn`` is called with, phase by phase."""
+    """phases: [(pyramid level, max iterations, irls_eps, conv_tol)] -- the schedule ``run_gn`` is called with, phase by phase
+    (``loops.track_gn_phases`` / ``map_gn_phases``)."""
     assert len(phases) <= _lib.SP_CHAIN_PHASES and max(win.level_ids) < _lib.SP_CHAIN_LEVELS
     for l in range(_lib.SP_CHAIN_LEVELS):
         cw.gn[l].pairs = None
     for l in win.level_ids:
-        _gn_record(cw.gn[l], win, l)
+        win.gn_record(l, cw.gn[l])
     for p, (level, n, eps, tol) in enumerate(phases):
         cw.phase[p].level, cw.phase[p].max_iters, cw.phase[p].irls_eps, cw.phase[p].conv_tol = int(level), int(n), float(eps), float(tol)
     cw.n_phases = len(phases)
     cw.check_every = _window.GN_CHECK_EVERY
     cw.check_first = int(check_first)
-    cw.flags = (2 if _window.GN_PREDICTED_EXIT else 0) | (4 if win.depths_fixed else 0)
-    cw.lam0, cw.lm_up, cw.lm_down, cw.lm_min = 1e-4, 8.0, 0.5, 1e-7          # (PoseWindow.reset_gn / run_gn defaults)
-    cw.state_host = win._gn_state()['state_host'].data_ptr()
+    cw.flags = _window.gn_flags(False, _window.GN_PREDICTED_EXIT, win.depths_fixed)
+    cw.lam0, cw.lm_up, cw.lm_down, cw.lm_min = (_window.GN_LM[k] for k in ('lam0', 'lm_up', 'lm_down', 'lm_min'))
+    cw.state_host = win.gn_state_host_ptr()
 
 
 class ChainStep:
@@ -81,11 +72,8 @@ class ChainStep:
     # ---- the windows of the latest keyframe ---------------------------------------------------------------------------------------------
     def bind_tracker(self, tracker, kf, affine):
         """``tracker``: a built ``loops.GnTracker`` (node 0 = the keyframe, node 1 = the tracked frame)."""
-        st, win, sch = self.st, tracker.win, tracker.sch
-        phases = [(l, n, sch['irls_eps'], sch['conv_tol']) for l, n in tracker.phases]
-        if sch['polish_max'] > 0:
-            phases.append((win.level_ids[0], sch['polish_max'], sch['polish_eps'], sch['polish_tol']))
-        _bind_window(st.track, win, phases)
+        st, win = self.st, tracker.win
+        _bind_window(st.track, win, tracker.phases)
         tg = st.track_target
         tg.node = 1
         for l in range(_lib.SP_CHAIN_LEVELS):
@@ -105,11 +93,8 @@ class ChainStep:
 
     def bind_mapper(self, mapper):
         """``mapper``: a built ``loops.GnSuppMapper`` of the same keyframe as the bound tracker."""
-        st, win, gn = self.st, mapper.win, mapper.gn
-        phases = [(0, min(mapper.num_iters, gn['max_iters']), gn['irls_eps'], gn['conv_tol'])]
-        if gn['polish_max'] > 0 and mapper.num_iters > gn['max_iters'] // 2:
-            phases.append((0, gn['polish_max'], gn['polish_eps'], gn['polish_tol']))
-        _bind_window(st.supp, win, phases, check_first=SUPP_CHECK_FIRST)      # (the depths of a keyframe that has been mapped every frame move in one step)
+        st, win = self.st, mapper.win
+        _bind_window(st.supp, win, mapper.phases, check_first=SUPP_CHECK_FIRST)      # (the depths of a keyframe that has been mapped every frame move in one step)
         for j in range(2):
             tg = st.supp_target[j]
             tg.node = mapper.slots[j]
@@ -171,8 +156,7 @@ class ChainStep:
         """After the call: the windows' pinned LM states are current; (tracker iterations, mapper iterations, criterion | None)."""
         st = self.st
         for w in ((self.tracker.win,) if stages & TRACK else ()) + ((self.mapper.win,) if stages & SUPP else ()):
-            w._gn.pop('host_stale', None)                # (the call left the pinned copy of the LM state current)
-            w._gn['host_seen'] = True
+            w.gn_host_current()
         crit = self.crit_host.tolist() if stages & CRITERION else None
         return st.track_iters, st.supp_iters, crit
 

@@ -125,6 +125,43 @@ TRACK_GN_SCHEDULE = dict(phases=((1, 4), (0, 6)), conv_tol=2e-3, irls_eps=1e-3, 
 MAP_GN_SCHEDULE = dict(max_iters=25, conv_tol=1e-3, irls_eps=1e-3, polish_max=12, polish_eps=1e-5, polish_tol=1e-5)
 
 
+def track_gn_phases(sch, levels, finest):
+    """[(level, max iterations, irls_eps, conv_tol)] of a ``TRACK_GN_SCHEDULE``-shaped ``sch``: its phases inside ``levels``, then the polish at ``finest``."""
+    out = [(int(l), int(n), sch['irls_eps'], sch['conv_tol']) for l, n in sch['phases'] if levels[0] <= int(l) < levels[1]]
+    if sch['polish_max'] > 0:
+        out.append((finest, sch['polish_max'], sch['polish_eps'], sch['polish_tol']))
+    return out
+
+
+def map_gn_phases(gn, num_iters):
+    """... of a ``MAP_GN_SCHEDULE``-shaped ``gn``: the main phase, capped by ``num_iters``, then the polish (a short budget gets none)."""
+    out = [(0, min(num_iters, gn['max_iters']), gn['irls_eps'], gn['conv_tol'])]
+    if gn['polish_max'] > 0 and num_iters > gn['max_iters'] // 2:
+        out.append((0, gn['polish_max'], gn['polish_eps'], gn['polish_tol']))
+    return out
+
+
+def run_gn_phases(win, phases):
+    """One ``PoseWindow.run_gn`` per phase; returns the iterations they took."""
+    return sum(win.run_gn(level, n, irls_eps=eps, conv_tol=tol) for level, n, eps, tol in phases)
+
+
+def _tracking_window(kf, kld, kf_pose, kf_aff, frame, frame_pose, frame_aff, levels, phases, share_sources):
+    """Node 0 = the keyframe (fixed, its depths too), node 1 = the tracked frame (6 pose + 2 affine unknowns; none without ``kf_aff``), one edge."""
+    from ..optim.window import KIND_WINDOW, PoseWindow
+    affine = kf_aff is not None
+    nodes = [dict(T=kf_pose, kind=KIND_WINDOW, aff=kf_aff),
+             dict(T=frame_pose, kind=KIND_WINDOW, lr_pose=1.0, lr_aff=1.0 if affine else 0.0, aff=frame_aff if affine else None,
+                  image=frame.image, K=frame.K)]
+    return PoseWindow([dict(kf=kf, kld=kld, lr=0.0, node=0)], nodes, [(0, 1, 1.0, dense_optim.Z_MIN_SINGLE)], levels, abs_loss=False,
+                      use_affine=affine, max_iters=sum(n for _, n, _, _ in phases) + 8, share_sources=share_sources)
+
+
+def _tracking_result(win, affine, its):
+    T = renormalise_se3(win.node_poses()[1].contiguous())
+    return T, (win.node_affines()[1] if affine else None), list(win.gn_losses().unbind(0)), its
+
+
 def track_frame_gn(kf, kld, supp_frame, supp_T, prev_pose, levels, prev_aff=None, curr_aff=None, schedule=None):
     """Frame-to-keyframe tracking (odometery/odometery.py:300-312,375-407) by Gauss-Newton / LM instead of 300 Adam steps: 6 pose
     + 2 affine unknowns of the tracked frame against the latest keyframe's points (its depths fixed), coarse to fine over the
@@ -132,22 +169,9 @@ def track_frame_gn(kf, kld, supp_frame, supp_T, prev_pose, levels, prev_aff=None
     Exp(d) inv(T_supp) T_prev, fold-in T_supp <- T_supp inv(Exp(d)) after every step, renormalise_se3 at the end -- so the result
     is directly comparable with ``track_frame`` / ``track_frame_fused`` run to convergence.
     Returns (supp_T, curr_aff, losses, iterations)."""
-    from ..optim.window import KIND_WINDOW, PoseWindow
-    sch = dict(TRACK_GN_SCHEDULE, **(schedule or {}))
-    affine = prev_aff is not None
-    nodes = [dict(T=prev_pose, kind=KIND_WINDOW, aff=prev_aff if affine else None),
-             dict(T=supp_T, kind=KIND_WINDOW, lr_pose=1.0, lr_aff=1.0 if affine else 0.0, aff=curr_aff if affine else None,
-                  image=supp_frame.image, K=supp_frame.K)]
-    phases = [(int(l), int(n)) for l, n in sch['phases'] if levels[0] <= int(l) < levels[1]]
-    win = PoseWindow([dict(kf=kf, kld=kld, lr=0.0, node=0)], nodes, [(0, 1, 1.0, dense_optim.Z_MIN_SINGLE)], levels,
-                     abs_loss=False, use_affine=affine, max_iters=sum(n for _, n in phases) + sch['polish_max'] + 8)
-    its = 0
-    for level, n in phases:
-        its += win.run_gn(level, n, irls_eps=sch['irls_eps'], conv_tol=sch['conv_tol'])
-    if sch['polish_max'] > 0:
-        its += win.run_gn(win.level_ids[0], sch['polish_max'], irls_eps=sch['polish_eps'], conv_tol=sch['polish_tol'])
-    T = renormalise_se3(win.node_poses()[1].contiguous())
-    return T, (win.node_affines()[1] if affine else None), list(win.gn_losses().unbind(0)), its
+    phases = track_gn_phases(dict(TRACK_GN_SCHEDULE, **(schedule or {})), levels, levels[0])
+    win = _tracking_window(kf, kld, prev_pose, prev_aff, supp_frame, supp_T, curr_aff, levels, phases, share_sources=False)
+    return _tracking_result(win, prev_aff is not None, run_gn_phases(win, phases))
 
 
 class GnTracker:
@@ -158,17 +182,10 @@ class GnTracker:
     result), at a fraction of the per-frame cost (tools/run_configs.py)."""
 
     def __init__(self, kf, kld, kf_pose, frame, levels, kf_aff=None, schedule=None):
-        from ..optim.window import KIND_WINDOW, PoseWindow
-        self.sch = dict(TRACK_GN_SCHEDULE, **(schedule or {}))
         self.affine = kf_aff is not None
-        dev = kf.image.device
-        z2 = torch.zeros(2, device=dev)
-        nodes = [dict(T=kf_pose, kind=KIND_WINDOW, aff=kf_aff if self.affine else None),
-                 dict(T=kf_pose, kind=KIND_WINDOW, lr_pose=1.0, lr_aff=1.0 if self.affine else 0.0, aff=z2 if self.affine else None,
-                      image=frame.image, K=frame.K)]
-        self.phases = [(int(l), int(n)) for l, n in self.sch['phases'] if levels[0] <= int(l) < levels[1]]
-        self.win = PoseWindow([dict(kf=kf, kld=kld, lr=0.0, node=0)], nodes, [(0, 1, 1.0, dense_optim.Z_MIN_SINGLE)], levels, abs_loss=False,
-                              use_affine=self.affine, max_iters=sum(n for _, n in self.phases) + self.sch['polish_max'] + 8, share_sources=True)
+        self.phases = track_gn_phases(dict(TRACK_GN_SCHEDULE, **(schedule or {})), levels, levels[0])      # (what ``chain.ChainStep`` binds too)
+        self.win = _tracking_window(kf, kld, kf_pose, kf_aff, frame, kf_pose, torch.zeros(2, device=kf.image.device), levels, self.phases,
+                                    share_sources=True)
         self._first_image = frame.image
 
     def update_keyframe(self, kld=None, kf_pose=None, kf_aff=None):
@@ -180,19 +197,13 @@ class GnTracker:
 
     def track(self, frame, supp_T, curr_aff=None):
         """Returns (supp_T, curr_aff, losses, iterations) like ``track_frame_gn``."""
-        win, sch = self.win, self.sch
+        win = self.win
         if frame.image is not self._first_image:
             win.set_target_image(1, frame.image)
         self._first_image = None
         win.set_nodes({1: dict(T=supp_T, aff=curr_aff if self.affine else None)})
         win.reset_gn()
-        its = 0
-        for level, n in self.phases:
-            its += win.run_gn(level, n, irls_eps=sch['irls_eps'], conv_tol=sch['conv_tol'])
-        if sch['polish_max'] > 0:
-            its += win.run_gn(win.level_ids[0], sch['polish_max'], irls_eps=sch['polish_eps'], conv_tol=sch['polish_tol'])
-        T = renormalise_se3(win.node_poses()[1].contiguous())
-        return T, (win.node_affines()[1] if self.affine else None), list(win.gn_losses().unbind(0)), its
+        return _tracking_result(win, self.affine, run_gn_phases(win, self.phases))
 
 
 def window_connectivity(n_kfs, mode='map'):
@@ -236,15 +247,12 @@ def map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose=1e-4, w
     (``sp_window_gn_step``; MAP_GN_SCHEDULE, ``num_iters`` caps the main phase) instead of Adam.
     Returns dict(kf_poses (K,4,4), klds [K], affs (K,2)|None, supp_poses [[...]], supp_affs [[...]], losses, stopped)."""
     assert mode in ('map', 'init', 'supp')
-    K = len(kfs)
-    affine = kf_affs is not None
-    frozen0 = K == window_size
+    affine, frozen0 = kf_affs is not None, len(kfs) == window_size
     if optimiser == "gn":
         ctx = map_window_gn_begin(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose=lr_pose, window_size=window_size,
                                   initialised=initialised, rel_tol=rel_tol, gn_schedule=gn_schedule, mode=mode)
         if ctx['win'] is not None:
-            for level, n, eps, tol in map_window_gn_phases(ctx):
-                ctx['n'] += ctx['win'].run_gn(level, n, irls_eps=eps, conv_tol=tol)
+            ctx['n'] = run_gn_phases(ctx['win'], map_window_gn_phases(ctx))
         return map_window_gn_end(ctx)
     if fused:
         return _map_window_fused(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode)
@@ -271,11 +279,11 @@ class GnSuppMapper:
         assert len(supp[-1]) in (1, 2), "built once the latest keyframe has a running supporting frame"
         self.K = K = len(kfs)
         self.affine = kf_affs is not None
-        self.gn = dict(MAP_GN_SCHEDULE, **(gn_schedule or {}))
-        self.num_iters = int(num_iters)
+        gn = dict(MAP_GN_SCHEDULE, **(gn_schedule or {}))
+        self.phases = map_gn_phases(gn, int(num_iters))              # (what ``chain.ChainStep`` binds too)
         rows = list(supp[:-1]) + [list(supp[-1]) * (3 - len(supp[-1]))]
         self.win, self.supp_node, src_ids = _build_map_window(kfs, kf_poses, kf_klds, kf_affs, rows, num_iters, 1e-4, K == window_size, self.affine, True,
-                                                              1e-8, 'supp', self.gn)
+                                                              1e-8, 'supp', gn)
         assert src_ids == [K - 1]
         self.slots = [self.supp_node[(K - 1, 0)], self.supp_node[(K - 1, 1)]]
         self.frames = [rows[-1][0][0], rows[-1][1][0]]               # the frame objects whose images sit in the slots
@@ -302,7 +310,7 @@ class GnSuppMapper:
     def __call__(self, running):
         """running: the latest keyframe's running supporting frames [(frame, pose, aff)], older first (two, or one).  Returns (the latest
         keyframe's new log-depths, losses, iterations)."""
-        win, gn = self.win, self.gn
+        win = self.win
         assert len(running) in (1, 2)
         if len(running) == 1:
             running = [running[0], running[0]]
@@ -318,9 +326,7 @@ class GnSuppMapper:
                 self.frames[j] = running[j][0]
         win.set_nodes({self.slots[j]: dict(T=running[j][1], aff=running[j][2] if self.affine else None) for j in range(2)})
         win.reset_gn()
-        n = win.run_gn(0, min(self.num_iters, gn['max_iters']), irls_eps=gn['irls_eps'], conv_tol=gn['conv_tol'])
-        if gn['polish_max'] > 0 and self.num_iters > gn['max_iters'] // 2:
-            n += win.run_gn(0, gn['polish_max'], irls_eps=gn['polish_eps'], conv_tol=gn['polish_tol'])
+        n = run_gn_phases(win, self.phases)
         return win.klds()[0], win.gn_losses(), n
 
 
@@ -366,58 +372,28 @@ def map_window_gn_begin(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pos
     """``map_window(..., optimiser='gn')`` in three parts -- this one builds the window; ``map_window_gn_phases`` lists its Gauss-Newton
     phases (run them with ``PoseWindow.run_gn`` or, for several windows side by side, ``PoseWindowBatch.run_gn``); ``map_window_gn_end``
     reads the result.  Returns the context the other two take."""
-    K = len(kfs)
-    affine = kf_affs is not None
     gn = dict(MAP_GN_SCHEDULE, **(gn_schedule or {}))
-    win, supp_node, src_ids = _build_map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, K == window_size, affine, initialised,
-                                                rel_tol, mode, gn)
-    return dict(win=win, supp_node=supp_node, src_ids=src_ids, K=K, affine=affine, gn=gn, num_iters=num_iters, kf_poses=kf_poses,
-                kf_klds=kf_klds, kf_affs=kf_affs, supp=supp, n=0)
+    win, supp_node, src_ids = _build_map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, len(kfs) == window_size, kf_affs is not None,
+                                                initialised, rel_tol, mode, gn)
+    return dict(win=win, supp_node=supp_node, src_ids=src_ids, gn=gn, num_iters=num_iters, kf_poses=kf_poses, kf_klds=kf_klds, kf_affs=kf_affs,
+                supp=supp, n=0)
 
 
 def map_window_gn_phases(ctx):
-    """[(level, max iterations, irls_eps, conv_tol)]: the main phase, then the polish (a short budget -- the supplementary mapping -- gets none)."""
-    gn, num_iters = ctx['gn'], ctx['num_iters']
-    out = [(0, min(num_iters, gn['max_iters']), gn['irls_eps'], gn['conv_tol'])]
-    if gn['polish_max'] > 0 and num_iters > gn['max_iters'] // 2:
-        out.append((0, gn['polish_max'], gn['polish_eps'], gn['polish_tol']))
-    return out
+    """``map_gn_phases`` of the context ``map_window_gn_begin`` returned."""
+    return map_gn_phases(ctx['gn'], ctx['num_iters'])
 
 
-def map_window_gn_end(ctx):
-    """``map_window``'s result once the phases ran (``ctx['n']``: the iterations they took)."""
-    K, affine, win, supp_node, src_ids, supp = ctx['K'], ctx['affine'], ctx['win'], ctx['supp_node'], ctx['src_ids'], ctx['supp']
-    kf_poses, kf_klds, kf_affs = ctx['kf_poses'], ctx['kf_klds'], ctx['kf_affs']
+def _map_window_result(win, supp_node, src_ids, kf_poses, kf_klds, kf_affs, supp, read):
+    """``map_window``'s dict from ``_build_map_window``'s results (no window: the inputs come back).  ``read(win)``: (loss history, ``stopped``, extras)."""
+    K, affine = len(kf_poses), kf_affs is not None
     det = lambda x: x.detach().clone()
-    if win is None:                                                # a single keyframe without supporting frames: nothing to match
+    if win is None:
         return dict(kf_poses=torch.stack([det(p) for p in kf_poses]), klds=[det(k) for k in kf_klds],
                     affs=torch.stack([det(a) for a in kf_affs]) if affine else None, supp_poses=[[] for _ in range(K)],
                     supp_affs=[[] for _ in range(K)] if affine else None, losses=[torch.zeros((), device=kf_poses[0].device)], stopped=-1)
-    poses, affs, losses = win.node_poses(), win.node_affines(), win.gn_losses()
-    extra = dict(gn=win.gn_stats())
-    if ctx['gn'].get('profile', False):                            # (phase time stamps of the last update kernel: a read-back, diagnostics only)
-        extra['gn_profile'] = win.gn_profile()
-    wk = win.klds()
-    klds = [det(k) for k in kf_klds]
-    for b, s in enumerate(src_ids):
-        klds[s] = wk[b]
-    return dict(kf_poses=poses[:K], klds=klds, affs=affs[:K] if affine else None,
-                supp_poses=[[poses[supp_node[(k, j)]] for j in range(len(supp[k]))] for k in range(K)],
-                supp_affs=[[affs[supp_node[(k, j)]] for j in range(len(supp[k]))] for k in range(K)] if affine else None,
-                losses=list(losses.unbind(0)), stopped=ctx['n'], **extra)
-
-
-def _map_window_fused(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode='map'):
-    K = len(kfs)
-    win, supp_node, src_ids = _build_map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode, None)
-    det = lambda x: x.detach().clone()
-    if win is None:                                                # a single keyframe without supporting frames: nothing to match
-        return dict(kf_poses=torch.stack([det(p) for p in kf_poses]), klds=[det(k) for k in kf_klds],
-                    affs=torch.stack([det(a) for a in kf_affs]) if affine else None, supp_poses=[[] for _ in range(K)],
-                    supp_affs=[[] for _ in range(K)] if affine else None, losses=[torch.zeros((), device=kf_poses[0].device)], stopped=-1)
-    win.run(0, num_iters)
-    poses, affs, losses = win.node_poses(), win.node_affines(), win.losses()
-    stopped, extra = (win.iterations() - 1 if win.converged() else -1), {}
+    poses, affs = win.node_poses(), win.node_affines()
+    losses, stopped, extra = read(win)
     wk = win.klds()
     klds = [det(k) for k in kf_klds]
     for b, s in enumerate(src_ids):
@@ -426,6 +402,24 @@ def _map_window_fused(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose,
                 supp_poses=[[poses[supp_node[(k, j)]] for j in range(len(supp[k]))] for k in range(K)],
                 supp_affs=[[affs[supp_node[(k, j)]] for j in range(len(supp[k]))] for k in range(K)] if affine else None,
                 losses=list(losses.unbind(0)), stopped=stopped, **extra)
+
+
+def map_window_gn_end(ctx):
+    """``map_window``'s result once the phases ran (``ctx['n']``: the iterations they took)."""
+    def read(win):
+        extra = dict(gn=win.gn_stats())
+        if ctx['gn'].get('profile', False):                        # (phase time stamps of the last update kernel: a read-back, diagnostics only)
+            extra['gn_profile'] = win.gn_profile()
+        return win.gn_losses(), ctx['n'], extra
+    return _map_window_result(ctx['win'], ctx['supp_node'], ctx['src_ids'], ctx['kf_poses'], ctx['kf_klds'], ctx['kf_affs'], ctx['supp'], read)
+
+
+def _map_window_fused(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode='map'):
+    win, supp_node, src_ids = _build_map_window(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode, None)
+    if win is not None:
+        win.run(0, num_iters)
+    return _map_window_result(win, supp_node, src_ids, kf_poses, kf_klds, kf_affs, supp,
+                              lambda w: (w.losses(), w.iterations() - 1 if w.converged() else -1, {}))
 
 
 def _map_window_eager(kfs, kf_poses, kf_klds, kf_affs, supp, num_iters, lr_pose, frozen0, affine, initialised, rel_tol, mode='map'):

@@ -152,20 +152,25 @@ class MonoVO:
             self.current_ts = self.curr_supp[-1].ts
 
     # ---- tracking (odometery.py:323-449) --------------------------------------------------------------------------
+    def _gn_tracker(self, f):
+        """The latest keyframe's Gauss-Newton tracker, built with frame ``f`` in its target slot on first use."""
+        if self.tracker is None:
+            self.tracker = GnTracker(self.kfs[-1], self.kf_klds[-1], self.kf_poses[-1], f, self.c['track_levels'],
+                                     kf_aff=self.kf_affs[-1] if self.affine else None)
+        return self.tracker
+
     def track_frame(self, i):
         f, c = self.frames[i], self.c
         supp_T = self.current_track
         if c['motion_prior'] and len(self.tracked) >= 2:            # apply_motion_prior, :314-321 (the reference switches it off, :324)
             supp_T = (self.current_track @ invertSE3(self.tracked[-2].pose)) @ supp_T
-        aff_kf = self.kf_affs[-1] if self.affine else None
         _sync(); t0 = time.perf_counter()
         if self.engine == "gn":
-            if self.tracker is None:
-                self.tracker = GnTracker(self.kfs[-1], self.kf_klds[-1], self.kf_poses[-1], f, c['track_levels'], kf_aff=aff_kf)
-            T, aff, _, _ = self.tracker.track(f, supp_T, self.current_aff if self.affine else None)
+            T, aff, _, _ = self._gn_tracker(f).track(f, supp_T, self.current_aff if self.affine else None)
         else:
             T, aff, _ = track_frame_fused(self.kfs[-1], self.kf_klds[-1], f, supp_T, self.kf_poses[-1], list(c['track_steps']), c['track_levels'],
-                                          lr=c['track_lr'], prev_aff=aff_kf, curr_aff=self.current_aff if self.affine else None)
+                                          lr=c['track_lr'], prev_aff=self.kf_affs[-1] if self.affine else None,
+                                          curr_aff=self.current_aff if self.affine else None)
         _sync(); self.secs['track'] += time.perf_counter() - t0
         self.current_track = T.detach().clone()
         if self.affine:
@@ -175,6 +180,16 @@ class MonoVO:
         self.track.append(self.current_track.clone())
 
     # ---- mapping (odometery.py:687-967) ---------------------------------------------------------------------------
+    def _supp_rows(self):
+        """get_supp_kf_poses_pairs (:481-521; none before initialisation): (rows of ``_Supp``, the same as (frame, pose, affine pair) tuples)."""
+        K = len(self.kfs)
+        rows = [(self.curr_supp if k == K - 1 else self.supp_opt[k]) if self.initialised else [] for k in range(K)]
+        return rows, [[(s.frame, s.pose, s.aff) for s in row] for row in rows]
+
+    def _new_supp_mapper(self, supp, num_iters):
+        return GnSuppMapper(self.kfs, self.kf_poses, self.kf_klds, self.kf_affs if self.affine else None, supp, num_iters,
+                            window_size=self.c['window_size'])
+
     def mapping(self, num_iters, mode='map'):
         assert mode in ('init', 'map', 'supp')
         c = self.c
@@ -184,9 +199,7 @@ class MonoVO:
         else:
             self.tracked_poses_to_supp()
         K = len(self.kfs)
-        # get_supp_kf_poses_pairs (:481-521): no supporting frames at all before the system is initialised
-        rows = [(self.curr_supp if k == K - 1 else self.supp_opt[k]) if self.initialised else [] for k in range(K)]
-        supp = [[(s.frame, s.pose, s.aff) for s in row] for row in rows]
+        rows, supp = self._supp_rows()
         lr_pose = 1e-2 if (mode == 'init' and c['mono_init']) else c['map_lr_pose']
         if mode == 'supp' and self.engine == "gn" and c['persistent_supp'] and self.initialised and len(self.curr_supp) in (1, 2):
             # the supplementary mapping between two keyframes is the same window every frame but for the running supporting frames (two; one
@@ -194,9 +207,8 @@ class MonoVO:
             # same arithmetic, same result as the branch below
             _sync(); t0 = time.perf_counter()
             if self.supp_mapper is None:
-                self.supp_mapper = GnSuppMapper(self.kfs, self.kf_poses, self.kf_klds, self.kf_affs if self.affine else None, supp, num_iters,
-                                                window_size=c['window_size'])
-            kld, _, _ = self.supp_mapper([(s.frame, s.pose, s.aff) for s in self.curr_supp])
+                self.supp_mapper = self._new_supp_mapper(supp, num_iters)
+            kld, _, _ = self.supp_mapper(supp[-1])
             _sync(); self.secs['supp_mapping'] += time.perf_counter() - t0
             self.kf_klds[-1] = kld
             self.n_map[mode] += 1
@@ -266,13 +278,23 @@ class MonoVO:
     def estimate_depth_latest_kf(self, pose):
         return estimate_depth_kf_native(self.kfs[-1], self.kf_klds[-1], invertSE3(pose) @ self.kf_poses[-1])
 
+    def _crit_wants_kf(self, crit):
+        """The keyframe rule on the criterion's values [validity ratio, scale, translation diff, rotation deg] (odometery.py:986-1016)."""
+        return crit[0] < self.c['depth_validity_ratio'] or crit[2] > self.c['translation_thresh']
+
     def is_kf(self, i):
-        c = self.c
         if not self.initialised:
-            return i == c['init_frames'], None
+            return i == self.c['init_frames'], None
         est = self.estimate_depth_latest_kf(self.current_track)
-        crit = keyframe_criterion(self.current_track, self.kf_poses[-1], est).tolist()      # [validity ratio, scale, translation diff, rotation deg]
-        return (crit[0] < c['depth_validity_ratio'] or crit[2] > c['translation_thresh']), (est, crit)
+        crit = keyframe_criterion(self.current_track, self.kf_poses[-1], est).tolist()
+        return self._crit_wants_kf(crit), (est, crit)
+
+    def _new_keyframe(self, i, info):
+        """Frame ``i`` becomes the latest keyframe; the tracked pool goes to its predecessor (odometery.py:1056-1075)."""
+        self.flush_tracked_poses_to_supp()
+        self.init_keyframe(i, info)
+        self.reset_tracked_poses()
+        self.reset_running_supp_kfs()
 
     def init_keyframe(self, i, info):
         # (``to_keyframe`` is the FRONTEND -- segmentation and per-segment depth shapes, out of the hot path's scope: its time is kept apart
@@ -308,9 +330,7 @@ class MonoVO:
             self.mapping(c['continual_steps'], mode='supp')
         if self.mapping_scheduled and len(self.curr_supp) >= 2:
             self.mapping(c['map_steps'], mode='map')
-            self.mapping_scheduled = False
-            self.reset_tracked_poses()
-            self.reset_running_supp_kfs()
+            self._mapping_done()
         assert self.current_ts == i
         self.keyframe_stage(i)
 
@@ -346,10 +366,7 @@ class MonoVO:
             H, W = f.image.shape[-2:]
             self.chain = ChainStep(len(self.frames), H, W, c['track_levels'][1], self.dev)
         ch = self.chain
-        aff_kf = self.kf_affs[-1] if self.affine else None
-        if self.tracker is None:
-            self.tracker = GnTracker(self.kfs[-1], self.kf_klds[-1], self.kf_poses[-1], f, c['track_levels'], kf_aff=aff_kf)
-        if ch.tracker is not self.tracker:
+        if ch.tracker is not self._gn_tracker(f):
             ch.bind_tracker(self.tracker, self.kfs[-1], self.affine)
         want_supp = c['continual_steps'] > 0
         native_supp = want_supp and c['persistent_supp']
@@ -360,8 +377,7 @@ class MonoVO:
                 K = len(self.kfs)
                 rows = [[(s.frame, s.pose, s.aff) for s in self.supp_opt[k]] for k in range(K - 1)]
                 rows.append(([(prev.frame, prev.pose, prev.aff)] if prev is not None else []) + [(f, self.current_track, self.current_aff)])
-                self.supp_mapper = GnSuppMapper(self.kfs, self.kf_poses, self.kf_klds, self.kf_affs if self.affine else None, rows, c['continual_steps'],
-                                                window_size=c['window_size'])
+                self.supp_mapper = self._new_supp_mapper(rows, c['continual_steps'])
             m = self.supp_mapper
             if ch.mapper is not m:
                 ch.bind_mapper(m)
@@ -412,10 +428,8 @@ class MonoVO:
         """``mapping(map_steps, mode='map')`` up to its window: (mapping context, its (positional, keyword) window arguments)."""
         c = self.c
         self.tracked_poses_to_supp()
-        K = len(self.kfs)
-        rows = [(self.curr_supp if k == K - 1 else self.supp_opt[k]) if self.initialised else [] for k in range(K)]
-        supp = [[(s.frame, s.pose, s.aff) for s in row] for row in rows]
-        ctx = self._mapping_begin(c['map_steps'], 'map', K, rows, supp, c['map_lr_pose'])
+        rows, supp = self._supp_rows()
+        ctx = self._mapping_begin(c['map_steps'], 'map', len(self.kfs), rows, supp, c['map_lr_pose'])
         return ctx, self._map_args(ctx)
 
     def _native_criterion_job(self):
@@ -428,13 +442,9 @@ class MonoVO:
 
     def _native_keyframe(self, i, crit):
         """Keyframe decision on the criterion's values and, for a new keyframe, its creation.  Returns the decision."""
-        c = self.c
-        new_kf = crit[0] < c['depth_validity_ratio'] or crit[2] > c['translation_thresh']
+        new_kf = self._crit_wants_kf(crit)
         if new_kf:
-            self.flush_tracked_poses_to_supp()
-            self.init_keyframe(i, (self.chain.depth, crit))
-            self.reset_tracked_poses()
-            self.reset_running_supp_kfs()
+            self._new_keyframe(i, (self.chain.depth, crit))
             _sync()
             self.mapping_scheduled = True
         return new_kf
@@ -446,10 +456,7 @@ class MonoVO:
         _sync(); t0 = time.perf_counter()
         new_kf, info = self.is_kf(i)
         if new_kf:
-            self.flush_tracked_poses_to_supp()
-            self.init_keyframe(i, info)
-            self.reset_tracked_poses()
-            self.reset_running_supp_kfs()
+            self._new_keyframe(i, info)
         _sync(); self.secs['keyframe'] += time.perf_counter() - t0
         if new_kf:
             if not self.initialised:

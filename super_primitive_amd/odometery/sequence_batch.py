@@ -13,7 +13,7 @@ import time
 import torch
 
 from ..optim.window import PoseWindowBatch
-from .loops import map_window_gn_begin, map_window_gn_end, map_window_gn_phases
+from .loops import map_window_gn_begin, map_window_gn_end, map_window_gn_phases, run_gn_phases
 from .sequence import DEFAULTS, MonoVO
 
 _LDS_Y = 192          # PoseWindowBatch: windows of at most this many camera unknowns, or all above, ride together
@@ -50,8 +50,7 @@ def _run_mappings(due, counters):
         win = m['win']
         if win is None:
             continue
-        n_y = win._gn_state()['n_y']
-        key = (None, id(m)) if win.depths_fixed else (n_y > _LDS_Y, tuple(map_window_gn_phases(m)))
+        key = (None, id(m)) if win.depths_fixed else (win.gn_unknowns > _LDS_Y, tuple(map_window_gn_phases(m)))
         groups.setdefault(key, []).append(m)
     for key, ms in groups.items():
         phases = map_window_gn_phases(ms[0])
@@ -62,11 +61,10 @@ def _run_mappings(due, counters):
             counters['mapping_batches'] += 1
             counters['windows_per_batch'].append(len(ms))
         else:
-            for level, n, eps, tol in phases:
-                ms[0]['win'].run_gn(level, n, irls_eps=eps, conv_tol=tol)
+            run_gn_phases(ms[0]['win'], phases)
             counters['mappings_alone'] += 1
         for m in ms:
-            m['n'] = int(m['win']._gn_state()['state_host'][5])
+            m['n'] = m['win'].gn_iterations()        # (the pinned copy the run's last poll left: no read-back)
     for mvo, ctx, m in parts:
         mvo._mapping_end(ctx, map_window_gn_end(m))
         mvo._mapping_done()

@@ -41,6 +41,16 @@ def _upload_struct_array(arr, device):
 import os as _os
 GN_CHECK_EVERY = int(_os.environ.get("SP_GN_CHECK_EVERY", "4"))
 GN_PREDICTED_EXIT = _os.environ.get("SP_GN_PREDICTED_EXIT", "1") != "0"
+# The LM constants every Gauss-Newton window starts from (lam0) and steps with, and the flag word of sp_window_gn_step (include/sp_hip.h).
+GN_LM = dict(lam0=1e-4, lm_up=8.0, lm_down=0.5, lm_min=1e-7)
+
+
+def gn_flags(pose_only=False, predicted_exit=False, depths_fixed=False):
+    return _lib.SP_WGN_POSE_ONLY * bool(pose_only) | _lib.SP_WGN_PREDICTED_EXIT * bool(predicted_exit) | _lib.SP_WGN_DEPTHS_FIXED * bool(depths_fixed)
+
+
+def _lm(over):          # (lm_up, lm_down, lm_min) of one call: GN_LM under the caller's overrides
+    return tuple(float(dict(GN_LM, **over)[k]) for k in ('lm_up', 'lm_down', 'lm_min'))
 
 
 class PoseWindow:
@@ -111,7 +121,7 @@ class PoseWindow:
             blocks[k].N = self.Ns[k]
             blocks[k].lr = float(s.get('lr', 0.0))
         self._blocks_host = blocks
-        self.depths_fixed = all(float(s_.get('lr', 0.0)) == 0.0 for s_ in sources)     # (sp_window_gn_step flags bit 2: no Schur launch)
+        self.depths_fixed = all(float(s_.get('lr', 0.0)) == 0.0 for s_ in sources)     # (SP_WGN_DEPTHS_FIXED: no Schur launch)
         # ---- pose nodes ----------------------------------------------------------------------------------------
         arr = (_lib.SpWindowNode * self.n_nodes)()
         # (ONE read-back for all poses and one for all affine pairs: a .cpu() per node was a host synchronisation each)
@@ -294,9 +304,7 @@ class PoseWindow:
     def _gn_state(self):
         if self._gn is None:
             sum_N = int(self.n_off[-1])
-            n_y = 0
-            for nd in self._node_array():
-                n_y += (6 if nd.lr_pose > 0 else 0) + (2 if nd.lr_aff > 0 else 0)
+            n_y = sum((6 if nd.lr_pose > 0 else 0) + (2 if nd.lr_aff > 0 else 0) for nd in self._node_array())
             if n_y > 512 or self.n_nodes > 64 or self.n_sources > 64:
                 raise ValueError(f"{n_y} camera unknowns / {self.n_nodes} nodes / {self.n_sources} source keyframes exceed the 512 / 64 / 64 "
                                  "the Gauss-Newton window solver holds; use the Adam optimiser")
@@ -304,13 +312,13 @@ class PoseWindow:
                 scratch=torch.zeros(self.lib.sp_window_gn_scratch_doubles(self.n_edges, self.n_sources, sum_N, self.max_N, n_y), dtype=torch.float64, device=self.device),
                 nodes_backup=torch.zeros_like(self.nodes), kld_backup=torch.zeros(sum_N, dtype=torch.float32, device=self.device),
                 state=torch.zeros(16, dtype=torch.float32, device=self.device), state_host=torch.zeros(16, dtype=torch.float32).pin_memory(),
-                losses=torch.zeros(self.max_iters, dtype=torch.float32, device=self.device), sum_N=sum_N, n_y=n_y,
+                losses=torch.zeros(self.max_iters, dtype=torch.float32, device=self.device), sum_N=sum_N, n_y=n_y, host_stale=False,
                 phase_keep=torch.tensor([1, 0, 1, 1, 0, 1, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1], dtype=torch.float32, device=self.device),
                 phase_set=torch.tensor([0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0], dtype=torch.float32, device=self.device))
             self.reset_gn()
         return self._gn
 
-    def reset_gn(self, lam=1e-4):
+    def reset_gn(self, lam=GN_LM['lam0']):
         """Fresh LM state (lambda, no accepted point yet, not converged); the loss history restarts."""
         gn = self._gn_state() if self._gn is None else self._gn
         gn['state'].zero_()
@@ -326,58 +334,75 @@ class PoseWindow:
         gn['state'].mul_(gn['phase_keep']).add_(gn['phase_set'])          # [1] = -1, [4] = [6] = 0 in two launches, no host value involved
         gn['host_seen'] = False
 
-    def gn_step(self, level, irls_eps=1e-3, pose_only=False, conv_tol=0.0, lm_up=8.0, lm_down=0.5, lm_min=1e-7):
-        """One Gauss-Newton / LM iteration of the whole window at pyramid ``level`` (3 launches, nothing returns to the host):
-        the cost pass in mode 2 (normal equations incl. the affine brightness columns) + ``sp_window_gn_step``."""
-        gn = self._gn_state()
-        d = self.desc[level]
-        _lib.check(self.lib.sp_pairs_cost(_lib.ptr(d), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, 2, float(irls_eps),
-                                          _lib.ptr(self.partials), _lib.ptr(self.seg_partials), _lib.stream_ptr()), "sp_pairs_cost")
-        _lib.check(self.lib.sp_window_gn_step(_lib.ptr(d), _lib.ptr(self.edges), self.n_edges, _lib.ptr(self.nodes), self.n_nodes,
-                                              _lib.ptr(self.blocks), self.n_sources, gn['sum_N'], self.max_N, gn['n_y'], _lib.ptr(self.partials),
-                                              _lib.ptr(self.seg_partials), _lib.ptr(gn['scratch']), _lib.ptr(gn['nodes_backup']),
-                                              _lib.ptr(gn['kld_backup']), (1 if pose_only else 0) | (4 if self.depths_fixed else 0), float(lm_up), float(lm_down), float(lm_min),
-                                              float(conv_tol), _lib.ptr(gn['state']), _lib.ptr(gn['losses']), self.max_iters,
-                                              _lib.stream_ptr()), "sp_window_gn_step")
-        gn['host_stale'] = True
+    def gn_record(self, level, rec=None):
+        """The ``SpWindowGn`` of this window at pyramid ``level`` (include/sp_hip.h), filled into ``rec`` or a new record; returns it."""
+        gn, d = self._gn_state(), self.desc[level]
+        rec = _lib.SpWindowGn() if rec is None else rec
+        rec.pairs, rec.chunks, rec.spans, rec.edges, rec.nodes, rec.blocks = d.data_ptr(), self.chunks.data_ptr(), self.spans.data_ptr(), self.edges.data_ptr(), self.nodes.data_ptr(), self.blocks.data_ptr()
+        rec.span_partials, rec.seg_partials, rec.scratch = self.partials.data_ptr(), self.seg_partials.data_ptr(), gn['scratch'].data_ptr()
+        rec.nodes_backup, rec.kld_backup, rec.state, rec.losses = gn['nodes_backup'].data_ptr(), gn['kld_backup'].data_ptr(), gn['state'].data_ptr(), gn['losses'].data_ptr()
+        rec.n_spans, rec.n_edges, rec.n_nodes, rec.n_blocks = self.n_spans, self.n_edges, self.n_nodes, self.n_sources
+        rec.sum_N, rec.max_N, rec.n_unknowns, rec.max_losses = gn['sum_N'], self.max_N, gn['n_y'], self.max_iters
+        return rec
 
-    def run_gn(self, level, max_iters, irls_eps=1e-3, conv_tol=2e-3, pose_only=False, check_every=None, lm_up=8.0, lm_down=0.5, lm_min=1e-7,
-               predicted_exit=None):
+    def gn_step(self, level, irls_eps=1e-3, pose_only=False, conv_tol=0.0, **lm):
+        """One Gauss-Newton / LM iteration of the whole window at pyramid ``level`` (3 launches, nothing returns to the host):
+        the cost pass in mode 2 (normal equations incl. the affine brightness columns) + ``sp_window_gn_step``.  ``lm``: GN_LM overrides."""
+        r = self.gn_record(level)
+        _lib.check(self.lib.sp_pairs_cost(r.pairs, r.chunks, r.spans, r.n_spans, 2, float(irls_eps), r.span_partials, r.seg_partials,
+                                          _lib.stream_ptr()), "sp_pairs_cost")
+        _lib.check(self.lib.sp_window_gn_step(r.pairs, r.edges, r.n_edges, r.nodes, r.n_nodes, r.blocks, r.n_blocks, r.sum_N, r.max_N, r.n_unknowns,
+                                              r.span_partials, r.seg_partials, r.scratch, r.nodes_backup, r.kld_backup,
+                                              gn_flags(pose_only, False, self.depths_fixed), *_lm(lm), float(conv_tol), r.state, r.losses,
+                                              r.max_losses, _lib.stream_ptr()), "sp_window_gn_step")
+        self._gn['host_stale'] = True
+
+    def run_gn(self, level, max_iters, irls_eps=1e-3, conv_tol=2e-3, pose_only=False, check_every=None, predicted_exit=None, **lm):
         """Up to ``max_iters`` LM iterations at ``level`` as ONE phase: stops once an accepted step lowers the loss by less than
         ``conv_tol`` of it (the device freezes the window -- launches after that change nothing; the host loop, ONE foreign call
         ``sp_window_gn_run``, looks at the state every ``check_every`` iterations).  Returns the iterations the phase really took
         (evaluations of the cost, rejected ones and the final converged-test evaluation included), from the device's counter.
         ``predicted_exit`` (default GN_PREDICTED_EXIT): the phase also ends right after a step PREDICTED to buy less than ``conv_tol`` of the
-        loss (flags bit 1 of sp_window_gn_step; the pair solver's SP_PHASE_PREDICTED_EXIT) -- without the evaluation that confirms it."""
-        gn = self._gn_state()
-        if check_every is None:
-            check_every = GN_CHECK_EVERY
-        if predicted_exit is None:
-            predicted_exit = GN_PREDICTED_EXIT
+        loss (SP_WGN_PREDICTED_EXIT; the pair solver's SP_PHASE_PREDICTED_EXIT) -- without the evaluation that confirms it.  ``lm``: as ``gn_step``."""
+        check_every = GN_CHECK_EVERY if check_every is None else check_every
+        predicted_exit = GN_PREDICTED_EXIT if predicted_exit is None else predicted_exit
         self.begin_gn_phase()
-        if gn.pop('host_stale', False):             # (ADVICE r04: gn_step() moved the device's counter since the host last saw it)
-            gn['state_host'].copy_(gn['state'])
-        n0 = int(gn['state_host'][5])
-        d = self.desc[level]
-        rc = self.lib.sp_window_gn_run(_lib.ptr(d), _lib.ptr(self.chunks), _lib.ptr(self.spans), self.n_spans, float(irls_eps), _lib.ptr(self.edges),
-                                       self.n_edges, _lib.ptr(self.nodes), self.n_nodes, _lib.ptr(self.blocks), self.n_sources, gn['sum_N'],
-                                       self.max_N, gn['n_y'], _lib.ptr(self.partials), _lib.ptr(self.seg_partials), _lib.ptr(gn['scratch']),
-                                       _lib.ptr(gn['nodes_backup']), _lib.ptr(gn['kld_backup']), (1 if pose_only else 0) | (2 if predicted_exit else 0) | (4 if self.depths_fixed else 0), float(lm_up),
-                                       float(lm_down), float(lm_min), float(conv_tol), _lib.ptr(gn['state']), _lib.ptr(gn['losses']),
-                                       self.max_iters, int(max_iters), int(check_every), gn['state_host'].data_ptr(), _lib.stream_ptr())
+        r, host = self.gn_record(level), self._gn['state_host']
+        if self._gn['host_stale']:                  # (ADVICE r04: gn_step() moved the device's counter since the host last saw it)
+            host.copy_(self._gn['state'])
+            self._gn['host_stale'] = False
+        n0 = int(host[5])
+        rc = self.lib.sp_window_gn_run(r.pairs, r.chunks, r.spans, r.n_spans, float(irls_eps), r.edges, r.n_edges, r.nodes, r.n_nodes, r.blocks,
+                                       r.n_blocks, r.sum_N, r.max_N, r.n_unknowns, r.span_partials, r.seg_partials, r.scratch, r.nodes_backup,
+                                       r.kld_backup, gn_flags(pose_only, predicted_exit, self.depths_fixed), *_lm(lm), float(conv_tol), r.state,
+                                       r.losses, r.max_losses, int(max_iters), int(check_every), host.data_ptr(), _lib.stream_ptr())
         if rc < 0:
             _lib.check(rc, "sp_window_gn_run")
-        gn['host_seen'] = int(max_iters) > 0            # (the run's last poll left the pinned copy current)
-        return int(gn['state_host'][5]) - n0
+        if int(max_iters) > 0:
+            self.gn_host_current()
+        return int(host[5]) - n0
+
+    @property
+    def gn_unknowns(self):
+        """The camera unknowns of the window (6 per free pose + 2 per free affine pair): what sizes its scratch and picks its update kernel."""
+        return self._gn_state()['n_y']
+
+    def gn_state_host_ptr(self):
+        """Address of the pinned 16-float copy of the LM state (``SpChainWindow.state_host``)."""
+        return self._gn_state()['state_host'].data_ptr()
+
+    def gn_host_current(self, values=None):
+        """A foreign call has just left the pinned LM state current; ``values``: the 16 floats, where it polled into an array of its own."""
+        if values is not None:
+            self._gn['state_host'].copy_(values)
+        self._gn.update(host_stale=False, host_seen=True)
 
     def _gn_host_state(self):
         """The 16-float LM state on the host: the pinned copy ``run_gn`` / ``sp_chain_step_multi`` left behind when nothing has moved the device's
         since (no read-back, no synchronisation), else a fresh copy."""
         gn = self._gn_state()
-        if gn.get('host_stale', False) or not gn.get('host_seen', False):
-            gn['state_host'].copy_(gn['state'])
-            gn.pop('host_stale', None)
-            gn['host_seen'] = True
+        if gn['host_stale'] or not gn['host_seen']:
+            self.gn_host_current(gn['state'])
         return gn['state_host']
 
     def gn_converged(self):
@@ -511,8 +536,6 @@ class PoseWindowBatch:
         self.lib = windows[0].lib
         self.device = windows[0].device
         S = len(self.windows)
-        for w in self.windows:
-            w._gn_state()
         self.args_dev = torch.empty(S * self.lib.sp_window_gn_multi_bytes() + 64, dtype=torch.uint8, device=self.device)
         self.states_dev = torch.zeros(S * 16, dtype=torch.float32, device=self.device)
         self.states_host = torch.zeros(S * 16, dtype=torch.float32).pin_memory()
@@ -522,35 +545,29 @@ class PoseWindowBatch:
         if level not in self._desc:
             arr = (_lib.SpWindowGn * len(self.windows))()
             for i, w in enumerate(self.windows):
-                gn, d, a = w._gn_state(), w.desc[level], arr[i]
-                a.pairs, a.chunks, a.spans, a.edges, a.nodes, a.blocks = d.data_ptr(), w.chunks.data_ptr(), w.spans.data_ptr(), w.edges.data_ptr(), w.nodes.data_ptr(), w.blocks.data_ptr()
-                a.span_partials, a.seg_partials, a.scratch = w.partials.data_ptr(), w.seg_partials.data_ptr(), gn['scratch'].data_ptr()
-                a.nodes_backup, a.kld_backup, a.state, a.losses = gn['nodes_backup'].data_ptr(), gn['kld_backup'].data_ptr(), gn['state'].data_ptr(), gn['losses'].data_ptr()
-                a.n_spans, a.n_edges, a.n_nodes, a.n_blocks = w.n_spans, w.n_edges, w.n_nodes, w.n_sources
-                a.sum_N, a.max_N, a.n_unknowns, a.max_losses = gn['sum_N'], w.max_N, gn['n_y'], w.max_iters
+                w.gn_record(level, arr[i])
             self._desc[level] = arr
         return self._desc[level]
 
-    def reset_gn(self, lam=1e-4):
+    def reset_gn(self, lam=GN_LM['lam0']):
         for w in self.windows:
             w.reset_gn(lam)
 
-    def run_gn(self, level, max_iters, irls_eps=1e-3, conv_tol=2e-3, pose_only=False, check_every=None, lm_up=8.0, lm_down=0.5, lm_min=1e-7,
-               predicted_exit=None):
+    def run_gn(self, level, max_iters, irls_eps=1e-3, conv_tol=2e-3, pose_only=False, check_every=None, predicted_exit=None, **lm):
         """One Gauss-Newton phase of EVERY window (``PoseWindow.run_gn``'s arguments); ends when every window has converged or after
         ``max_iters``.  Returns the rounds launched."""
-        if check_every is None:
-            check_every = GN_CHECK_EVERY
-        if predicted_exit is None:
-            predicted_exit = GN_PREDICTED_EXIT
+        check_every = GN_CHECK_EVERY if check_every is None else check_every
+        predicted_exit = GN_PREDICTED_EXIT if predicted_exit is None else predicted_exit
         for w in self.windows:
             w.begin_gn_phase()
         arr = self._records(level)
-        rc = self.lib.sp_window_gn_run_multi(ctypes.addressof(arr), len(self.windows), float(irls_eps), (1 if pose_only else 0) | (2 if predicted_exit else 0),
-                                             float(lm_up), float(lm_down), float(lm_min), float(conv_tol), int(max_iters), int(check_every),
-                                             _lib.ptr(self.args_dev), _lib.ptr(self.states_dev), self.states_host.data_ptr(), _lib.stream_ptr())
+        # (one flag word for all, without SP_WGN_DEPTHS_FIXED: odometery/sequence_batch.py runs a window whose depths are all fixed alone)
+        rc = self.lib.sp_window_gn_run_multi(ctypes.addressof(arr), len(self.windows), float(irls_eps), gn_flags(pose_only, predicted_exit), *_lm(lm),
+                                             float(conv_tol), int(max_iters), int(check_every), _lib.ptr(self.args_dev), _lib.ptr(self.states_dev),
+                                             self.states_host.data_ptr(), _lib.stream_ptr())
         if rc < 0:
             _lib.check(rc, "sp_window_gn_run_multi")
-        for i, w in enumerate(self.windows):
-            w._gn['state_host'].copy_(self.states_host[16 * i: 16 * i + 16])
+        if int(max_iters) > 0:                       # (the last poll of the call: the device's states as they stand)
+            for i, w in enumerate(self.windows):
+                w.gn_host_current(self.states_host[16 * i: 16 * i + 16])
         return rc

@@ -163,6 +163,76 @@ def test_window_gn_freezes_when_converged_and_undoes_rejected_steps():
             np.testing.assert_allclose(L[i + 1], L[i - 1], rtol=1e-6)
 
 
+def test_host_copy_of_the_lm_state_is_the_devices_after_every_kind_of_call():
+    """The window keeps a pinned copy of its 16-float LM state and flags for when that copy is current; four calls move the device's state:
+    ``gn_step``, ``run_gn``, ``PoseWindowBatch.run_gn`` and ``ChainStep.run(TRACK)`` through a ``GnTracker``.  After each of them, and
+    whatever came before, ``gn_stats`` / ``gn_iterations`` / ``gn_converged`` report the device's state as read here directly, and ``run_gn``
+    counts its iterations from the device's counter (a ``gn_step`` since the last look included).  On the 60 x 80, 6-segment, one-edge
+    tracking window of the test above."""
+    from super_primitive_amd import synth
+    from super_primitive_amd.core import dense_optim
+    from super_primitive_amd.image.keyframe import KeyFrame
+    from super_primitive_amd.odometery.chain import TRACK, ChainStep
+    from super_primitive_amd.odometery.loops import GnTracker
+    from super_primitive_amd.optim.window import KIND_WINDOW, PoseWindow, PoseWindowBatch
+    pair = synth.make_pair(60, 80, 6, seed=9, init_sigma=0.01, overlap=1)
+    t = lambda a: T(np.ascontiguousarray(a))
+    kf = KeyFrame(t(pair.src_image), t(pair.K), t(pair.logdepth_perseg), t(pair.keypoints), t(pair.keypoint_regions))
+    frame = KeyFrame(t(pair.trg_image), t(pair.K))
+    eye = torch.eye(4, device=kf.image.device)
+    supp_T0 = torch.linalg.inv(t(pair.pose_init))
+
+    def build():
+        nodes = [dict(T=eye, kind=KIND_WINDOW), dict(T=supp_T0, kind=KIND_WINDOW, lr_pose=1.0, image=frame.image, K=frame.K)]
+        return PoseWindow([dict(kf=kf, kld=t(pair.kld_gt), lr=0.0, node=0)], nodes, [(0, 1, 1.0, dense_optim.Z_MIN_SINGLE)], (0, 1), max_iters=64)
+
+    def device_state(win):
+        return npy(win._gn_state()['state'])                 # (the device's copy itself, behind the accessors' back)
+
+    def check(win, what):
+        st = device_state(win)
+        want = dict(lam=float(st[0]), accepted=int(st[2]), rejected=int(st[3]), iterations=int(st[5]), converged=bool(st[6]),
+                    failed_solves=int(st[8]), too_many_unknowns=bool(st[9]))
+        assert win.gn_iterations() == want["iterations"] and win.gn_converged() == want["converged"], what
+        assert win.gn_stats() == want, (what, win.gn_stats(), want)
+        return want
+
+    def counted(win, run, what):
+        """``run()`` returns the iterations it took: the device's counter after minus before."""
+        before = int(device_state(win)[5])
+        n = run()
+        assert n == check(win, what)["iterations"] - before, what
+        return n
+
+    win = build()
+    win.gn_step(0, conv_tol=1e-4)                            # the first call of all: nothing has been looked at yet
+    assert check(win, "gn_step on a fresh window")["iterations"] == 1
+    counted(win, lambda: win.run_gn(0, 2, conv_tol=1e-4), "run_gn after gn_step")      # (ADVICE r04: the step above moved the counter)
+    seen = check(win, "run_gn, looked at twice")
+    win.gn_step(0, conv_tol=1e-4)                            # the pinned copy run_gn left is no longer current
+    assert check(win, "gn_step after run_gn")["iterations"] == seen["iterations"] + (0 if seen["converged"] else 1)
+    win.gn_step(0, conv_tol=1e-4)
+    assert counted(win, lambda: win.run_gn(0, 30, conv_tol=1e-4), "run_gn to convergence") < 30 and win.gn_converged()
+
+    two = [build(), build()]
+    batch = PoseWindowBatch(two)
+    two[1].gn_step(0, conv_tol=1e-4)                         # (one of the two with a step the host has not seen)
+    batch.run_gn(0, 2, conv_tol=1e-4)
+    assert all(check(w, "batch of two, two rounds")["iterations"] >= 2 for w in two)
+    batch.reset_gn()
+    batch.run_gn(0, 30, conv_tol=1e-4)
+    assert all(check(w, "batch of two to convergence")["converged"] for w in two)
+
+    trk = GnTracker(kf, t(pair.kld_gt), eye, frame, (0, 1))
+    chain = ChainStep(2, 60, 80, 1, kf.image.device)
+    chain.bind_tracker(trk, kf, False)
+    trk.win.gn_step(0, conv_tol=1e-4)                        # (a step the host has not seen, then the call resets and runs the schedule)
+    its, _, _ = chain.run(TRACK, i=1, image=frame.image, start_pose=supp_T0)
+    st = check(trk.win, "ChainStep.run(TRACK)")
+    assert its == st["iterations"] > 0
+    torch.cuda.synchronize()
+
+
 def test_gn_tracker_reuses_one_window_per_keyframe_with_identical_results():
     """GnTracker (one PoseWindow per keyframe; per frame only the target pyramid, two poses and the LM state change) returns
     bitwise what a freshly built window (track_frame_gn) returns, frame after frame, also after the keyframe was updated."""
@@ -409,7 +479,7 @@ def test_windows_side_by_side_are_bitwise_the_windows_one_at_a_time():
     batch.reset_gn()
     rounds = phases(batch.run_gn)
     torch.cuda.synchronize()
-    n_y = [w._gn['n_y'] for w in together]
+    n_y = [w.gn_unknowns for w in together]
     print(f"\n{len(shapes)} windows of {n_y} camera unknowns side by side: {rounds} rounds for the batch; alone {its} iterations")
     assert len(set(n_y)) >= 3 and max(n_y) > 64 > min(n_y)
     for a, b in zip(alone, together):

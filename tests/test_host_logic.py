@@ -520,3 +520,50 @@ def test_schedule_lays_out_three_attempts_and_picks_the_damping_from_the_segment
     assert (s4.entry, s4.retry_entry, s4.retry2_entry) == (n2, -1, 0) and s4.phase[n2 - 1].next == n2 + 4
     assert pb.VERDICT_DEFAULTS["seg_mean_ratio"] == 1.3 and pb.VERDICT_DEFAULTS["seg_max_ratio"] == 8.0 and pb.VERDICT_DEFAULTS["seg_product"] == 0.9
     assert pb.VERDICT_DEFAULTS["retry_on"] & _lib.SP_STATUS_SEGMENTS
+
+
+def test_gauss_newton_phase_lists_of_the_tracker_and_the_mapping_schedules():
+    """The two functions every user of a Gauss-Newton schedule takes its (level, max_iters, irls_eps, conv_tol) phases from
+    (``track_frame_gn``, ``GnTracker``, ``GnSuppMapper``, ``map_window``, the chain's bindings)."""
+    from super_primitive_amd.odometery.loops import MAP_GN_SCHEDULE, TRACK_GN_SCHEDULE, map_gn_phases, map_window_gn_phases, track_gn_phases
+    main, polish = (0, 6, 1e-3, 2e-3), (0, 5, 1e-5, 1e-4)
+    assert track_gn_phases(TRACK_GN_SCHEDULE, (0, 3), 0) == [(1, 4, 1e-3, 2e-3), main, polish]
+    assert track_gn_phases(TRACK_GN_SCHEDULE, (0, 1), 0) == [main, polish]
+    assert track_gn_phases(dict(TRACK_GN_SCHEDULE, polish_max=0), (0, 3), 0) == [(1, 4, 1e-3, 2e-3), main]
+    m_polish = (0, 12, 1e-5, 1e-5)
+    want = {500: [(0, 25, 1e-3, 1e-3), m_polish], 13: [(0, 13, 1e-3, 1e-3), m_polish], 12: [(0, 12, 1e-3, 1e-3)], 10: [(0, 10, 1e-3, 1e-3)]}
+    for num_iters, phases in want.items():
+        assert map_gn_phases(MAP_GN_SCHEDULE, num_iters) == phases, num_iters
+        assert map_window_gn_phases(dict(gn=dict(MAP_GN_SCHEDULE), num_iters=num_iters)) == phases, num_iters
+    no_polish = dict(MAP_GN_SCHEDULE, polish_max=0)
+    assert map_gn_phases(no_polish, 500) == map_window_gn_phases(dict(gn=no_polish, num_iters=500)) == [(0, 25, 1e-3, 1e-3)]
+
+
+@pytest.mark.parametrize("E,B,sumN,maxN,y,kind", [(1, 1, 6, 6, 8, "ok"), (28, 5, 200, 40, 112, "ok"), (4, 2, 80, 40, 192, "ok"), (4, 2, 80, 40, 193, "ok"),
+                                                  (1, 1, 1, 1, 0, "ok"), (1, 1, 1, 1, 512, "ok"), (1, 1, 1, 1, 513, "bad"), (0, 1, 1, 1, 8, "bad"),
+                                                  (60000, 64, 100000, 4000, 512, "too large")])
+def test_window_gn_scratch_size_and_profile_offset_follow_the_closed_form(E, B, sumN, maxN, y, kind):
+    """The scratch of a Gauss-Newton window: edge records (46 + 10 max_N each), Ad and the node-coordinate systems (36 + 272 per edge), C / Dinv
+    / Bd (ldc + 2 per depth unknown), S / Rhs / cols (tri + 2 ldc per block), nc (n_blocks + 2), the 16 time stamps, the global-memory
+    triangle beyond 192 unknowns and n_blocks + 6 doubles of slack.  Callers allocate by these numbers."""
+    from super_primitive_amd import _lib
+    lib = _lib.load()
+    size, offset = lib.sp_window_gn_scratch_doubles(E, B, sumN, maxN, y), lib.sp_window_gn_profile_offset(E, B, sumN, maxN, y)
+    if kind == "bad":
+        assert (size, offset) == (0, -1)
+        return
+    if kind == "too large":                                                # (beyond 2^31 - 1 doubles)
+        assert size == 0
+        return
+    ldc, tri = (y + 1) & ~1, y * (y + 1) // 2
+    hg = tri if y > 192 else 0
+    assert size == E * (46 + 10 * maxN) + 308 * E + sumN * (ldc + 2) + B * (tri + 2 * ldc + 2) + hg + 24
+    assert offset == E * (46 + 10 * maxN) + 308 * E + sumN * (ldc + 2) + B * (tri + 2 * ldc) + B + 2
+    assert offset + 16 + hg <= size
+
+
+def test_window_gn_flag_bits_match_the_header():
+    from super_primitive_amd import _lib
+    header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
+    for macro, bit in (("SP_WGN_POSE_ONLY", 1), ("SP_WGN_PREDICTED_EXIT", 2), ("SP_WGN_DEPTHS_FIXED", 4)):
+        assert int(re.search(r"#define\s+" + macro + r"\s+(\d+)", header).group(1)) == getattr(_lib, macro) == bit, macro
