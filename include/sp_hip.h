@@ -1599,6 +1599,75 @@ int sp_cloud_register(const float* queries, const float* normals, long long Qa, 
                       int with_scale, double huber, double tol, long long min_pairs, int max_iters, SpCloudReg* state, double* history,
                       int32_t* index, double* work, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Map surfaces (sp_tsdf.hip): V depth images fused into one dense signed-distance volume, and its zero level set cut into an indexed
+ * triangle mesh.  Everything runs on the caller's stream without a synchronisation; argument checks come before any device work; no
+ * floating-point atomics anywhere: two runs give the same bits.
+ *
+ * sp_tsdf_integrate fuses V depth images into the volume, in place.
+ *     depth   : (V,H,W) float32;  images : (V,3,H,W) float32, or NULL together with colour
+ *     views   : V SpView records on the device, camera-to-world (the records of sp_render_views)
+ *     tsdf, weight : (nz,ny,nx) float32;  colour : (nz,ny,nx,3) float32 -- all three read and updated.  A fresh volume is all zeros;
+ *               clearing it is the caller's job, so a second call continues the first
+ *     voxel   : the voxel's side;  ox, oy, oz : the origin o;  trunc : the truncation distance;  z_min, depth_max : the depth range
+ * Node (ix,iy,iz) sits at its voxel's centre, per axis a
+ *     p_a = ((float64(i_a) + 0.5) * voxel) + o_a
+ * in float64 from the float32 inputs, every operation rounded on its own (no fma, no reciprocal), as everywhere in the map kernels.
+ * One thread owns one node and walks the views in order v = 0 .. V-1:
+ *     d = p - t,  p_c = R^T d  with the operation order of sp_render_views (the same device function);  z = p_c.z;  skip unless z > z_min
+ *     u = x fx / z + cx,  v = y fy / z + cy;  col = floor(u + 0.5),  row = floor(v + 0.5): pixel centres are at integers here (the
+ *     tables unproject (c - cx) / fx);  skip unless both are finite, 0 <= col < W and 0 <= row < H
+ *     D = depth[v,row,col];  skip unless D is finite and 0 < D <= depth_max
+ *     sdf = float64(D) - z;  skip if sdf < -trunc;  s = float32(min(1.0, sdf / trunc))
+ *     in float32, every operation rounded on its own:  Wn = weight + 1;  tsdf = (tsdf * weight + s) / Wn;  each colour channel likewise
+ *     from images[v,ch,row,col], a NaN colour taken as 0;  weight = Wn
+ * One call over views 0 .. V-1 therefore leaves the bits of two calls over 0 .. k-1 and k .. V-1.
+ * Null depth / views / tsdf / weight, images without colour or the reverse, V, H, W, nx, ny or nz < 1, voxel or trunc not finite or not
+ * > 0, z_min negative or NaN, depth_max not > 0 (+inf is allowed), a non-finite origin: SP_EINVAL.  V > 65535, V H W >= 2^31,
+ * nx ny nz > 2^30: SP_ELIMIT.  Invalid beats too large.
+ *
+ * sp_tsdf_mesh cuts the zero level set by marching tetrahedra on the Kuhn split of every cell.
+ *     tsdf, weight, colour (or NULL), nx, ny, nz, voxel, ox, oy, oz : the volume, as above
+ *     scratch : sp_tsdf_mesh_scratch_bytes(nx, ny, nz) bytes, aligned to 4, initialised by the call.  One int32 per node (the 7-bit mask of
+ *               its crossing edges and the number of crossing edges before it in its 256-node block), one per 256 nodes and one per 256
+ *               cells, each array rounded up to 64 bytes: at most 4 (nx ny nz) (1 + 2 / 256) + 256 bytes, below 4.1 GiB at the
+ *               limit -- the reason the size is a long long
+ *     vertices, vertex_colours : (max_vertices,3) float32;  faces : (max_faces,3) int32 -- CAPACITY buffers: rows at or beyond the
+ *               capacity are never written.  vertices is NULL iff max_vertices = 0, faces is NULL iff max_faces = 0, vertex_colours is
+ *               non-NULL iff colour is given and max_vertices > 0; everything NULL and 0 is the counting call
+ *     n_out   : two int64 on the device, always written: the true number of vertices and of faces; the caller compares them with its
+ *               capacities.  Should either exceed 2^31 - 1 (indices are int32), no row is written at all
+ * A node is VALID iff its weight is >= min_weight and its tsdf is finite, NEGATIVE iff its tsdf is < 0 (an exact 0 is positive).
+ * Corner c of a cell has offset bits x = 1, y = 2, z = 4.  Lattice edges run from a node to node + offset for the seven offsets with
+ * bits 1 .. 7; the edge id is node_linear * 7 + (bits - 1), node_linear = (iz ny + iy) nx + ix.  An edge CROSSES iff both ends are valid
+ * and exactly one is negative.
+ * Vertices: one per crossing edge, numbered in ascending edge id (a scan; no sort, no atomics).  With a the lower node and b the upper,
+ *     t = f_a / (f_a - f_b)  in float64 from the float32 values;  per axis  p_a + t * (p_b - p_a)  with the node positions above, rounded
+ *     to float32 once;  colours the same way from the two nodes' colours.
+ * Faces: each of the (nx-1)(ny-1)(nz-1) cells splits into six tetrahedra that share the diagonal 0-7, by corner
+ *     0: 0,1,3,7   1: 0,1,5,7   2: 0,2,3,7   3: 0,2,6,7   4: 0,4,5,7   5: 0,4,6,7
+ * whose edges are all lattice edges of the seven types, and neighbouring cells agree on their shared face diagonals: the mesh welds
+ * without a search.  A tetrahedron emits only if all four nodes are valid: one or three negative nodes give one triangle on the three
+ * edges at the lone node, two give a quad on the four crossing edges.  The crossing edges are written as a cycle q0, q1, .. that starts
+ * at the smallest edge id and is oriented so that, with every vertex at the MIDPOINT of its edge (exact half-lattice integers),
+ * (v1 - v0) x (v2 - v0) has a positive dot product with (centroid of the positive nodes - centroid of the negative nodes): faces look
+ * into free space, towards the cameras.  The triangles are (q0,q1,q2) and, for a quad, (q0,q2,q3).  That orientation depends only on
+ * (tetrahedron, sign case): a table of 6 x 16 entries, built from this rule at compile time.
+ * Faces are ordered by ascending cell linear index ((iz (ny-1) + iy)(nx-1) + ix), then tetrahedron 0 .. 5, then triangle (a scan).
+ * A vertex that falls on a node (t = 0 or 1) is kept, so degenerate triangles may occur.
+ * Null tsdf / weight / scratch / n_out, a scratch not aligned to 4 bytes, nx, ny or nz < 2, a negative capacity, a buffer that is NULL
+ * with a capacity > 0 or the reverse, voxel not finite or not > 0, a non-finite origin, a NaN min_weight: SP_EINVAL.  nx ny nz > 2^30 or
+ * a capacity > 2^31 - 1: SP_ELIMIT.  Invalid beats too large.  sp_tsdf_mesh_scratch_bytes answers sizes < 2 and nx ny nz > 2^30 with the
+ * same codes.  Three launches count (nodes, cells, one scan of both block arrays), two more write. */
+#define SP_TSDF_MAX_NODES (1LL << 30)
+int sp_tsdf_integrate(const float* depth, const float* images, const SpView* views, int V, int H, int W, int nx, int ny, int nz, float voxel,
+                      float ox, float oy, float oz, float trunc, float z_min, float depth_max, float* tsdf, float* weight, float* colour,
+                      void* stream);
+long long int sp_tsdf_mesh_scratch_bytes(int nx, int ny, int nz);
+int sp_tsdf_mesh(const float* tsdf, const float* weight, const float* colour, int nx, int ny, int nz, float voxel, float ox, float oy, float oz,
+                 float min_weight, void* scratch, long long max_vertices, long long max_faces, float* vertices, float* vertex_colours,
+                 int32_t* faces, long long* n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

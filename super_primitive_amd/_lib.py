@@ -17,7 +17,7 @@ P = c_void_p
 I = c_int
 F = c_float
 
-# name -> argtypes (restype is always int); mirrors include/sp_hip.h one to one
+# name -> argtypes (restype is int unless RESTYPES says otherwise); mirrors include/sp_hip.h one to one
 SIGNATURES = {
     "sp_abi_version": [],
     "sp_mask_count": [P, I, I, I, P, P, P, P],
@@ -111,7 +111,13 @@ SIGNATURES = {
     "sp_cloud_normals": [P, ctypes.c_longlong, P, P, ctypes.c_longlong, I, P, I, P, P, P, P, P],
     "sp_cloud_register_work_doubles": [ctypes.c_longlong],
     "sp_cloud_register": [P, P, ctypes.c_longlong, ctypes.c_longlong, P, I, I, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, I, P, P, P, P, P],
+    "sp_tsdf_integrate": [P, P, P, I, I, I, I, I, I, F, F, F, F, F, F, F, P, P, P, P],
+    "sp_tsdf_mesh_scratch_bytes": [I, I, I],
+    "sp_tsdf_mesh": [P, P, P, I, I, I, F, F, F, F, F, P, ctypes.c_longlong, ctypes.c_longlong, P, P, P, P, P],
 }
+
+# the entry points that do not return an int
+RESTYPES = {"sp_tsdf_mesh_scratch_bytes": ctypes.c_longlong}
 
 SP_ABI_VERSION = 20
 SP_GRAD_PARTIAL_FLOATS = 16
@@ -287,6 +293,7 @@ SP_VIEW_FLOATS = 25
 SP_MAP_FUSE_MAX_POINTS = 1 << 28
 SP_CLOUD_GRID_MAX_POINTS = 1 << 28
 SP_CLOUD_KNN_MAX = 32
+SP_TSDF_MAX_NODES = 1 << 30
 SP_CLOUD_REG_RUNNING, SP_CLOUD_REG_CONVERGED, SP_CLOUD_REG_MAX_ITERS, SP_CLOUD_REG_FEW, SP_CLOUD_REG_DEGENERATE = range(5)
 SP_CLOUD_REG_ITERS_LIMIT = 4096
 SP_CLOUD_REG_WORK_DOUBLES = 40
@@ -341,7 +348,7 @@ def load():
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here = header / library mismatch: fail loudly
         fn.argtypes = args
-        fn.restype = c_int
+        fn.restype = RESTYPES.get(name, c_int)
     if lib.sp_abi_version() != SP_ABI_VERSION:
         raise RuntimeError("libsp_hip.so ABI version mismatch; rebuild")
     _lib = lib

@@ -1,4 +1,4 @@
-// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip, sp_register.hip): each idiom has its one definition here.
+// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip, sp_register.hip, sp_tsdf.hip): each idiom has its one definition here.
 #pragma once
 #include "sp_device.h"
 
@@ -36,6 +36,24 @@ __device__ __forceinline__ BlockRank block_rank(bool keep, int* wc) {
     if (lane == 0) wc[wave] = __popcll(ballot);
     __syncthreads();
     BlockRank r = {(int)__popcll(ballot & ((1ull << lane) - 1ull)), (wc[0] + wc[1]) + (wc[2] + wc[3])};
+    for (int w = 0; w < wave; ++w) r.rank += wc[w];
+    return r;
+}
+
+// block_rank for lanes that keep `count` >= 0 rows each (sp_tsdf.hip: the crossing edges of a node, the faces of a cell): rank = the rows
+// kept before this lane in its workgroup (a wave's inclusive scan by lane swaps, then the waves before it), count = all of the
+// workgroup's.  The same conditions: every thread calls it, once per kernel; wc: SP_WAVES ints of LDS
+__device__ __forceinline__ BlockRank block_prefix(int count, int* wc) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = count;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) wc[wave] = incl;
+    __syncthreads();
+    BlockRank r = {incl - count, (wc[0] + wc[1]) + (wc[2] + wc[3])};
     for (int w = 0; w < wave; ++w) r.rank += wc[w];
     return r;
 }

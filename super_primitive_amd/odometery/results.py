@@ -29,7 +29,10 @@
                       ``write_ply`` exports ``nx ny nz``; ``statistical_outliers`` is the mean distance to the k nearest against the
                       cloud's mean and deviation, ``select_map`` the map reduced to the rows a mask keeps.
 ``write_tum_format``  the two trajectory files of the reference's ``convert_traj_to_tum.py``.
-``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file."""
+``fuse_tsdf``         depth images fused into one dense signed-distance volume (``tsdf_volume``; ONE ``sp_tsdf_integrate`` launch):
+                      the average of what every view saw; ``sequence_tsdf`` fuses a sequence's own keyframes, ``extract_mesh`` cuts the
+                      zero level set into an indexed triangle mesh (``sp_tsdf_mesh``) whose vertices are a cloud every function above takes.
+``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file; a mesh's faces too."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -269,11 +272,23 @@ def sequence_consistency(world, result, tol=0.05, window=1):
     scale when ``world`` carries ``align``: the world points are scaled, the tables are not), through the archive poses in the map's
     frame (``point_radii``'s).  Returns ``map_consistency``'s dict plus ``depths`` (n,H,W) float32 and ``seg_maps`` (n,H,W) int32.
     No synchronisation beyond the keyframes' table builds."""
+    views = _sequence_views(world, result, "sequence_consistency")
+    out = map_consistency(world, views['depths'], views['Ks'], views['poses'], view_kf=torch.arange(len(world['ids']), dtype=torch.int32),
+                          tol=tol, window=window)
+    out.update(depths=views['depths'], seg_maps=views['seg_maps'])
+    return out
+
+
+def _sequence_views(world, result, what):
+    """What the keyframes of ``world`` (``sequence_map`` of ``result``) claim to see, in the map's frame: ``dict(depths (n,H,W) float32 --
+    ``tool.viz.keyframe_depths`` on the archive, in ``world['ids']`` order, multiplied by the alignment scale when ``world`` carries
+    ``align`` --, seg_maps (n,H,W) int32, Ks (n,3,3), poses (n,4,4) float64 -- ``_map_poses``)``: the views ``sequence_consistency`` tests the
+    map against and ``sequence_tsdf`` fuses."""
     from ..tool import viz
     archive = result['kf_archive']
     ids = world['ids']
     if any(archive[i]['kf'] is None for i in ids):
-        raise ValueError("sequence_consistency: the result holds no keyframes (run with keep_keyframes=True)")
+        raise ValueError(f"{what}: the result holds no keyframes (run with keep_keyframes=True)")
     _lib.require_device(world['points'], world['kf_index'])
     own = viz.keyframe_depths([archive[i]['kf'] for i in ids], [archive[i]['kld'] for i in ids])
     depths = own['depth']
@@ -282,10 +297,7 @@ def sequence_consistency(world, result, tol=0.05, window=1):
         depths = depths * a['s'][0].to(torch.float32)
     dev = depths.device
     Ks = torch.stack([archive[i]['kf'].K.detach().reshape(3, 3).to(dev) for i in ids])
-    out = map_consistency(world, depths, Ks, _map_poses(world, result), view_kf=torch.arange(len(ids), dtype=torch.int32), tol=tol,
-                          window=window)
-    out.update(depths=depths, seg_maps=own['seg'])
-    return out
+    return dict(depths=depths, seg_maps=own['seg'], Ks=Ks, poses=_map_poses(world, result))
 
 
 def segment_consistency(world, consistency, n_segments=None):
@@ -659,12 +671,142 @@ def statistical_outliers(world, radius, k=16, std_ratio=2.0, knn=None):
     return dict(mean_dist=mean_dist, keep=mean_dist <= threshold, mu=mu, sigma=sigma, threshold=threshold, knn=knn)
 
 
+def _three(x, what):
+    """Three finite numbers as Python floats (a list, an array or a tensor: a device tensor costs one host read)."""
+    try:
+        v = [float(a) for a in torch.as_tensor(x, dtype=torch.float64).detach().reshape(-1).tolist()]
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"{what} {x!r}: {e}") from None
+    if len(v) != 3 or not all(abs(a) < float("inf") for a in v):
+        raise ValueError(f"{what} {x!r} (three finite numbers)")
+    return v
+
+
+def _voxel_trunc(voxel, trunc, what):
+    """``voxel`` and ``trunc`` (default 4 voxels) as finite floats > 0."""
+    try:
+        voxel = float(voxel)
+        trunc = 4.0 * voxel if trunc is None else float(trunc)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: voxel {voxel!r}, trunc {trunc!r}: {e}") from None
+    if not (0.0 < voxel < float("inf")) or not (0.0 < trunc < float("inf")):
+        raise ValueError(f"{what}: voxel {voxel}, trunc {trunc} (finite, > 0)")
+    return voxel, trunc
+
+
+def tsdf_volume(lo, hi, voxel, trunc=None, colour=True, device="cuda"):
+    """An empty signed-distance volume over the box ``lo`` .. ``hi`` (three numbers each): ``ceil((hi - lo) / voxel)`` nodes per axis, at
+    least one, node (ix,iy,iz) at ``lo + (i + 0.5) voxel``.  ``trunc``: the truncation distance (default ``4 * voxel``).  Returns
+    ``dict(tsdf, weight (nz,ny,nx) float32 zeros, colour (nz,ny,nx,3) float32 zeros or None, origin (three floats), voxel, trunc, dims
+    (nx, ny, nz))`` -- what ``fuse_tsdf`` / ``viz.tsdf_integrate`` update in place and ``extract_mesh`` cuts.  Raises ``ValueError`` for a
+    box of more than 2^30 nodes, before anything is allocated."""
+    voxel, trunc = _voxel_trunc(voxel, trunc, "tsdf_volume")
+    lo, hi = _three(lo, "tsdf_volume: lo"), _three(hi, "tsdf_volume: hi")
+    if any(h < l for l, h in zip(lo, hi)):
+        raise ValueError(f"tsdf_volume: box {lo} .. {hi}")
+    dims = tuple(max(1, int(np.ceil((h - l) / voxel))) for l, h in zip(lo, hi))
+    if dims[0] * dims[1] * dims[2] > _lib.SP_TSDF_MAX_NODES:
+        raise ValueError(f"tsdf_volume: {dims[0]}x{dims[1]}x{dims[2]} nodes are beyond the kernels' limit of 2^30; use a larger voxel or a smaller box")
+    nx, ny, nz = dims
+    return dict(tsdf=torch.zeros(nz, ny, nx, dtype=torch.float32, device=device), weight=torch.zeros(nz, ny, nx, dtype=torch.float32, device=device),
+                colour=torch.zeros(nz, ny, nx, 3, dtype=torch.float32, device=device) if colour else None, origin=tuple(lo), voxel=voxel, trunc=trunc,
+                dims=dims)
+
+
+def _finite_extent(points, valid=None):
+    """(lo, hi) of the rows of ``points`` (Q,3) whose coordinates are all finite (and ``valid``): two device reductions, ONE host read."""
+    ok = torch.isfinite(points).all(dim=1)
+    if valid is not None:
+        ok = ok & valid
+    inf = torch.full_like(points, float("inf"))
+    lo = torch.where(ok[:, None], points, inf).amin(dim=0)
+    hi = torch.where(ok[:, None], points, -inf).amax(dim=0)
+    both = torch.stack((lo, hi)).double().tolist()                                     # the one host read
+    if not all(abs(a) < float("inf") for row in both for a in row):
+        raise ValueError("no finite point to take the bounds from")
+    return both[0], both[1]
+
+
+def fuse_tsdf(depths, Ks, poses, voxel, bounds=None, images=None, volume=None, trunc=None, z_min=None, depth_max=float("inf")):
+    """Depth images fused into a signed-distance volume (``viz.tsdf_integrate``: ONE ``sp_tsdf_integrate`` launch; include/sp_hip.h has
+    the rule): ``depths`` (V,H,W) float32 -- the keyframes' own (``sequence_tsdf``) or ground truth, for a ground-truth surface --, ``Ks``
+    (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world, ``images`` (V,3,H,W) float32 or None.  ``volume``: an existing volume to continue
+    (``voxel``, ``bounds`` and ``trunc`` are then ignored); else a new one over ``bounds`` = (lo, hi), or -- ``bounds=None`` -- over the
+    finite extent of the lifted depths (``viz.lift_depth_images``; one host read) padded by ``trunc`` (default ``4 * voxel``), with a
+    colour iff there are images.  Returns the volume."""
+    from ..tool import viz
+    Ks, poses = _view_cameras(Ks, poses, "fuse_tsdf")
+    z_min = viz.Z_MIN if z_min is None else z_min
+    try:
+        depth_max = float(depth_max)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"fuse_tsdf: depth_max {depth_max!r}: {e}") from None
+    if not depth_max > 0.0:
+        raise ValueError(f"fuse_tsdf: depth_max {depth_max} (> 0; inf allowed)")
+    if volume is None:
+        voxel, trunc = _voxel_trunc(voxel, trunc, "fuse_tsdf")
+        if not torch.is_tensor(depths) or depths.dim() != 3 or depths.dtype != torch.float32 or depths.shape[0] != poses.shape[0]:
+            raise ValueError(f"fuse_tsdf: depths must be float32 (V,H,W) for {poses.shape[0]} views, got "
+                             f"{tuple(depths.shape) if torch.is_tensor(depths) else type(depths).__name__}")
+        if bounds is None:
+            cap = min(depth_max, 3.0e38)
+            lifted = viz.lift_depth_images(depths, Ks, poses.float(), depth_trunc=cap)
+            rows = torch.arange(lifted['points'].shape[0], device=lifted['points'].device)
+            try:
+                lo, hi = _finite_extent(lifted['points'], rows < lifted['offsets'][-1])
+            except ValueError as e:
+                raise ValueError(f"fuse_tsdf: {e}") from None
+            lo, hi = [a - trunc for a in lo], [a + trunc for a in hi]
+        else:
+            try:
+                lo, hi = bounds
+            except (TypeError, ValueError):
+                raise ValueError(f"fuse_tsdf: bounds {bounds!r} (a pair (lo, hi))") from None
+        volume = tsdf_volume(lo, hi, voxel, trunc, colour=images is not None, device=depths.device)
+    return viz.tsdf_integrate(volume, depths, Ks, poses, images=images, z_min=z_min, depth_max=depth_max)
+
+
+def sequence_tsdf(world, result, voxel, trunc=None, depth_max=float("inf")):
+    """The surface a sequence saw: the keyframes' own depth images (``sequence_consistency``'s: ``viz.keyframe_depths`` on the archive,
+    times the alignment scale when ``world`` carries ``align``), their Ks and their poses in the map's frame, fused into ONE volume over
+    the finite extent of ``world['points']`` padded by ``trunc`` (default ``4 * voxel``; one host read), coloured from the keyframes'
+    images.  ``world`` is ``sequence_map`` of ``result`` (``run_sequence(..., keep_keyframes=True)``).  Returns the volume plus ``depths``
+    (n,H,W): pass it to ``extract_mesh``."""
+    voxel, trunc = _voxel_trunc(voxel, trunc, "sequence_tsdf")
+    views = _sequence_views(world, result, "sequence_tsdf")
+    archive = result['kf_archive']
+    images = torch.stack([archive[i]['kf'].image[:3].detach().float() for i in world['ids']]).contiguous()
+    try:
+        lo, hi = _finite_extent(world['points'])
+    except ValueError as e:
+        raise ValueError(f"sequence_tsdf: {e}") from None
+    volume = fuse_tsdf(views['depths'], views['Ks'], views['poses'], voxel, bounds=([a - trunc for a in lo], [a + trunc for a in hi]), images=images,
+                       trunc=trunc, depth_max=depth_max)
+    volume['depths'] = views['depths']
+    return volume
+
+
+def extract_mesh(volume, min_weight=1.0):
+    """The zero level set of a volume as a triangle mesh (``viz.tsdf_mesh``: ``sp_tsdf_mesh``, marching tetrahedra; one host read of the
+    two counts).  Returns ``dict(points (M,3), colours (M,3) float32 -- zeros for a volume without colour --, faces (F,3) int32 into
+    ``points``, looking into free space, and kf_index, seg_ids (M,) int32 = -1, offsets = [0, M])``: the vertices are a cloud, so
+    ``map_distance``, ``register_map``, ``estimate_normals``, ``render_map`` and ``write_ply`` accept the dict as it is."""
+    from ..tool import viz
+    found = viz.tsdf_mesh(volume, min_weight=min_weight)
+    points = found['vertices']
+    M, dev = int(points.shape[0]), points.device
+    colours = found['colours'] if found['colours'] is not None else torch.zeros(M, 3, dtype=torch.float32, device=dev)
+    none = torch.full((M,), -1, dtype=torch.int32, device=dev)
+    return dict(points=points, colours=colours, faces=found['faces'], kf_index=none, seg_ids=none.clone(), offsets=np.array([0, M], dtype=np.int64))
+
+
 def write_ply(path, world):
     """``world['points']`` (M,3) float32 and ``world['colours']`` (M,3) float32 in 0..1 as a binary little-endian PLY file: per vertex
     ``x y z`` float32 and ``red green blue`` uchar, the colours by the renderer's 8-bit rule (trunc(c * 255) from the float64 product,
     clamped to 0 .. 255, NaN gives 0).  With ``world['normals']`` (M,3) float32 the vertex is ``x y z nx ny nz`` float32 and ``red green
     blue`` uchar; without, the file is what it always was.  Device tensors come to the host in one copy of 15 (27) bytes per point; CPU
-    tensors work too.  Returns the path."""
+    tensors work too.  With ``world['faces']`` (F,3) int32 -- ``extract_mesh``'s dict -- the file also has ``element face F`` with ``property list
+    uchar int vertex_indices``, 13 bytes per face after the vertices.  Returns the path."""
     points, colours = world.get('points'), world.get('colours')
     if not torch.is_tensor(points) or not torch.is_tensor(colours) or points.dtype != torch.float32 or colours.dtype != torch.float32 \
             or points.dim() != 2 or points.shape[1] != 3 or tuple(colours.shape) != tuple(points.shape) or points.device != colours.device:
@@ -674,17 +816,25 @@ def write_ply(path, world):
     if normals is not None and (not torch.is_tensor(normals) or normals.dtype != torch.float32 or tuple(normals.shape) != (M, 3)
                                 or normals.device != points.device):
         raise ValueError("write_ply: world['normals'] must be float32 (M,3) on the points' device")
+    faces = world.get('faces')
+    if faces is not None and (not torch.is_tensor(faces) or faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3):
+        raise ValueError("write_ply: world['faces'] must be int32 (F,3)")
     rgb = torch.nan_to_num(colours.detach().double() * 255.0, nan=0.0).clamp(0.0, 255.0).to(torch.uint8)
     floats = [points] if normals is None else [points, normals]
     rows = torch.cat([t.detach().contiguous().view(torch.uint8).reshape(M, 12) for t in floats] + [rgb], dim=1).cpu().numpy()   # the one copy
     header = ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {M}\n" + "property float x\nproperty float y\nproperty float z\n"
               + ("" if normals is None else "property float nx\nproperty float ny\nproperty float nz\n") +
-              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n" +
+              ("" if faces is None else f"element face {int(faces.shape[0])}\nproperty list uchar int vertex_indices\n") + "end_header\n")
     if np.little_endian is False:                                                      # (the float bytes above are the host's)
         raise ValueError("write_ply: a big-endian host")
     with open(path, 'wb') as f:
         f.write(header.encode('ascii'))
         f.write(rows.tobytes())
+        if faces is not None:                                                          # per face: the count 3 as uchar, three int32
+            lists = np.empty(int(faces.shape[0]), dtype=np.dtype([('n', 'u1'), ('v', '<i4', (3,))]))
+            lists['n'], lists['v'] = 3, faces.detach().cpu().numpy()
+            f.write(lists.tobytes())
     return path
 
 

@@ -18,6 +18,8 @@ matplotlib is imported):
 ``nearest_points``     per query point the nearest point of such a cloud, its distance and the count within the radius (``sp_cloud_grid_nearest``).
 ``nearest_k``          per query point its k nearest points of such a cloud within the radius, sorted (``sp_cloud_grid_knn``).
 ``cloud_normals``      a normal and a surface variation per point of a cloud that has none, from its k nearest points (``sp_cloud_normals``).
+``tsdf_integrate``     depth images fused into a dense signed-distance volume, in place (``sp_tsdf_integrate``).
+``tsdf_mesh``          the volume's zero level set as an indexed triangle mesh: a counting call, one host read, a filling call (``sp_tsdf_mesh``).
 ``register_clouds``    the similarity that moves a query cloud onto such a cloud, by Gauss-Newton ICP on the device (``sp_cloud_register``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
@@ -608,3 +610,97 @@ def register_clouds(queries, grid, normals=None, residual='point', T0=None, s0=1
     words = state.view(torch.int32)
     return dict(rot=rot, trans=trans, s=s, T=T, status=words[2 * 58], iterations=words[2 * 58 + 1], n=state.view(torch.int64)[57], cost=state[55],
                 history=history, index=index)
+
+
+def _volume(volume, what):
+    """What ``odometery.results.tsdf_volume`` returned, checked: (tsdf, weight, colour or None, (nx, ny, nz), voxel, origin, trunc) with the
+    three numbers as the float32 the kernel reads.  The state tensors are updated in place, so they must be contiguous as they are."""
+    if not isinstance(volume, dict) or any(k not in volume for k in ('tsdf', 'weight', 'colour', 'origin', 'voxel', 'trunc', 'dims')):
+        raise ValueError(f"{what}: volume must be what tsdf_volume returned")
+    tsdf, weight, colour = volume['tsdf'], volume['weight'], volume['colour']
+    try:
+        nx, ny, nz = (int(n) for n in volume['dims'])
+        vox, trunc = (float(torch.tensor(float(volume[k]), dtype=torch.float32)) for k in ('voxel', 'trunc'))
+        org = [float(o) for o in torch.as_tensor(volume['origin'], dtype=torch.float64).reshape(-1).float().tolist()]
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"{what}: volume dims {volume['dims']!r}, voxel {volume['voxel']!r}, trunc {volume['trunc']!r}, origin {volume['origin']!r}: {e}") from None
+    if min(nx, ny, nz) < 1 or nx * ny * nz > _lib.SP_TSDF_MAX_NODES:
+        raise ValueError(f"{what}: a volume of {nx}x{ny}x{nz} nodes (1 .. 2^30 in all)")
+    if not (0.0 < vox < float("inf")) or not (0.0 < trunc < float("inf")):
+        raise ValueError(f"{what}: voxel {volume['voxel']}, trunc {volume['trunc']} (finite float32 > 0)")
+    if len(org) != 3 or not all(abs(o) < float("inf") for o in org):
+        raise ValueError(f"{what}: origin {volume['origin']} (three finite float32 numbers)")
+    for name, t, shape in (('tsdf', tsdf, (nz, ny, nx)), ('weight', weight, (nz, ny, nx)), ('colour', colour, (nz, ny, nx, 3))):
+        if t is None and name == 'colour':
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{what}: volume['{name}'] must be a contiguous float32 tensor {shape}")
+    return tsdf, weight, colour, (nx, ny, nz), vox, org, trunc
+
+
+def tsdf_integrate(volume, depths, Ks, poses, images=None, z_min=Z_MIN, depth_max=float("inf")):
+    """ONE ``sp_tsdf_integrate`` launch (include/sp_hip.h has the rule): ``depths`` (V,H,W) float32 fused into ``volume`` (what
+    ``odometery.results.tsdf_volume`` returned) IN PLACE, view after view; ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world in the
+    volume's frame, ``images`` (V,3,H,W) float32 or None -- without them the volume's colour, if it has one, is left untouched.  A depth
+    counts iff it is finite and 0 < d <= ``depth_max``; a node is tested against a view iff its z there is > ``z_min``.  Returns
+    ``volume``.  No synchronisation."""
+    tsdf, weight, colour, (nx, ny, nz), vox, org, trunc = _volume(volume, "tsdf_integrate")
+    _on_device(tsdf, weight, colour, depths, Ks, poses, images)
+    if poses.dim() != 3:
+        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
+    V = int(poses.shape[0])
+    if V == 0:
+        raise ValueError("tsdf_integrate: poses of no views")
+    d = _f32(depths, (V, None, None), "depths")
+    H, W = _size(d.shape[1], d.shape[2])
+    views = _views(Ks, poses, V)
+    img = None
+    if images is not None:
+        if colour is None:
+            raise ValueError("tsdf_integrate: images for a volume without colour")
+        img = _f32(images, (V, 3, H, W), "images")
+    _z_min(z_min)
+    if not float(depth_max) > 0.0:
+        raise ValueError(f"tsdf_integrate: depth_max {depth_max} (> 0; inf allowed)")
+    _limits("tsdf_integrate", V, H, W)
+    lib = _lib.load()
+    _lib.check(lib.sp_tsdf_integrate(_lib.ptr(d), _lib.ptr(img), _lib.ptr(views), V, H, W, nx, ny, nz, vox, org[0], org[1], org[2], trunc,
+                                     float(z_min), float(depth_max), _lib.ptr(tsdf), _lib.ptr(weight), _lib.ptr(colour if img is not None else None),
+                                     _lib.stream_ptr()), "sp_tsdf_integrate")
+    return volume
+
+
+def tsdf_mesh(volume, min_weight=1.0):
+    """The zero level set of ``volume`` as an indexed triangle mesh (``sp_tsdf_mesh``; include/sp_hip.h has the rule): a counting call,
+    ONE host read of the two counts (the one synchronisation), buffers of exactly that size, and a second call that fills them.  A node
+    counts iff its weight is >= ``min_weight`` and its tsdf is finite.  Returns ``dict(vertices (n,3) float32, colours (n,3) float32 or
+    None -- for a volume without colour --, faces (F,3) int32)``; faces look into free space."""
+    tsdf, weight, colour, (nx, ny, nz), vox, org, _ = _volume(volume, "tsdf_mesh")
+    _on_device(tsdf, weight, colour)
+    try:
+        min_weight = float(min_weight)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"tsdf_mesh: min_weight {min_weight!r}: {e}") from None
+    if min_weight != min_weight:
+        raise ValueError("tsdf_mesh: min_weight is NaN")
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"tsdf_mesh: a volume of {nx}x{ny}x{nz} nodes has no cell (every size must be >= 2)")
+    lib = _lib.load()
+    dev = tsdf.device
+    scratch = torch.empty(lib.sp_tsdf_mesh_scratch_bytes(nx, ny, nz) // 4, dtype=torch.int32, device=dev)
+    n_out = torch.empty(2, dtype=torch.int64, device=dev)
+
+    def call(nv, nf, vertices, colours, faces):
+        _lib.check(lib.sp_tsdf_mesh(_lib.ptr(tsdf), _lib.ptr(weight), _lib.ptr(colour), nx, ny, nz, vox, org[0], org[1], org[2], min_weight,
+                                    _lib.ptr(scratch), nv, nf, _lib.ptr(vertices), _lib.ptr(colours), _lib.ptr(faces), _lib.ptr(n_out),
+                                    _lib.stream_ptr()), "sp_tsdf_mesh")
+    call(0, 0, None, None, None)
+    nv, nf = (int(n) for n in n_out.tolist())                                    # the one host read
+    if nv > 2 ** 31 - 1 or nf > 2 ** 31 - 1:
+        raise ValueError(f"tsdf_mesh: {nv} vertices and {nf} faces are beyond 32-bit indices")
+    out = dict(vertices=torch.empty(nv, 3, dtype=torch.float32, device=dev),
+               colours=None if colour is None else torch.empty(nv, 3, dtype=torch.float32, device=dev),
+               faces=torch.empty(nf, 3, dtype=torch.int32, device=dev))
+    if nv > 0:
+        call(nv, nf, out['vertices'], out['colours'], out['faces'] if nf > 0 else None)
+    return out
