@@ -510,7 +510,21 @@ typedef struct SpSchedule {
  * and, when (status & retry_mask) and the schedule has a retry_entry and the pair has made one attempt, puts pose and log-depths
  * back to pose0 / kld0, resets its LM state (lambda = lam0) and restarts it at retry_entry IN THE SAME LAUNCH -- the pair keeps its
  * slot, the resident set stays full.  A pair's verdict depends on the pair alone (no batch statistics): bitwise what it is alone.
- * pose0 / kld0: the initial values, laid out like the batch's own pose / kld arrays (pose_base / kld_base: element 0 of those). */
+ * pose0 / kld0: the initial values, laid out like the batch's own pose / kld arrays (pose_base / kld_base: element 0 of those).
+ * THE SMALL PRINT (pinned by tests/test_gpu_schedule_verdict.py against tests/schedule_verdict_ref.py):
+ *   - every test is a strict comparison in float32: a quantity EQUAL to its bound is not flagged; a bound <= 0 switches its test off;
+ *   - finiteness is tested of pose entries 0..11 (the last row is constant and not looked at), of the pair's N log-depths and of the
+ *     final cost; a magnitude above 3e38 counts as non-finite; diag[1] is the maximum over the finite differences only;
+ *   - diag[5] is the first evaluated cost of the attempt that is not exactly 0 (a first cost of 0 leaves it for the next evaluation);
+ *     cost_ratio is tested only against a first cost > 0;
+ *   - a segment's mean |r| is float32(a / (3 c)), a / c = the float64 sums of columns [8] / [9] over its records; the median is the LOWER
+ *     median, rank (n_judged - 1) >> 1 of the judged costs ordered by (value, segment index); diag[7] is the maximum over every judged
+ *     segment, also when fewer than SP_VERDICT_MIN_SEGMENTS are judged -- there is then no median (diag[6] = 0) and no segment test;
+ *   - a restart sets lm_state[0, 1, 4, 7] = {lam0, -1, 0, 0}, iters = 0, diag[5] = 0, attempts[pair] = the attempt's number and zeroes the
+ *     slot's Adam moments; lm_state[2, 3] (the iteration counts) run on over all attempts, lm_state[5, 6] keep the last evaluated cost and
+ *     valid fraction until the next evaluation; status, the rest of diag, backup and costs are left alone; pose (all 16 entries) and the
+ *     pair's N log-depths are bitwise pose0 / kld0;
+ *   - with attempts == NULL a pair counts as having made its last attempt: nothing is retried, diag[4] = 1, no SP_STATUS_RETRIED. */
 #define SP_STATUS_NONFINITE   1   /* a non-finite pose entry, log-depth or cost */
 #define SP_STATUS_LAST_CAP    2   /* the last phase ended on its iteration cap, not by its convergence test */
 #define SP_STATUS_DEPTH_RANGE 4   /* some |kld - kld0| > kld_bound: a segment's depth ran away */

@@ -1,7 +1,8 @@
 """-m gpu: ONE call of the per-pair Gauss-Newton / LM solver (solve_gn / solve_adam_sched in csrc/sp_solve_device.h, through
 sp_pairs_gn_step, sp_pairs_gn_step_conv and sp_pairs_schedule_gn_step) against the float64 dense solve of tests/gn_step_ref.py.
 
-The solver reads only the partial records and a few SpPair fields, so the records are hand-made (no image, no table).  Every case
+The solver reads only the partial records and a few SpPair fields, so the records are hand-made (no image, no table).  The rig (Rig,
+make_pair, neighbours, swap_cost) lives in tests/gn_step_rig.py, shared with test_gpu_schedule_verdict.py.  Every case
 launches THREE pairs; the middle one is the pair under test, so its tile0, rec0, backup / lm_state / adam_state strides are non-zero and
 max_N > N; the neighbours are compared with the reference as well (a write into a neighbour is a mismatch), and so is every buffer a
 call may write: kld (with the unused tail of each pair's slot), pose, lm_state[0..7], backup, costs, done or phase / iters, the Adam
@@ -29,197 +30,15 @@ Case -> branch
   test_predicted_exit            SP_PHASE_PREDICTED_EXIT (the gain, also in the recompute path), not at lambda = 0.1, not with depth damping
   test_adam_phase                SP_PHASE_ADAM (solve_adam_sched), its cap
 """
-import ctypes
-
 import numpy as np
 import pytest
-import torch
 
 import gn_step_ref as ref
-from gn_step_ref import GnArgs, f32
-from gpu_util import T, npy
+from gn_step_ref import f32
+from gn_step_rig import SENTINEL, Rig, make_pair, neighbours, swap_cost
+from gpu_util import npy
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 1.0e6          # records in front of and behind the pairs' own: reading one moves every sum far
-SENTINEL = -5.0
-
-
-def make_pair(rng, N, rps, n_spans, exact=True, lam0=2.0, phase=0, residual_scale=0.25):
-    rec = ref.make_records(rng, N, rps, n_spans, exact=exact, residual_scale=residual_scale)
-    return dict(rec=rec, pose=ref.random_pose(rng), kld=(1.0 + 0.5 * rng.random(N)).astype(f32), lam0=lam0, phase=phase)
-
-
-def neighbours(rng, exact=True):
-    return (make_pair(rng, 5, [1, 0, 3, 2, 9], 3, exact=exact, lam0=0.5), make_pair(rng, 9, 2, 70, exact=exact, lam0=8.0))
-
-
-class Rig:
-    """Three pairs on the device and their reference states.  entry: 'gn' | 'conv' | 'sched'; phases: list of dict(max_iters, conv_tol,
-    flags, next) for 'sched'.  The layout (N, record counts) of every pair is fixed; ``load`` swaps the record CONTENTS."""
-
-    def __init__(self, pairs, entry="gn", conv_tol=0.0, phases=None, lm=(8.0, 0.5, 1e-7), adam_lr=(1e-2, 1e-3)):
-        from super_primitive_amd import _lib
-        self._lib, self.lib = _lib, _lib.load()
-        self.entry, self.conv_tol, self.phases, self.lm, self.adam_lr = entry, conv_tol, phases, lm, adam_lr
-        self.n = len(pairs)
-        self.max_N = max(p["rec"]["pair"]["N"] for p in pairs) + 3
-        self.Ns = [p["rec"]["pair"]["N"] for p in pairs]
-        self.tile0 = np.cumsum([1] + [p["rec"]["pair"]["n_tiles"] for p in pairs])
-        self.rec0 = np.cumsum([1] + [len(p["rec"]["seg"]) for p in pairs])
-        self.recs = [p["rec"] for p in pairs]
-        self.ref = []
-        kld = np.full((self.n, self.max_N), SENTINEL, f32)
-        for i, p in enumerate(pairs):
-            st = ref.new_state(p["pose"], p["kld"], self.max_N, lam0=p["lam0"], scheduled=entry == "sched")
-            if entry == "gn":
-                st["done"] = None
-            if entry == "sched":
-                st["phase"] = p["phase"]
-            st["backup"][:] = SENTINEL
-            st["cost"] = f32(SENTINEL)
-            self.ref.append(st)
-            kld[i, :self.Ns[i]] = p["kld"]
-        self.kld = T(kld)
-        self.pose = T(np.stack([st["pose"] for st in self.ref]).reshape(self.n, 16))
-        self.lm_state = T(np.stack([st["lm_state"] for st in self.ref]))
-        self.backup = T(np.full((self.n, 16 + self.max_N), SENTINEL, f32))
-        self.costs = T(np.full(self.n, SENTINEL, f32))
-        self.done = T(np.zeros(self.n, np.int32))
-        self.phase = T(np.array([p["phase"] for p in pairs], np.int32))
-        self.iters = T(np.zeros(self.n, np.int32))
-        self.adam_state = T(np.zeros((self.n, 2 + 2 * (self.max_N + 8)), f32))
-        self.sto = T(np.concatenate([p["rec"]["pair"]["seg_tile_off"] for p in pairs]).astype(np.int32))
-        sto_off = np.cumsum([0] + [N + 1 for N in self.Ns])
-        arr = (_lib.SpPair * self.n)()
-        for i, p in enumerate(pairs):                     # pix, src4, kp_L, trg3, aff stay NULL: the solver must not touch them
-            d, q = arr[i], p["rec"]["pair"]
-            d.kld, d.pose = self.kld[i].data_ptr(), self.pose[i].data_ptr()
-            d.seg_tile_off = self.sto.data_ptr() + 4 * int(sto_off[i])
-            d.N, d.P, d.tile0, d.n_tiles, d.rec0 = q["N"], q["P"], int(self.tile0[i]), q["n_tiles"], int(self.rec0[i])
-        self.pairs = T(np.frombuffer(bytes(arr), np.uint8).copy())
-        self.span = T(np.full((int(self.tile0[-1]) + 1, ref.NVP), GUARD, f32))
-        self.seg = T(np.full((int(self.rec0[-1]) + 1, ref.NVS), GUARD, f32))
-        self.load(self.recs)
-
-    def load(self, recs):
-        self.recs = list(recs)
-        for i, r in enumerate(recs):
-            assert r["span"].shape == (self.tile0[i + 1] - self.tile0[i], ref.NVP) and len(r["seg"]) == self.rec0[i + 1] - self.rec0[i]
-            self.span[int(self.tile0[i]):int(self.tile0[i + 1])] = T(r["span"])
-            if len(r["seg"]):
-                self.seg[int(self.rec0[i]):int(self.rec0[i + 1])] = T(r["seg"])
-
-    def args(self, i):
-        a = dict(lm_up=self.lm[0], lm_down=self.lm[1], lm_min=self.lm[2], adam_lr_pose=self.adam_lr[0], adam_lr_kld=self.adam_lr[1])
-        if self.entry == "conv":
-            a["conv_tol"] = self.conv_tol
-        if self.entry == "sched":
-            p = self.ref[i]["phase"]
-            ph = self.phases[p]
-            fl = ph.get("flags", 0)
-            a.update(conv_tol=ph.get("conv_tol", 0.0), max_iters=ph["max_iters"], next_phase=ph.get("next", 0) or p + 1,
-                     pose_only=bool(fl & self._lib.SP_PHASE_POSE_ONLY), depth_damp=0.125 * ((fl >> self._lib.SP_PHASE_DEPTH_DAMP_SHIFT) & 0xff),
-                     predicted_exit=bool(fl & self._lib.SP_PHASE_PREDICTED_EXIT), adam=bool(fl & self._lib.SP_PHASE_ADAM))
-        return GnArgs(**a)
-
-    def expect(self, i, info=None):
-        """The reference's new state of pair i for the loaded records."""
-        st, r = self.ref[i], self.recs[i]
-        if self.entry == "sched" and st["phase"] >= len(self.phases):
-            if info is not None:
-                info["decision"] = "finished"
-            return ref.copy_state(st)
-        a = self.args(i)
-        if a.get("adam"):
-            if info is not None:
-                info["decision"] = "adam"
-            return ref.adam_sched_ref(r["span"], r["seg"], r["pair"], st, a)
-        return ref.gn_step_ref(r["span"], r["seg"], r["pair"], st, a, info)
-
-    def launch(self):
-        L, p = self._lib, self._lib.ptr
-        up, down, lmin = (float(x) for x in self.lm)
-        if self.entry == "gn":
-            rc = self.lib.sp_pairs_gn_step(p(self.pairs), self.n, self.max_N, p(self.span), p(self.seg), up, down, lmin, p(self.lm_state),
-                                           p(self.backup), p(self.costs), L.stream_ptr())
-        elif self.entry == "conv":
-            rc = self.lib.sp_pairs_gn_step_conv(p(self.pairs), self.n, self.max_N, p(self.span), p(self.seg), up, down, lmin, p(self.lm_state),
-                                                p(self.backup), p(self.costs), float(self.conv_tol), p(self.done), L.stream_ptr())
-        else:
-            sched = L.SpSchedule()
-            for k, spec in enumerate(self.phases):
-                ph = sched.phase[k]
-                ph.pairs, ph.span_partials, ph.seg_partials = self.pairs.data_ptr(), self.span.data_ptr(), self.seg.data_ptr()
-                ph.n_spans, ph.max_iters, ph.conv_tol = int(self.tile0[-1]), spec["max_iters"], spec.get("conv_tol", 0.0)
-                ph.flags, ph.next = spec.get("flags", 0), spec.get("next", 0)
-            sched.n_phases, sched.entry, sched.retry_entry, sched.retry2_entry = len(self.phases), 0, -1, -1
-            sched.adam_lr_pose, sched.adam_lr_kld, sched.adam_state = self.adam_lr[0], self.adam_lr[1], self.adam_state.data_ptr()
-            rc = self.lib.sp_pairs_schedule_gn_step(ctypes.addressof(sched), self.n, self.max_N, up, down, lmin, p(self.lm_state), p(self.backup),
-                                                    p(self.costs), p(self.phase), p(self.iters), None, L.stream_ptr())
-        L.check(rc, self.entry)
-        torch.cuda.synchronize()
-
-    def step(self, exact=True, what=""):
-        """Launch once, compare all three pairs with the reference, let the reference continue from the device's values.  Returns the
-        reference's ``info`` of every pair."""
-        infos = [{} for _ in range(self.n)]
-        want = [self.expect(i, infos[i]) for i in range(self.n)]
-        self.launch()
-        kld, pose, lm, backup, costs = npy(self.kld), npy(self.pose), npy(self.lm_state), npy(self.backup), npy(self.costs)
-        done, phase, iters, adam = npy(self.done), npy(self.phase), npy(self.iters), npy(self.adam_state)
-        assert np.array_equal(npy(self.span[0]), np.full(ref.NVP, GUARD, f32)) and np.array_equal(npy(self.seg[-1]), np.full(ref.NVS, GUARD, f32))
-        worst = {}
-        for i, (w, info) in enumerate(zip(want, infos)):
-            tag, N, dec = f"{what} pair {i} ({info['decision']})", self.Ns[i], info["decision"]
-            if dec in ("step", "adam"):
-                assert info.get("cond", 1.0) <= 1e6, f"{tag}: condition number {info['cond']:.3g}"
-            wk = np.full(self.max_N, SENTINEL, f32)
-            wk[:N] = w["kld"]
-            if dec == "adam":
-                lr_p, lr_k = self.adam_lr
-                dk, dp = np.abs(kld[i].astype(np.float64) - wk), np.abs(pose[i].astype(np.float64) - w["pose"].ravel())
-                assert (dk <= 1e-6 * lr_k + np.spacing(np.abs(wk))).all(), f"{tag}: kld off by {dk.max():.3g}"
-                assert (dp <= 1e-6 * lr_p + np.spacing(np.abs(w["pose"].ravel()))).all(), f"{tag}: pose off by {dp.max():.3g}"
-                wa = ref.adam_moments(w, self.max_N)
-                assert adam[i, 0] == wa[0] and adam[i, 1] == 0
-                M = self.max_N               # each moment vector to 1e-6 of its own scale: a handful of float32 roundings per iteration
-                for lo, hi in ((2, 2 + M), (2 + M, 2 + 2 * M), (2 + 2 * M, 8 + 2 * M), (8 + 2 * M, 14 + 2 * M), (14 + 2 * M, len(wa))):
-                    np.testing.assert_allclose(adam[i, lo:hi], wa[lo:hi], rtol=1e-6, atol=1e-6 * np.abs(wa[lo:hi]).max(), err_msg=tag)
-                for name, v in (("adam kld / lr", dk.max() / lr_k), ("adam pose / lr", dp.max() / lr_p)):
-                    worst[name] = max(worst.get(name, 0.0), v)
-            else:
-                ulps = 2 if dec == "step" else 0
-                for name, got, exp in (("kld", kld[i], wk), ("pose", pose[i], w["pose"].ravel())):
-                    d = np.abs(got.astype(np.float64) - exp.astype(np.float64)) / np.spacing(np.maximum(np.abs(exp), f32(1e-30)))
-                    worst[name] = max(worst.get(name, 0.0), float(d.max()))
-                    assert d.max() <= ulps, f"{tag}: {name} off by {d.max():.3g} ulp at {d.argmax()}"
-                assert np.array_equal(adam[i], np.zeros_like(adam[i])), tag
-            assert np.array_equal(backup[i], w["backup"]), f"{tag}: backup"
-            for k in (0, 2, 3, 4, 7):
-                assert lm[i, k] == w["lm_state"][k], f"{tag}: lm_state[{k}] {lm[i, k]} != {w['lm_state'][k]}"
-            for name, got, exp in [(f"lm_state[{k}]", lm[i, k], w["lm_state"][k]) for k in (1, 5, 6)] + [("costs", costs[i], w["cost"])]:
-                d = abs(float(got) - float(exp)) / np.spacing(abs(exp))
-                worst["cost"] = max(worst.get("cost", 0.0), d)
-                assert d <= (0 if exact else 1), f"{tag}: {name} {got!r} != {exp!r} ({d:.3g} ulp)"
-            if self.entry == "conv":
-                assert done[i] == w["done"], f"{tag}: done"
-            if self.entry == "sched":
-                assert (phase[i], iters[i]) == (w["phase"], w["iters"]), f"{tag}: phase / iters {phase[i], iters[i]} != {w['phase'], w['iters']}"
-            # the reference goes on from what the device holds
-            w["kld"], w["pose"] = kld[i, :N].copy(), pose[i].reshape(4, 4).copy()
-            w["lm_state"], w["cost"] = lm[i].copy(), costs[i]
-        print(f"{what}: worst distance from the reference (ulp) " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
-        self.ref = want
-        return infos
-
-
-def swap_cost(rec, base, factor):
-    """``rec`` with the sum |r| column of ``base`` times ``factor``: a scripted cost on another system."""
-    out = dict(rec, span=rec["span"].copy())
-    out["span"][:, 0] = base["span"][:, 0]
-    ref.scale_cost(out, factor)
-    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
