@@ -1682,6 +1682,48 @@ int sp_tsdf_mesh(const float* tsdf, const float* weight, const float* colour, in
                  float min_weight, void* scratch, long long max_vertices, long long max_faces, float* vertices, float* vertex_colours,
                  int32_t* faces, long long* n_out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Surface views (sp_raycast.hip): the volume ray-cast into depth, normal, colour and cell-index images of V cameras -- the surface a
+ * sequence saw, or a ground-truth surface, as sp_depth_metrics and sp_image_metrics score it, and the model view a frame-to-model step
+ * needs.  ONE launch, one thread per pixel, on the caller's stream without a synchronisation; no atomics, no scratch, nothing zeroed:
+ * two runs give the same bits.  Argument checks come before any device work.
+ *     tsdf, weight, colour (or NULL), nx, ny, nz, voxel, ox, oy, oz, min_weight : the volume, as sp_tsdf_mesh takes it
+ *     views   : V SpView records on the device, camera-to-world
+ *     z_start, step, n_steps : the samples of a ray, at camera depths z_k = z_start + k step, k = 0 .. n_steps-1
+ *     depth   : (V,H,W) float32;  normals : (V,H,W,3) float32, world frame;  image : (V,H,W,3) uint8;  index : (V,H,W) int32 -- each may be
+ *               NULL, at least one must be given, image needs colour.  EVERY GIVEN OUTPUT IS WRITTEN FOR EVERY PIXEL
+ * THE RULE.  Float64 from the float32 inputs, every operation rounded on its own (no fma, no reciprocal).
+ * Ray.  Pixel centres are at integers, as in sp_tsdf_integrate:  xr = (col - cx) / fx,  yr = (row - cy) / fy.  The ray is parameterised by
+ * camera z, the quantity depth images and the projective sdf of sp_tsdf_integrate use:  q = (xr z, yr z, z), and the world point is
+ *     p_a(z) = ((R_a0 q0 + R_a1 q1) + R_a2 q2) + t_a;   an exact identity pose leaves p = q (sp_render_views' convention).
+ * Sample S(p).  Per axis  g_a = ((p_a - o_a) / voxel) - 0.5,  i_a = floor(g_a),  f_a = g_a - i_a.  The sample is VALID iff every g_a is
+ * finite, 0 <= i_a and i_a + 1 <= n_a - 1 on all three axes, and all eight nodes (ix + dx, iy + dy, iz + dz), dx, dy, dz in {0, 1}, are
+ * valid by sp_tsdf_mesh's definition (weight >= min_weight, tsdf finite).  Its value is the trilinear interpolation of the eight tsdf
+ * values by lerps a + f (b - a): along x first (four, f = f_x, a at dx = 0), then y (two), then z (one).  C(p), three colour channels, is
+ * interpolated in the same way from the same cell.
+ * March.  z_k = z_start + float64(k) step,  F_k = S(p(z_k)).  The ray ENDS at the first k whose sample is valid and negative (F_k < 0; an
+ * exact 0 is positive, as in the mesh).  It is a HIT iff k >= 1, sample k-1 is valid and F_{k-1} >= 0; otherwise the ray ends without a
+ * hit (the surface is seen from behind, or through an unobserved gap).  A ray that never meets a valid negative sample has no hit.
+ * On a hit.  t = F_{k-1} / (F_{k-1} - F_k),  z* = t step + z_{k-1};  depth = float32(z*);  index = (iz ny + iy) nx + ix of the lower
+ * node of sample k's cell;  per channel c = C_{k-1} + t (C_k - C_{k-1}), rounded to float32 once, and image = trunc(c * 255) from the
+ * exact float64 product, clamped to 0 .. 255, NaN gives 0 (sp_render_views' rule and device function).
+ * Normal.  With p* = p(z*) and h = voxel:  g_a = S(p* + h e_a) - S(p* - h e_a).  If any of the six samples is invalid all three components
+ * are NaN (the depth stands).  Otherwise n = g / sqrt((g0 g0 + g1 g1) + g2 g2), IEEE square root and divisions, rounded to float32 once;
+ * a length that is not finite or not > 0 gives NaN.  The tsdf grows towards free space, so n faces the cameras that saw the surface: the
+ * orientation of sp_map_normals and of the mesh's faces.
+ * No hit.  depth = 0, index = -1, image = 0, 0, 0, normals NaN.
+ * A sample outside the box of node centres is invalid by the rule, so the kernel skips the k it can prove invalid (the ray clipped
+ * against the box, widened by far more than any rounding, plus a step either side) and runs the rule over the rest: the result is that
+ * of marching every k.  The step is fixed; skipping free space by the field's value would change which pair of samples brackets the
+ * crossing and is not done.
+ * Null tsdf / weight / views, all four outputs NULL, image without colour, nx, ny or nz < 2, V, H or W < 1, voxel or step not finite or
+ * not > 0, a non-finite origin, a NaN min_weight, z_start negative or not finite, n_steps < 2: SP_EINVAL.  V > 65535, V H W >= 2^31,
+ * nx ny nz > 2^30, n_steps > 2^20 (SP_TSDF_RAYCAST_MAX_STEPS): SP_ELIMIT.  Invalid beats too large. */
+#define SP_TSDF_RAYCAST_MAX_STEPS (1 << 20)
+int sp_tsdf_raycast(const float* tsdf, const float* weight, const float* colour, int nx, int ny, int nz, float voxel, float ox, float oy, float oz,
+                    float min_weight, const SpView* views, int V, int H, int W, float z_start, float step, int n_steps, float* depth,
+                    float* normals, uint8_t* image, int32_t* index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

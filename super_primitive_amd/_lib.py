@@ -114,6 +114,7 @@ SIGNATURES = {
     "sp_tsdf_integrate": [P, P, P, I, I, I, I, I, I, F, F, F, F, F, F, F, P, P, P, P],
     "sp_tsdf_mesh_scratch_bytes": [I, I, I],
     "sp_tsdf_mesh": [P, P, P, I, I, I, F, F, F, F, F, P, ctypes.c_longlong, ctypes.c_longlong, P, P, P, P, P],
+    "sp_tsdf_raycast": [P, P, P, I, I, I, F, F, F, F, F, P, I, I, I, F, F, I, P, P, P, P, P],
 }
 
 # the entry points that do not return an int
@@ -294,6 +295,7 @@ SP_MAP_FUSE_MAX_POINTS = 1 << 28
 SP_CLOUD_GRID_MAX_POINTS = 1 << 28
 SP_CLOUD_KNN_MAX = 32
 SP_TSDF_MAX_NODES = 1 << 30
+SP_TSDF_RAYCAST_MAX_STEPS = 1 << 20
 SP_CLOUD_REG_RUNNING, SP_CLOUD_REG_CONVERGED, SP_CLOUD_REG_MAX_ITERS, SP_CLOUD_REG_FEW, SP_CLOUD_REG_DEGENERATE = range(5)
 SP_CLOUD_REG_ITERS_LIMIT = 4096
 SP_CLOUD_REG_WORK_DOUBLES = 40

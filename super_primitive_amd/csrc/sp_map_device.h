@@ -1,4 +1,4 @@
-// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip, sp_register.hip, sp_tsdf.hip): each idiom has its one definition here.
+// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip, sp_register.hip, sp_tsdf.hip, sp_raycast.hip): each idiom has its one definition here.
 #pragma once
 #include "sp_device.h"
 
@@ -277,6 +277,20 @@ __device__ __forceinline__ void camera_point(const ViewD& w, double px, double p
     }
 }
 
+// camera_point's inverse along the ray of one pixel (the contract of sp_tsdf_raycast in include/sp_hip.h): the ray is parameterised by
+// camera z, q = (xr z, yr z, z), and p = R q + t, every row as ((a + b) + c) + t.  R is Rt read transposed (R_ab = Rt[3 b + a]); an exact
+// identity pose leaves p = q.
+__device__ __forceinline__ void world_point(const ViewD& w, double xr, double yr, double z, double& px, double& py, double& pz) {
+#pragma clang fp contract(off)
+    const double q0 = xr * z, q1 = yr * z;
+    px = q0; py = q1; pz = z;
+    if (!w.ident) {
+        px = ((w.Rt[0] * q0 + w.Rt[3] * q1) + w.Rt[6] * z) + w.t[0];
+        py = ((w.Rt[1] * q0 + w.Rt[4] * q1) + w.Rt[7] * z) + w.t[1];
+        pz = ((w.Rt[2] * q0 + w.Rt[5] * q1) + w.Rt[8] * z) + w.t[2];
+    }
+}
+
 // u = x fx / z + cx, v = y fy / z + cy: two IEEE divisions
 __device__ __forceinline__ void pixel_of(const ViewD& w, double x, double y, double z, double& u, double& v) {
 #pragma clang fp contract(off)
@@ -286,6 +300,27 @@ __device__ __forceinline__ void pixel_of(const ViewD& w, double x, double y, dou
 
 // the half-width of a footprint in pixels: anything that is not >= 0 (a negative or NaN radius, inf / inf) is a point
 __device__ __forceinline__ double half_width(double h, double cap) { return !(h >= 0.0) ? 0.0 : (h < cap ? h : cap); }
+
+// ---- signed-distance volumes (sp_tsdf.hip, sp_raycast.hip): where a node sits, when it counts, its cell's corners, the sizes allowed ----
+// the centre of node i of one axis: ((float64(i) + 0.5) * voxel) + o
+__device__ __forceinline__ double node_centre(int i, double voxel, double o) {
+#pragma clang fp contract(off)
+    return ((double)i + 0.5) * voxel + o;
+}
+// a node is VALID iff its weight is >= min_weight and its tsdf is finite
+__device__ __forceinline__ bool node_valid(float f, float w, float min_weight) { return w >= min_weight && fabsf(f) < HUGE_VALF; }
+// the linear offset of corner / edge type c from a node (offset bits x = 1, y = 2, z = 4)
+__device__ __forceinline__ int corner_offset(int c, int nx, int nxy) { return (c & 1) + ((c >> 1) & 1) * nx + (c >> 2) * nxy; }
+
+// nx ny nz without overflow: 0 if any is < 1, -1 beyond the limit
+inline long long volume_nodes(int nx, int ny, int nz) {
+    if (nx < 1 || ny < 1 || nz < 1) return 0;
+    const long long xy = (long long)nx * ny;
+    if (xy > SP_TSDF_MAX_NODES || xy * nz > SP_TSDF_MAX_NODES) return -1;
+    return xy * nz;
+}
+
+inline bool finite_f(float x) { return fabsf(x) < HUGE_VALF; }
 
 // ---- the resolve pass of every depth buffer of keys (sp_render_views, sp_render_splats, sp_render_surfels): one definition here, one
 // static copy in every file that launches it and says so by defining SP_MAP_DEVICE_RESOLVE before this header ----------------------

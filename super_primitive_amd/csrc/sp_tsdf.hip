@@ -31,9 +31,6 @@
 namespace {
 
 // ---- integrate ------------------------------------------------------------------------------------------------------------------------
-// the centre of node i of one axis: ((float64(i) + 0.5) * voxel) + o
-__device__ __forceinline__ double node_centre(int i, double voxel, double o) { return ((double)i + 0.5) * voxel + o; }
-
 // new = (old * weight + sample) / (weight + 1), float32, every operation rounded on its own
 __device__ __forceinline__ float running_mean(float old, float weight, float sample, float wn) {
     return __fdiv_rn(__fadd_rn(__fmul_rn(old, weight), sample), wn);
@@ -182,10 +179,6 @@ __constant__ MeshTable MESH_TABLE = MESH_TABLE_HOST;
 // ---- mesh: kernels ----------------------------------------------------------------------------------------------------------------------
 struct MeshDims { int nx, ny, nz; };
 
-__device__ __forceinline__ bool node_valid(float f, float w, float min_weight) { return w >= min_weight && fabsf(f) < HUGE_VALF; }
-// the linear offset of corner / edge type c from a node
-__device__ __forceinline__ int corner_offset(int c, int nx, int nxy) { return (c & 1) + ((c >> 1) & 1) * nx + (c >> 2) * nxy; }
-
 // grid ceil(nx ny nz / 256)
 __global__ __launch_bounds__(SP_BLOCK) void k_mesh_nodes(const float* __restrict__ tsdf, const float* __restrict__ weight, MeshDims d, int n_nodes,
                                                          float min_weight, int32_t* __restrict__ words, int32_t* __restrict__ block_counts) {
@@ -326,16 +319,6 @@ __global__ __launch_bounds__(SP_BLOCK) void k_mesh_vertices(const float* __restr
         ++row;
     }
 }
-
-// nx ny nz without overflow: 0 if any is < 1, -1 beyond the limit
-long long volume_nodes(int nx, int ny, int nz) {
-    if (nx < 1 || ny < 1 || nz < 1) return 0;
-    const long long xy = (long long)nx * ny;
-    if (xy > SP_TSDF_MAX_NODES || xy * nz > SP_TSDF_MAX_NODES) return -1;
-    return xy * nz;
-}
-
-bool finite_f(float x) { return fabsf(x) < HUGE_VALF; }
 
 struct MeshLayout { long long nodes, cells, node_blocks, cell_blocks, word_units, node_block_units, cell_block_units; };
 

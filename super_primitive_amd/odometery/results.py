@@ -32,6 +32,10 @@
 ``fuse_tsdf``         depth images fused into one dense signed-distance volume (``tsdf_volume``; ONE ``sp_tsdf_integrate`` launch):
                       the average of what every view saw; ``sequence_tsdf`` fuses a sequence's own keyframes, ``extract_mesh`` cuts the
                       zero level set into an indexed triangle mesh (``sp_tsdf_mesh``) whose vertices are a cloud every function above takes.
+``render_surface``    the fused surface seen from V cameras, one ray per pixel through the volume (ONE ``sp_tsdf_raycast`` launch): depth at
+                      the zero crossing, normals from the field's gradient, interpolated colour, the cell behind the surface;
+                      ``score_surface`` / ``score_surface_images`` score those views against ground-truth depth and real images, as
+                      ``score_map`` / ``score_map_images`` score the points (the scoring tails are shared).
 ``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file; a mesh's faces too."""
 from __future__ import annotations
 
@@ -188,6 +192,24 @@ def render_map(world, Ks, poses, size, depth_buffer=True, radii=None, max_px=8, 
                             normals=_surfel_normals(world, normals, radii, "render_map"), cull=cull)
 
 
+def _target_images(images, poses, what):
+    """(H, W) of ``images``, which must be float32 (V,3,H,W) for the V ``poses``."""
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[0] != poses.shape[0] or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError(f"{what}: images must be float32 (V,3,H,W) for {poses.shape[0]} views, got "
+                         f"{tuple(images.shape) if torch.is_tensor(images) else type(images).__name__}")
+    return int(images.shape[2]), int(images.shape[3])
+
+
+def _image_scores(rendered, images, index):
+    """The tail of ``score_map_images`` / ``score_surface_images``: ONE ``sp_image_metrics`` launch over the pixels with ``index >= 0`` and
+    the figures from its integer sums."""
+    from ..tool import viz
+    H, W = int(images.shape[2]), int(images.shape[3])
+    sums = viz.image_metrics(rendered, images, index)
+    n3, s1, s2 = 3.0 * sums[:, 0].double(), sums[:, 1].double(), sums[:, 2].double()
+    return dict(sums=sums, psnr=10.0 * torch.log10(255.0 ** 2 * n3 / s2), l1=s1 / n3, coverage=sums[:, 0].double() / float(H * W))
+
+
 def score_map_images(world, images, Ks, poses, radii=None, max_px=8, normals=False, cull=False):
     """The map's rendered views against real images: ``images`` (V,3,H,W) float32 in 0..1, ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4)
     camera-to-world in the map's frame; ``radii`` / ``max_px`` / ``normals`` / ``cull`` as in ``render_map``.  One render launch (depth buffer) plus ONE
@@ -197,16 +219,32 @@ def score_map_images(world, images, Ks, poses, radii=None, max_px=8, normals=Fal
     n = 0), coverage (V,) float64 = n / (H W)).  No synchronisation."""
     from ..tool import viz
     Ks, poses = _view_cameras(Ks, poses, "score_map_images")
-    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[0] != poses.shape[0] or images.shape[1] != 3 or images.dtype != torch.float32:
-        raise ValueError(f"score_map_images: images must be float32 (V,3,H,W) for {poses.shape[0]} views, got "
-                         f"{tuple(images.shape) if torch.is_tensor(images) else type(images).__name__}")
-    H, W = int(images.shape[2]), int(images.shape[3])
+    H, W = _target_images(images, poses, "score_map_images")
     _lib.require_device(images, world['points'])
     out = viz.render_views(world['points'], world['colours'], Ks, poses, H, W, depth_buffer=True, depth=False, radii=radii, max_px=max_px,
                            normals=_surfel_normals(world, normals, radii, "score_map_images"), cull=cull)
-    sums = viz.image_metrics(out['image'], images, out['index'])
-    n3, s1, s2 = 3.0 * sums[:, 0].double(), sums[:, 1].double(), sums[:, 2].double()
-    return dict(sums=sums, psnr=10.0 * torch.log10(255.0 ** 2 * n3 / s2), l1=s1 / n3, coverage=sums[:, 0].double() / float(H * W))
+    return _image_scores(out['image'], images, out['index'])
+
+
+def _target_depths(gt_depths, gt_poses, min_depth, max_depth, what):
+    """(V, H, W) of ``gt_depths``, which must be float32 (V,H,W) for the V ``gt_poses``; the depth range must not be empty."""
+    if not torch.is_tensor(gt_depths) or gt_depths.dim() != 3 or gt_depths.shape[0] != gt_poses.shape[0] or gt_depths.dtype != torch.float32:
+        raise ValueError(f"{what}: gt_depths must be float32 (V,H,W) for {gt_poses.shape[0]} views, got "
+                         f"{tuple(gt_depths.shape) if torch.is_tensor(gt_depths) else type(gt_depths).__name__}")
+    if not float(min_depth) <= float(max_depth):
+        raise ValueError(f"{what}: depth range {min_depth} .. {max_depth}")
+    return tuple(int(n) for n in gt_depths.shape)
+
+
+def _depth_scores(depth, landed, gt_depths, min_depth, max_depth):
+    """The tail of ``score_map`` / ``score_surface``: ``depth`` (V,H,W) scored against ``gt_depths`` on the pixels where something ``landed``
+    and ``min_depth <= gt <= max_depth``: ONE ``sp_depth_metrics`` call, and the coverage."""
+    from ..depth_completion import void
+    in_range = (gt_depths >= min_depth) & (gt_depths <= max_depth)
+    scored = in_range & landed
+    metrics = void.depth_metrics(depth, gt_depths, scored)
+    coverage = scored.sum(dim=(1, 2)).double() / in_range.sum(dim=(1, 2)).double()
+    return dict(metrics=metrics, columns=void._COLUMNS, coverage=coverage)
 
 
 def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size=None, radii=None, max_px=8, normals=False, cull=False):
@@ -220,25 +258,15 @@ def score_map(world, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, size
     ``radii`` / ``max_px``: the footprints of ``render_map``, so that a sparse map is scored on every pixel its surfaces cover;
     ``normals`` / ``cull``: its oriented surfels, so that the score carries no error of a flat splat on a slanted surface.
     No synchronisation."""
-    from ..depth_completion import void
     from ..tool import viz
     Ks, gt_poses = _view_cameras(Ks, gt_poses, "score_map")
-    if not torch.is_tensor(gt_depths) or gt_depths.dim() != 3 or gt_depths.shape[0] != gt_poses.shape[0] or gt_depths.dtype != torch.float32:
-        raise ValueError(f"score_map: gt_depths must be float32 (V,H,W) for {gt_poses.shape[0]} views, got "
-                         f"{tuple(gt_depths.shape) if torch.is_tensor(gt_depths) else type(gt_depths).__name__}")
-    if not float(min_depth) <= float(max_depth):
-        raise ValueError(f"score_map: depth range {min_depth} .. {max_depth}")
-    V, H, W = gt_depths.shape
+    V, H, W = _target_depths(gt_depths, gt_poses, min_depth, max_depth, "score_map")
     if size is not None and tuple(int(s) for s in size) != (H, W):
         raise ValueError(f"score_map: size {tuple(size)} against ground-truth depths of {H}x{W}")
     _lib.require_device(gt_depths, world['points'])
     depth = viz.render_views(world['points'], None, Ks, gt_poses, H, W, depth_buffer=True, image=False, index=False, radii=radii,
                              max_px=max_px, normals=_surfel_normals(world, normals, radii, "score_map"), cull=cull)['depth']
-    in_range = (gt_depths >= min_depth) & (gt_depths <= max_depth)
-    scored = in_range & (depth > 0)
-    metrics = void.depth_metrics(depth, gt_depths, scored)
-    coverage = scored.sum(dim=(1, 2)).double() / in_range.sum(dim=(1, 2)).double()
-    return dict(metrics=metrics, columns=void._COLUMNS, coverage=coverage)
+    return _depth_scores(depth, depth > 0, gt_depths, min_depth, max_depth)
 
 
 def map_consistency(world, depths, Ks, poses, view_kf=None, tol=0.05, window=1):
@@ -798,6 +826,59 @@ def extract_mesh(volume, min_weight=1.0):
     colours = found['colours'] if found['colours'] is not None else torch.zeros(M, 3, dtype=torch.float32, device=dev)
     none = torch.full((M,), -1, dtype=torch.int32, device=dev)
     return dict(points=points, colours=colours, faces=found['faces'], kf_index=none, seg_ids=none.clone(), offsets=np.array([0, M], dtype=np.int64))
+
+
+def render_surface(volume, Ks, poses, size, z_max, min_weight=1.0, step=None):
+    """The fused surface seen from V cameras: ``render_map``'s counterpart for a volume (``fuse_tsdf`` / ``sequence_tsdf``), ONE
+    ``sp_tsdf_raycast`` launch (``tool.viz.tsdf_raycast``; include/sp_hip.h has the rule).  ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4)
+    camera-to-world in the volume's frame, ``size`` = (H, W); every ray is sampled every ``step`` (default: one voxel) of camera depth up
+    to ``z_max``.  Returns dict(depth (V,H,W) float32 -- the zero crossing, 0 without a hit --, normals (V,H,W,3) float32 in the volume's
+    frame, facing the cameras that saw the surface, NaN without a hit or next to unobserved cells, image (V,H,W,3) uint8 -- zeros for a
+    volume without colour --, index (V,H,W) int32 -- the lower node of the cell behind the surface, -1 without a hit).  No synchronisation."""
+    from ..tool import viz
+    Ks, poses = _view_cameras(Ks, poses, "render_surface")
+    H, W = size
+    out = viz.tsdf_raycast(volume, Ks, poses, H, W, z_max, min_weight=min_weight, step=step)
+    if 'image' not in out:
+        out['image'] = torch.zeros(*out['index'].shape, 3, dtype=torch.uint8, device=out['index'].device)
+    return out
+
+
+def _surface_step(volume, step, what):
+    """``step`` (default: the volume's voxel) as a finite float > 0."""
+    try:
+        step = float(volume['voxel'] if step is None else step)
+    except (TypeError, ValueError, KeyError) as e:
+        raise ValueError(f"{what}: step {step!r} for volume {type(volume).__name__}: {e}") from None
+    if not (0.0 < step < float("inf")):
+        raise ValueError(f"{what}: step {step} (finite, > 0)")
+    return step
+
+
+def score_surface(volume, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, min_weight=1.0, step=None):
+    """The fused surface against ground-truth depth images: ``score_map`` for a volume.  The surface is ray-cast into each of the V
+    ground-truth views up to ``z_max = max_depth + step`` (``render_surface``'s launch, depth and index only) and scored where a ray hit
+    (``index >= 0``) and ``min_depth <= gt <= max_depth``.  Returns ``score_map``'s dict (metrics (V,12), columns, coverage).  No
+    synchronisation."""
+    from ..tool import viz
+    Ks, gt_poses = _view_cameras(Ks, gt_poses, "score_surface")
+    V, H, W = _target_depths(gt_depths, gt_poses, min_depth, max_depth, "score_surface")
+    step = _surface_step(volume, step, "score_surface")
+    viz._on_device(gt_depths)
+    out = viz.tsdf_raycast(volume, Ks, gt_poses, H, W, float(max_depth) + step, min_weight=min_weight, step=step, normals=False, image=False)
+    return _depth_scores(out['depth'], out['index'] >= 0, gt_depths, min_depth, max_depth)
+
+
+def score_surface_images(volume, images, Ks, poses, z_max, min_weight=1.0, step=None):
+    """The fused surface's colour views against real images: ``score_map_images`` for a volume with colour.  ``images`` (V,3,H,W) float32
+    in 0..1; one ``sp_tsdf_raycast`` launch (image and index) plus ONE ``sp_image_metrics`` launch over the pixels a ray hit.  Returns
+    ``score_map_images``' dict (sums, psnr, l1, coverage).  No synchronisation."""
+    from ..tool import viz
+    Ks, poses = _view_cameras(Ks, poses, "score_surface_images")
+    H, W = _target_images(images, poses, "score_surface_images")
+    viz._on_device(images)
+    out = viz.tsdf_raycast(volume, Ks, poses, H, W, z_max, min_weight=min_weight, step=step, depth=False, normals=False, image=True)
+    return _image_scores(out['image'], images, out['index'])
 
 
 def write_ply(path, world):

@@ -20,6 +20,7 @@ matplotlib is imported):
 ``cloud_normals``      a normal and a surface variation per point of a cloud that has none, from its k nearest points (``sp_cloud_normals``).
 ``tsdf_integrate``     depth images fused into a dense signed-distance volume, in place (``sp_tsdf_integrate``).
 ``tsdf_mesh``          the volume's zero level set as an indexed triangle mesh: a counting call, one host read, a filling call (``sp_tsdf_mesh``).
+``tsdf_raycast``       the volume seen from V cameras: depth, world normals, colour and cell index per pixel, one ray each (``sp_tsdf_raycast``).
 ``register_clouds``    the similarity that moves a query cloud onto such a cloud, by Gauss-Newton ICP on the device (``sp_cloud_register``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
@@ -703,4 +704,64 @@ def tsdf_mesh(volume, min_weight=1.0):
                faces=torch.empty(nf, 3, dtype=torch.int32, device=dev))
     if nv > 0:
         call(nv, nf, out['vertices'], out['colours'], out['faces'] if nf > 0 else None)
+    return out
+
+
+def tsdf_raycast(volume, Ks, poses, H, W, z_max, min_weight=1.0, z_min=Z_MIN, step=None, depth=True, normals=True, image=None, index=True):
+    """ONE ``sp_tsdf_raycast`` launch (include/sp_hip.h has the rule): ``volume`` (what ``odometery.results.tsdf_volume`` returned, fused)
+    seen from V cameras, ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world in the volume's frame.  One ray per pixel, sampled at
+    the camera depths ``z_min + k step``, ``k = 0 .. n_steps-1`` with ``n_steps = ceil((z_max - z_min) / step) + 1`` (``step`` defaults to
+    the volume's voxel); the first valid sample with a negative field ends it, and it is a hit iff the sample before is valid and not
+    negative.  A node counts iff its weight is >= ``min_weight`` and its tsdf is finite.  Returns the requested of ``depth`` (V,H,W)
+    float32 (0 without a hit), ``normals`` (V,H,W,3) float32 in the volume's frame, facing the cameras that saw the surface (NaN without
+    a hit, or where a neighbouring cell is unobserved), ``image`` (V,H,W,3) uint8 (0) and ``index`` (V,H,W) int32, the lower node of the
+    cell behind the surface (-1), as a dict.  ``image=None``: an image iff the volume has a colour; ``image=True`` for a volume without
+    one is an error.  No synchronisation."""
+    tsdf, weight, colour, (nx, ny, nz), vox, org, _ = _volume(volume, "tsdf_raycast")
+    _on_device(tsdf, weight, colour, Ks, poses)
+    if poses.dim() != 3:
+        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
+    V = int(poses.shape[0])
+    if V == 0:
+        raise ValueError("tsdf_raycast: poses of no views")
+    H, W = _size(H, W)
+    views = _views(Ks, poses, V)
+    try:
+        min_weight, z_min, z_max = float(min_weight), float(z_min), float(z_max)
+        step = vox if step is None else float(torch.tensor(float(step), dtype=torch.float32))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"tsdf_raycast: min_weight {min_weight!r}, z_min {z_min!r}, z_max {z_max!r}, step {step!r}: {e}") from None
+    _z_min(z_min)
+    if min_weight != min_weight:
+        raise ValueError("tsdf_raycast: min_weight is NaN")
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"tsdf_raycast: a volume of {nx}x{ny}x{nz} nodes has no cell (every size must be >= 2)")
+    if not (0.0 < step < float("inf")):
+        raise ValueError(f"tsdf_raycast: step {step} (finite float32 > 0)")
+    if not (z_min < z_max < float("inf")):
+        raise ValueError(f"tsdf_raycast: depth range z_min {z_min} .. z_max {z_max} (z_min < z_max, both finite)")
+    steps = (z_max - z_min) / step
+    if not steps < _lib.SP_TSDF_RAYCAST_MAX_STEPS:
+        raise ValueError(f"tsdf_raycast: {steps:.3g} steps of {step} from {z_min} to {z_max} are beyond the kernel's limit of 2^20")
+    n_steps = int(-(-steps // 1)) + 1
+    if image and colour is None:
+        raise ValueError("tsdf_raycast: an image needs a volume with colour")
+    image = colour is not None if image is None else bool(image)
+    if not (depth or normals or image or index):
+        raise ValueError("tsdf_raycast: no output asked for")
+    _limits("tsdf_raycast", V, H, W)
+    lib = _lib.load()
+    dev = tsdf.device
+    out = {}
+    if depth:
+        out['depth'] = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    if normals:
+        out['normals'] = torch.empty(V, H, W, 3, dtype=torch.float32, device=dev)
+    if image:
+        out['image'] = torch.empty(V, H, W, 3, dtype=torch.uint8, device=dev)
+    if index:
+        out['index'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    _lib.check(lib.sp_tsdf_raycast(_lib.ptr(tsdf), _lib.ptr(weight), _lib.ptr(colour), nx, ny, nz, vox, org[0], org[1], org[2], min_weight,
+                                   _lib.ptr(views), V, H, W, z_min, step, n_steps, _lib.ptr(out.get('depth')), _lib.ptr(out.get('normals')),
+                                   _lib.ptr(out.get('image')), _lib.ptr(out.get('index')), _lib.stream_ptr()), "sp_tsdf_raycast")
     return out
