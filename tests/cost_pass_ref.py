@@ -72,6 +72,17 @@ def pair_inputs(pix, src4, kp_L, kld, trg, K_src, K_trg, H, W, Hl, Wl, P, zmin, 
                 Wl=int(Wl), P=int(P), zmin=float(f32(zmin)), pose=np.asarray(pose).reshape(4, 4), aff=None if aff is None else np.asarray(aff).reshape(4))
 
 
+def point_inputs(xyz, rgb, trg, K_trg, H, W, Hl, Wl, P, zmin, pose, aff=None):
+    """One explicit point list as sp_points_cost_grad sees it (tests/single_cost_ref.py): xyz (n,3) source-camera points and rgb (n,3)
+    given directly -- no source camera, no pixel words, no shift; a point is source-valid when its depth xyz[:, 2] > 1e-7."""
+    xyz, rgb = np.asarray(xyz).reshape(-1, 3), np.asarray(rgb).reshape(-1, 3)
+    n = len(xyz)
+    pr = pair_inputs(np.zeros(n, np.uint32), np.concatenate((rgb, np.zeros((n, 1), rgb.dtype)), axis=1), np.zeros(0, xyz.dtype), np.zeros(0, xyz.dtype),
+                     trg, (1.0, 1.0, 0.0, 0.0), K_trg, H, W, Hl, Wl, P, zmin, pose, aff)
+    pr["xyz"] = xyz
+    return pr
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # attribution
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -138,10 +149,14 @@ def point_terms(pr, seg, mode, depth_table, irls_eps, dtype, force=None, alt=Non
     R, t = c(pr["pose"][:3, :3]), c(pr["pose"][:3, 3])
     band = T(1.0 if _alter == "band_1" else BAND)
     with np.errstate(all="ignore"):
-        shift = (c(pr["kld"]) - c(pr["kp_L"]))[segc] if len(pr["kld"]) else np.zeros(n, T)
-        w4 = c(pr["src4"][:, 3])
-        d = w4 * np.exp(shift) if depth_table else np.exp(w4 + shift)
-        p = np.stack(((col - cx_s) * d / fx_s, (row - cy_s) * d / fy_s, d), axis=1)
+        if pr.get("xyz") is not None:                               # the explicit-point front (point_inputs): x, y, d as given
+            p = c(pr["xyz"])
+            d, src_ok = p[:, 2], np.ones(n, bool)
+        else:
+            shift = (c(pr["kld"]) - c(pr["kp_L"]))[segc] if len(pr["kld"]) else np.zeros(n, T)
+            w4 = c(pr["src4"][:, 3])
+            d = w4 * np.exp(shift) if depth_table else np.exp(w4 + shift)
+            p = np.stack(((col - cx_s) * d / fx_s, (row - cy_s) * d / fy_s, d), axis=1)
         q = p @ R.T + t
         qx, qy, qz = q[:, 0], q[:, 1], q[:, 2]
         guard = np.abs(qz) > T(1e-6)

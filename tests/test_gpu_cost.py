@@ -1,7 +1,8 @@
 """-m gpu: the HIP cost path (through the C ABI) against (a) golden vectors produced by the real reference and
 (b) the CPU oracle on fresh seeded inputs.  Tolerances (fp32, different exp / reduction order than ATen-CPU):
 residual rtol 2e-5; per-point values atol 2e-5; gradients within 5e-6 of the largest entry (measured: 1.1e-6 worst over
-the reference goldens, profiles/r02_parity.txt; the reference's own fp32 autograd is that far from the exact value)."""
+the reference goldens, profiles/r02_parity.txt; the reference's own fp32 autograd is that far from the exact value).
+Entry-wise bounds against a float64 reference (every gradient entry, every diagnostic point): tests/test_gpu_single_cost.py."""
 import numpy as np
 import pytest
 import torch
