@@ -40,6 +40,17 @@ extern "C" {
 
 #define SP_ABI_VERSION 20
 
+/* Every record of this ABI states its size once, right after its definition: checked by every C++ and C11 translation unit that
+ * includes this header (and, field by field, by tests/test_abi_mirror.py against the ctypes mirror).  Uses take no semicolon. */
+#if defined(__cplusplus)
+#define SP_ABI_ASSERT(cond, msg) static_assert(cond, msg);
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+#define SP_ABI_ASSERT(cond, msg) _Static_assert(cond, msg);
+#else
+#define SP_ABI_ASSERT(cond, msg)
+#endif
+#define SP_ABI_SIZE(T, n) SP_ABI_ASSERT(sizeof(T) == (n), #T " is part of the ABI: " #n " bytes")
+
 #define SP_EINVAL (-1)   /* bad argument (null pointer, non-positive size, ...) */
 #define SP_ELIMIT (-2)   /* size outside what the kernels support (H or W > 32767, N > 65535, ...) */
 
@@ -146,7 +157,8 @@ typedef struct SpPrepTable {     /* one keyframe: its masks are read once per pa
                                     breaks the contract is not seen when its ROW is outside the box or its 16-pixel piece does not
                                     meet the box columns, and seen otherwise (deterministic either way).  Fast path only (see
                                     bits); ignored on the general path, which scans everything */
-} SpPrepTable;                   /* 240 bytes */
+} SpPrepTable;
+SP_ABI_SIZE(SpPrepTable, 240)
 typedef struct SpPrepSample {    /* one table, sampled at up to SP_PREP_MAX_LEVELS pyramid levels in one pass; sets pix bit 31 */
     uint32_t* pix;
     const float* baseL;          /* [P] the table's own log-depths; under SP_PREP_DENSE_L: the keyframe's dense (N,H,W) array (N H W < 2^32) */
@@ -162,14 +174,16 @@ typedef struct SpPrepSample {    /* one table, sampled at up to SP_PREP_MAX_LEVE
     int32_t granule;             /* low 16 bits: padding granule of the runs: 0 / 256, or 64 for wave-span tables (SP_COST_WAVE_SPANS);
                                     | SP_PREP_DEPTH_TABLE: write exp(L) instead of L into src4.w (SP_COST_DEPTH_TABLE)
                                     | SP_PREP_DENSE_L: baseL is the dense (N,H,W) array, a point's log-depth sits at (its segment, row, column) */
-} SpPrepSample;                  /* 176 bytes */
+} SpPrepSample;
+SP_ABI_SIZE(SpPrepSample, 176)
 #define SP_PREP_DEPTH_TABLE 0x10000
 #define SP_PREP_DENSE_L 0x20000
 typedef struct SpPrepImage {
     const float* in;             /* (C,H,W) planar */
     float* out;                  /* (H,W,3) */
     int32_t H, W;
-} SpPrepImage;                   /* 24 bytes */
+} SpPrepImage;
+SP_ABI_SIZE(SpPrepImage, 24)
 int sp_prepare_count(const SpPrepTable* tables, int n_tables, int max_rows, int max_N, void* stream);
 /* (ABI 15) sp_prepare_count for batches whose keyframes ALL carry the segment-box hint (SpPrepTable.boxes; mask_generation.py:93,155-180 computes
  * the boxes of SAM's masks): same outputs, bit for bit; a workgroup tests 64 blocks of 64 rows against the boxes at once and only walks those
@@ -193,7 +207,8 @@ typedef struct SpPrepImagePack {
     float* packed_in;
     float* packed_out;
     int32_t H, W;
-} SpPrepImagePack;               /* 40 bytes */
+} SpPrepImagePack;
+SP_ABI_SIZE(SpPrepImagePack, 40)
 int sp_prepare_blur_pack(const SpPrepImagePack* jobs, int n_jobs, int max_out_pixels, void* stream);
 int sp_prepare_gather(const float* const* src, const long long* off, int n, float* out, void* stream);
 
@@ -288,6 +303,7 @@ typedef struct SpPair {
     float zmin;
     int32_t rec0;             /* first segment record of this pair (= 4 * its first chunk) */
 } SpPair;
+SP_ABI_SIZE(SpPair, 136)
 
 /* HOST helpers (no device work): the work list above for a whole batch.  pc[s] / seg_pos[s]: padded run length and pair-relative
  * position of every segment (all pairs concatenated), n_off[m]: first segment of pair m (n_pairs + 1 entries).  Chunks: pieces of at
@@ -419,6 +435,7 @@ typedef struct SpRunDesc {
     float k;                     /* 1 - s1 */
     int32_t runs;                /* runs among the group's points (1 for an all-zero group) */
 } SpRunDesc;
+SP_ABI_SIZE(SpRunDesc, 32)
 
 /* descriptors of the n_groups groups of pix[0 .. 64 n_groups) into desc[0 .. n_groups] (n_groups + 1 records); *n_general
  * (device int32, zeroed by the caller) += number of groups with more than two runs.  Build it after the table's validity bits are
@@ -482,7 +499,8 @@ typedef struct SpPhase {
     float conv_tol;
     int32_t flags;               /* SP_PHASE_* */
     int32_t next;                /* the phase a pair moves on to: 0 = the following one (p + 1), k > p = phase k (skips phases p+1..k-1) */
-} SpPhase;               /* 64 bytes */
+} SpPhase;
+SP_ABI_SIZE(SpPhase, 64)
 /* entry: the phase a fresh pair starts in.  retry_entry: the phase a pair RESTARTS in -- from its initial pose and log-depths, once --
  * when its verdict at the end of the schedule says it failed (SpVerdict below); -1 = no second attempt.  The phases in front of
  * `entry` belong to the later attempts only: with phases {R0, R1 (next = J), P0, J, ..., polish}, entry = 2 and retry_entry = 0 a
@@ -497,7 +515,8 @@ typedef struct SpSchedule {
     int32_t retry2_entry;
     float adam_lr_pose, adam_lr_kld;     /* SP_PHASE_ADAM phases */
     float* adam_state;                   /* [pairs or slots][2 + 2 (max_N + 8)], device; NULL when no phase is SP_PHASE_ADAM */
-} SpSchedule;            /* 800 bytes */
+} SpSchedule;
+SP_ABI_SIZE(SpSchedule, 800)
 
 /* THE VERDICT of a scheduled run, per pair, on the device.  The reference asserts finiteness every iteration and nothing else
  * (core/dense_optim.py:311,321,340-343); a Gauss-Newton schedule that ends in the wrong basin (about one of the reference's own
@@ -559,7 +578,8 @@ typedef struct SpVerdict {
     float seg_product;           /* <= 0: not tested.  (cost / median - 1) x (worst / median) above this: a moderately raised cost TOGETHER WITH a clear
                                   * outlier segment -- neither ratio alone separates such a pair from a converged one with noisy small segments */
     float pad_;
-} SpVerdict;             /* 104 bytes */
+} SpVerdict;
+SP_ABI_SIZE(SpVerdict, 104)
 #define SP_VERDICT_SEGMENTS 2048
 #define SP_VERDICT_SEGMENT_POINTS 64
 #define SP_VERDICT_MIN_SEGMENTS 8
@@ -622,7 +642,8 @@ typedef struct SpQueue {
     int32_t* active;             /* (ABI 13) device scratch [n_slots] or NULL: the slots that still work on a pair, listed at every poll -- once the queue
                                   * is empty and at most an eighth of the slots are busy, the launches of a round go over those alone (the tail of a run:
                                   * a third attempt iterates 1500 rounds by itself) */
-} SpQueue;               /* 296 bytes */
+} SpQueue;
+SP_ABI_SIZE(SpQueue, 296)
 int sp_pairs_schedule_run_queue(const SpSchedule* sched, const SpQueue* queue, int n_slots, int max_N, float lm_up, float lm_down,
                                 float lm_min, float* lm_state, float* backup, float* costs, int32_t* phase, int32_t* iters,
                                 int check_every, int max_rounds, int32_t* flag_dev, int32_t* flag_host, const SpVerdict* verdict /* or NULL */,
@@ -656,7 +677,8 @@ typedef struct SpWindowNode {
     int32_t kind;        /* 0: edge pose = inv(T_trg) T_src evaluated at zero tangents, T <- T inv(Exp(d)) after every step;
                             1: edge pose = Exp(a) X (two-frame SfM; such a node is only ever a target) */
     int32_t flags;       /* bit 0: renormalise_se3 after every iteration (odometery.py:868,879) */
-} SpWindowNode;          /* 176 bytes */
+} SpWindowNode;
+SP_ABI_SIZE(SpWindowNode, 176)
 
 typedef struct SpWindowEdge {
     int32_t src_node;    /* pose node of the source keyframe, -1 = identity (two-frame SfM) */
@@ -664,6 +686,7 @@ typedef struct SpWindowEdge {
     int32_t block;       /* log-depth block of the source keyframe */
     float weight;        /* loss = sum_e weight_e * (abs_loss ? |residual_e| : residual_e) */
 } SpWindowEdge;
+SP_ABI_SIZE(SpWindowEdge, 16)
 
 typedef struct SpWindowBlock {
     float* kld;          /* [N] -- the SpPair.kld of every edge whose source is this keyframe */
@@ -671,7 +694,8 @@ typedef struct SpWindowBlock {
     float* v;
     int32_t N;
     float lr;            /* 0 = frozen (oldest keyframe of a full window, odometery.py:594-603; tracking) */
-} SpWindowBlock;         /* 32 bytes */
+} SpWindowBlock;
+SP_ABI_SIZE(SpWindowBlock, 32)
 
 /* doubles of scratch sp_window_step needs */
 int sp_window_scratch_doubles(int n_edges, int max_N);
@@ -775,7 +799,8 @@ typedef struct SpWindowGn {
     float* state;                    /* 16 floats, as sp_window_gn_step */
     float* losses;
     int32_t n_spans, n_edges, n_nodes, n_blocks, sum_N, max_N, n_unknowns, max_losses;
-} SpWindowGn;                        /* 136 bytes */
+} SpWindowGn;
+SP_ABI_SIZE(SpWindowGn, 136)
 int sp_window_gn_multi_bytes(void);
 int sp_window_gn_run_multi(const SpWindowGn* windows, int n_windows, float irls_eps, int flags, float lm_up, float lm_down, float lm_min,
                            float conv_tol, int max_iters, int check_every, void* args_dev, float* states_dev, float* states_host, void* stream);
@@ -1036,7 +1061,8 @@ int sp_sam_cut_masks(const uint8_t* masks, int K, int H, int W, const float* edg
 typedef struct SpCamera {
     double fx, fy, cx, cy;
     double k1, k2, p1, p2, k3, k4, k5, k6;   /* OpenCV's order; absent coefficients are 0 */
-} SpCamera;                                  /* 96 bytes */
+} SpCamera;
+SP_ABI_SIZE(SpCamera, 96)
 int sp_frame_ingest(const uint8_t* raw, int B, int H, int W, const SpCamera* cam, int top, int left, int Hc, int Wc, int Ho, int Wo,
                     int bgr, float* out, void* stream);
 int sp_depth_ingest(const uint16_t* raw, int B, int H, int W, float scale, float max_depth, int top, int left, int Hc, int Wc, int Ho,
@@ -1071,7 +1097,8 @@ typedef struct SpChainPhase {
     int32_t level;                     /* pyramid level (index into SpChainWindow.gn) */
     int32_t max_iters;
     float irls_eps, conv_tol;
-} SpChainPhase;                        /* 16 bytes */
+} SpChainPhase;
+SP_ABI_SIZE(SpChainPhase, 16)
 typedef struct SpChainWindow {         /* a built window with its Gauss-Newton schedule */
     SpWindowGn gn[SP_CHAIN_LEVELS];    /* the window at pyramid level l (pairs == NULL: the window has no descriptors there) */
     SpChainPhase phase[SP_CHAIN_PHASES];
@@ -1083,14 +1110,16 @@ typedef struct SpChainWindow {         /* a built window with its Gauss-Newton s
     int32_t check_first;               /* > 0: every phase looks at the state after this many iterations for the first time (a window that
                                         * usually converges at once -- the supplementary mapping -- should not run check_every iterations blind) */
     float* state_host;                 /* host: 16 floats, filled by the call */
-} SpChainWindow;                       /* 680 bytes */
+} SpChainWindow;
+SP_ABI_SIZE(SpChainWindow, 680)
 typedef struct SpChainTarget {         /* a target node whose frame the step replaces */
     float* packed[SP_CHAIN_LEVELS];    /* the node's packed (H_l, W_l, 3) image at pyramid level l, where the window has that level */
     const float* pose;                 /* 16 floats: the node's new camera-to-world pose */
     const float* aff;                  /* 2 floats, or NULL (no affine compensation) */
     int32_t node;
     int32_t pad_;
-} SpChainTarget;                       /* 56 bytes */
+} SpChainTarget;
+SP_ABI_SIZE(SpChainTarget, 56)
 typedef struct SpChainStep {
     int32_t stages;
     int32_t H, W, n_levels;            /* the frame; pyramid levels to build (level 0 = the image itself) */
@@ -1119,6 +1148,7 @@ typedef struct SpChainStep {
     int32_t track_iters, supp_iters;   /* out (host) */
     int32_t pad_;
 } SpChainStep;
+SP_ABI_SIZE(SpChainStep, 1752)
 
 /* ----------------------------------------------------------------------------------------------------
  * sp_chain_step_multi: the stages named in `stages` for n_steps records at once, one record per sequence (n_steps = 1: one sequence), with
@@ -1179,7 +1209,8 @@ typedef struct SpTrajAlign {
     double ate_scaled, ate;            /* root mean square of the per-pose errors with / without scale */
     double dots, norms;                /* s = dots / norms */
     double sigma[3];                   /* singular values of W, descending */
-} SpTrajAlign;                         /* 256 bytes */
+} SpTrajAlign;
+SP_ABI_SIZE(SpTrajAlign, 256)
 int sp_traj_align(const float* pred, const float* gt, const int32_t* lengths, int S, int n_max, int anchor_rotation, SpTrajAlign* out,
                   double* err_scaled, double* err, void* stream);
 
@@ -1205,7 +1236,8 @@ typedef struct SpMapKeyframe {
     long long out_offset;              /* first output row */
     int32_t align;                     /* index of an SpTrajAlign record, or -1 */
     int32_t first_block;               /* first workgroup of the launch that works on this keyframe */
-} SpMapKeyframe;                       /* 96 bytes */
+} SpMapKeyframe;
+SP_ABI_SIZE(SpMapKeyframe, 96)
 int sp_map_points(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int stride, const SpTrajAlign* align, int n_align, float* points,
                   float* colours, int32_t* kf_index, int32_t* seg_ids, long long total_rows, void* stream);
 
@@ -1272,7 +1304,8 @@ int sp_keyframe_depths(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int
 typedef struct SpView {
     float K[9];                        /* row major; fx = K[0], fy = K[4], cx = K[2], cy = K[5] */
     float pose[16];                    /* camera-to-world */
-} SpView;                              /* 100 bytes */
+} SpView;
+SP_ABI_SIZE(SpView, 100)
 int sp_render_views(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, int mode, float z_min,
                     unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream);
 
@@ -1601,13 +1634,10 @@ typedef struct SpCloudReg {
     long long n;
     int32_t status;      /* SP_CLOUD_REG_* */
     int32_t iterations;  /* the iterations that ran while RUNNING */
-    double pad_[5];      /* 512 bytes: a whole number of 64-byte units */
+    double pad_[5];      /* to a whole number of 64-byte units */
 } SpCloudReg;
-#ifdef __cplusplus
-static_assert(sizeof(SpCloudReg) % 64 == 0 && sizeof(SpCloudReg) == 512, "SpCloudReg is padded to a multiple of 64 bytes");
-#else
-_Static_assert(sizeof(SpCloudReg) % 64 == 0 && sizeof(SpCloudReg) == 512, "SpCloudReg is padded to a multiple of 64 bytes");
-#endif
+SP_ABI_SIZE(SpCloudReg, 512)
+SP_ABI_ASSERT(sizeof(SpCloudReg) % 64 == 0, "SpCloudReg is padded to a multiple of 64 bytes")
 int sp_cloud_register_work_doubles(long long Qa);
 int sp_cloud_register(const float* queries, const float* normals, long long Qa, long long Q, const void* grid_scratch, int residual,
                       int with_scale, double huber, double tol, long long min_pairs, int max_iters, SpCloudReg* state, double* history,
@@ -1677,7 +1707,7 @@ int sp_cloud_register(const float* queries, const float* normals, long long Qa, 
 int sp_tsdf_integrate(const float* depth, const float* images, const SpView* views, int V, int H, int W, int nx, int ny, int nz, float voxel,
                       float ox, float oy, float oz, float trunc, float z_min, float depth_max, float* tsdf, float* weight, float* colour,
                       void* stream);
-long long int sp_tsdf_mesh_scratch_bytes(int nx, int ny, int nz);
+long long sp_tsdf_mesh_scratch_bytes(int nx, int ny, int nz);
 int sp_tsdf_mesh(const float* tsdf, const float* weight, const float* colour, int nx, int ny, int nz, float voxel, float ox, float oy, float oz,
                  float min_weight, void* scratch, long long max_vertices, long long max_faces, float* vertices, float* vertex_colours,
                  int32_t* faces, long long* n_out, void* stream);

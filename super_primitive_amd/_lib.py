@@ -131,7 +131,7 @@ SP_LM_STATE_FLOATS = 8
 
 
 class SpPair(ctypes.Structure):
-    """Mirror of ``struct SpPair`` (include/sp_hip.h); 136 bytes."""
+    """Mirror of ``struct SpPair`` (include/sp_hip.h)."""
     _fields_ = [
         ("pix", c_void_p), ("src4", c_void_p), ("kp_L", c_void_p), ("trg3", c_void_p),
         ("kld", c_void_p), ("pose", c_void_p), ("aff", c_void_p), ("seg_tile_off", c_void_p),
@@ -179,7 +179,7 @@ class SpPrepImage(ctypes.Structure):
 
 
 class SpPrepImagePack(ctypes.Structure):
-    """Mirror of ``struct SpPrepImagePack`` (include/sp_hip.h): a pyramid step with the packed forms of its input / output level; 40 bytes."""
+    """Mirror of ``struct SpPrepImagePack`` (include/sp_hip.h): a pyramid step with the packed forms of its input / output level."""
     _fields_ = [("inp", c_void_p), ("out", c_void_p), ("packed_in", c_void_p), ("packed_out", c_void_p), ("H", c_int), ("W", c_int)]
 
 
@@ -228,7 +228,7 @@ class SpQueue(ctypes.Structure):
 
 
 class SpWindowGn(ctypes.Structure):
-    """Mirror of ``struct SpWindowGn`` (include/sp_hip.h): one window of a multi-window Gauss-Newton run; 136 bytes."""
+    """Mirror of ``struct SpWindowGn`` (include/sp_hip.h): one window of a multi-window Gauss-Newton run."""
     _fields_ = [("pairs", c_void_p), ("chunks", c_void_p), ("spans", c_void_p), ("edges", c_void_p), ("nodes", c_void_p), ("blocks", c_void_p),
                 ("span_partials", c_void_p), ("seg_partials", c_void_p), ("scratch", c_void_p), ("nodes_backup", c_void_p), ("kld_backup", c_void_p),
                 ("state", c_void_p), ("losses", c_void_p), ("n_spans", c_int), ("n_edges", c_int), ("n_nodes", c_int), ("n_blocks", c_int),
@@ -245,14 +245,14 @@ class SpChainPhase(ctypes.Structure):
 
 
 class SpChainWindow(ctypes.Structure):
-    """Mirror of ``struct SpChainWindow`` (include/sp_hip.h): a built window with its Gauss-Newton schedule; 680 bytes."""
+    """Mirror of ``struct SpChainWindow`` (include/sp_hip.h): a built window with its Gauss-Newton schedule."""
     _fields_ = [("gn", SpWindowGn * SP_CHAIN_LEVELS), ("phase", SpChainPhase * SP_CHAIN_PHASES), ("n_phases", c_int), ("check_every", c_int),
                 ("flags", c_int), ("lam0", c_float), ("lm_up", c_float), ("lm_down", c_float), ("lm_min", c_float), ("check_first", c_int),
                 ("state_host", c_void_p)]
 
 
 class SpChainTarget(ctypes.Structure):
-    """Mirror of ``struct SpChainTarget``; 56 bytes."""
+    """Mirror of ``struct SpChainTarget``."""
     _fields_ = [("packed", c_void_p * SP_CHAIN_LEVELS), ("pose", c_void_p), ("aff", c_void_p), ("node", c_int), ("pad_", c_int)]
 
 
@@ -269,28 +269,27 @@ class SpChainStep(ctypes.Structure):
 
 
 class SpCamera(ctypes.Structure):
-    """Mirror of ``struct SpCamera`` (include/sp_hip.h): pinhole intrinsics and OpenCV's distortion coefficients; 96 bytes, host memory."""
+    """Mirror of ``struct SpCamera`` (include/sp_hip.h): pinhole intrinsics and OpenCV's distortion coefficients; host memory."""
     _fields_ = [(name, ctypes.c_double) for name in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")]
 
 
-SP_TRAJ_ALIGN_DOUBLES = 32
-
-
 class SpTrajAlign(ctypes.Structure):
-    """Mirror of ``struct SpTrajAlign`` (include/sp_hip.h): the similarity alignment of one trajectory; 256 bytes, device memory."""
+    """Mirror of ``struct SpTrajAlign`` (include/sp_hip.h): the similarity alignment of one trajectory; device memory."""
     _fields_ = [("rot", ctypes.c_double * 9), ("trans_scaled", ctypes.c_double * 3), ("trans", ctypes.c_double * 3), ("s", ctypes.c_double),
                 ("rot_reanchor", ctypes.c_double * 9), ("ate_scaled", ctypes.c_double), ("ate", ctypes.c_double), ("dots", ctypes.c_double),
                 ("norms", ctypes.c_double), ("sigma", ctypes.c_double * 3)]
 
 
+SP_TRAJ_ALIGN_DOUBLES = ctypes.sizeof(SpTrajAlign) // 8      # the record as a float64 tensor
+
+
 class SpMapKeyframe(ctypes.Structure):
-    """Mirror of ``struct SpMapKeyframe`` (include/sp_hip.h): one keyframe of a world-map launch; 96 bytes, device memory."""
+    """Mirror of ``struct SpMapKeyframe`` (include/sp_hip.h): one keyframe of a world-map launch; device memory."""
     _fields_ = [("pix", c_void_p), ("baseL", c_void_p), ("seg_off", c_void_p), ("kp_L", c_void_p), ("kld", c_void_p), ("image", c_void_p),
                 ("K", c_void_p), ("pose", c_void_p), ("N", c_int), ("P", c_int), ("H", c_int), ("W", c_int), ("out_offset", ctypes.c_longlong),
                 ("align", c_int), ("first_block", c_int)]
 
 
-SP_VIEW_FLOATS = 25
 SP_MAP_FUSE_MAX_POINTS = 1 << 28
 SP_CLOUD_GRID_MAX_POINTS = 1 << 28
 SP_CLOUD_KNN_MAX = 32
@@ -302,7 +301,7 @@ SP_CLOUD_REG_WORK_DOUBLES = 40
 
 
 class SpCloudReg(ctypes.Structure):
-    """Mirror of ``struct SpCloudReg`` (include/sp_hip.h): the state of one registration; 512 bytes, device memory (64 float64 words:
+    """Mirror of ``struct SpCloudReg`` (include/sp_hip.h): the state of one registration; device memory (64 float64 words:
     rot 0..8, trans 9..11, s 12, H 13..40, g 41..47, delta 48..54, cost 55, step 56, n 57 as int64, status and iterations the two int32
     of word 58)."""
     _fields_ = [("rot", ctypes.c_double * 9), ("trans", ctypes.c_double * 3), ("s", ctypes.c_double), ("H", ctypes.c_double * 28),
@@ -311,12 +310,15 @@ class SpCloudReg(ctypes.Structure):
 
 
 class SpView(ctypes.Structure):
-    """Mirror of ``struct SpView`` (include/sp_hip.h): one camera of sp_render_views; 100 bytes, device memory (a (V, 25) float32 tensor)."""
+    """Mirror of ``struct SpView`` (include/sp_hip.h): one camera of sp_render_views; device memory (a (V, SP_VIEW_FLOATS) float32 tensor)."""
     _fields_ = [("K", c_float * 9), ("pose", c_float * 16)]
 
 
+SP_VIEW_FLOATS = ctypes.sizeof(SpView) // 4
+
+
 class SpWindowNode(ctypes.Structure):
-    """Mirror of ``struct SpWindowNode`` (include/sp_hip.h); 176 bytes."""
+    """Mirror of ``struct SpWindowNode`` (include/sp_hip.h)."""
     _fields_ = [("T", c_float * 16), ("a", c_float * 6), ("m", c_float * 6), ("v", c_float * 6), ("aff", c_float * 2),
                 ("aff_m", c_float * 2), ("aff_v", c_float * 2), ("lr_pose", c_float), ("lr_aff", c_float),
                 ("kind", c_int), ("flags", c_int)]

@@ -23,9 +23,6 @@
 
 #define SP_CHAIN_STATE 16   // floats of a window's LM state (sp_window_gn_step)
 
-static_assert(sizeof(SpChainPhase) == 16 && sizeof(SpChainWindow) == 680 && sizeof(SpChainTarget) == 56 && sizeof(SpChainStep) == 1752,
-              "SpChain* layouts are part of the ABI (super_primitive_amd/_lib.py mirrors them)");
-
 namespace {
 
 struct ChainSeq {                      // per record: what the small kernels of the chain read

@@ -18,8 +18,6 @@
 #include <math.h>
 #include "sp_map_device.h"
 
-static_assert(sizeof(SpTrajAlign) == 256 && sizeof(SpMapKeyframe) == 96, "result records are part of the ABI");
-
 namespace {
 
 // every thread ends up with the block's totals of its NV accumulators; red: SP_WAVES * NV doubles of LDS

@@ -17,9 +17,6 @@ __global__ __launch_bounds__(SP_BLOCK) void k_pairs_gn(const SpPair* __restrict_
     solve_gn(pairs, blockIdx.x, partials, seg_partials, h);
 }
 
-static_assert(sizeof(SpPhase) == 64 && sizeof(SpSchedule) == 800 && sizeof(SpVerdict) == 104 && sizeof(SpQueue) == 296 && sizeof(SpPair) == 136,
-              "SpSchedule / SpVerdict / SpQueue / SpPair are part of the ABI");
-
 // per-pair schedules: the pair's current phase selects the level descriptors, the partial records of that level's work list,
 // the convergence threshold and the iteration budget.
 // THE VERDICT (SpVerdict, v.status != NULL): the workgroup that takes a pair out of its last phase looks at what it ended with --

@@ -19,8 +19,6 @@
 
 #pragma clang fp contract(off)
 
-static_assert(sizeof(SpView) == 100 && sizeof(SpMapKeyframe) == 96 && sizeof(SpTrajAlign) == 256, "the records are part of the ABI");
-
 namespace {
 
 // the first table point of [lo, hi) whose pixel word (validity bit masked off) is at or beyond `want`: hi if there is none

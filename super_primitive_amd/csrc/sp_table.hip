@@ -1416,8 +1416,6 @@ int chain_pyramid_multi(const ChainImgJob* jobs_dev, int n, int n_levels, int H,
 
 extern "C" {
 
-static_assert(sizeof(SpPrepTable) == 240 && sizeof(SpPrepSample) == 176 && sizeof(SpPrepImage) == 24, "preparation job records are part of the ABI");
-
 // ---- batched preparation ----
 static int check_grid(long x, long y) { return (x <= 0 || y <= 0 || y > 65535) ? SP_EINVAL : 0; }
 

@@ -44,8 +44,6 @@
 
 #pragma clang fp contract(off)
 
-static_assert(sizeof(SpView) == 100, "view records are part of the ABI");
-
 namespace {
 
 // the radii of a workgroup's points: LDS that only the footprint instantiation of k_view_keys has

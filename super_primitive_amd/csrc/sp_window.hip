@@ -21,8 +21,6 @@
 
 namespace {
 
-static_assert(sizeof(SpWindowNode) == 176 && sizeof(SpWindowEdge) == 16 && sizeof(SpWindowBlock) == 32, "window structs are part of the ABI");
-
 #define SP_WIN_REC 28            // doubles per edge record, followed by max_N per-segment sums
 #define SP_WIN_MAX_EDGES 1024
 #define SP_WIN_LDS_EDGES 96      // windows up to this many edges / 64 nodes are staged in LDS (records, edge list, slot

@@ -74,24 +74,16 @@ def test_huber_in_the_reference_ends_closer_to_the_truth(kind):
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------------------------
 def test_symbols_struct_size_and_the_abi_version_stays():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
     from super_primitive_amd import _lib
     header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name, n_args in (("sp_cloud_register_work_doubles", 1), ("sp_cloud_register", 16)):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", header)
-        assert decl and len(decl.group(1).split(",")) == n_args == len(_lib.SIGNATURES[name]), name
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
-    assert ctypes.sizeof(_lib.SpCloudReg) == 512 and ctypes.sizeof(_lib.SpCloudReg) % 64 == 0
+    for name in ("sp_cloud_register_work_doubles", "sp_cloud_register"):
+        assert name in _lib.SIGNATURES, name
+    assert ctypes.sizeof(_lib.SpCloudReg) % 64 == 0
     assert "sizeof(SpCloudReg) % 64 == 0" in header and "TWO RUNS GIVE THE SAME BITS" in header
-    body = re.search(r"typedef struct SpCloudReg \{(.*?)\} SpCloudReg;", header, re.S).group(1)
-    names = re.findall(r"\b(\w+)(?:\[\d+\])?;", body)
-    assert names == [f[0] for f in _lib.SpCloudReg._fields_]
     for k, name in enumerate(("RUNNING", "CONVERGED", "MAX_ITERS", "FEW", "DEGENERATE")):
-        assert int(re.search(r"#define\s+SP_CLOUD_REG_" + name + r"\s+(\d+)", header).group(1)) == k == getattr(_lib, "SP_CLOUD_REG_" + name)
-        assert getattr(ref, name) == k
-    assert int(re.search(r"#define\s+SP_CLOUD_REG_ITERS_LIMIT\s+(\d+)", header).group(1)) == _lib.SP_CLOUD_REG_ITERS_LIMIT
-    assert int(re.search(r"#define\s+SP_CLOUD_REG_WORK_DOUBLES\s+(\d+)", header).group(1)) == _lib.SP_CLOUD_REG_WORK_DOUBLES == 40
+        assert getattr(_lib, "SP_CLOUD_REG_" + name) == k == getattr(ref, name)
+    assert _lib.SP_CLOUD_REG_WORK_DOUBLES == 40
     assert float(re.search(r"#define\s+SP_CLOUD_REG_SMALL_ANGLE2\s+(\S+)", header).group(1)) == ref.SMALL_ANGLE2
 
 

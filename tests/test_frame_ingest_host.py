@@ -3,7 +3,6 @@ analytic pinhole image rendered through the distortion (the direction of the map
 entry points (header / ctypes table / library, every refusal, host tensors refused)."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -138,23 +137,17 @@ def test_depth_restatement_is_numpy_and_interpolate_nearest(shape, margins, size
 
 
 def test_header_ctypes_table_and_library_agree_on_the_new_symbols():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
+    import abi_header
     from super_primitive_amd import _lib
     header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
     for cite in ("data/tum_undistort.py:113", "data/image_transforms.py:36-60", "frontend/process_frame.py:170-189",
                  "frontend/process_frame.py:257-270", "tool/camera.py:13-22", "data/tum_undistort.py:16-36", "odometery/odometery.py:152-156"):
         assert cite in header, cite
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
+    prototypes = abi_header.parse()[0]
     for name in NEW_SYMBOLS:
-        proto = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", code, flags=re.S)
-        assert proto is not None, name
-        assert proto.group(1).count(",") + 1 == len(_lib.SIGNATURES[name]), name
-        assert proto.group(1).strip().endswith("void* stream"), name
-        assert hasattr(lib, name), name
-    fields = re.search(r"typedef struct SpCamera \{(.*?)\} SpCamera;", code, flags=re.S).group(1)
-    names = re.findall(r"\b([a-z][a-z0-9]*)\s*[,;]", fields)
-    assert names == [n for n, _ in _lib.SpCamera._fields_] and len(names) == 12 and ctypes.sizeof(_lib.SpCamera) == 96
-    assert _lib.load().sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
+        assert name in _lib.SIGNATURES and prototypes[name][2][-1] == "stream", name      # (void* stream, last: the rule for every launch)
+    assert len(_lib.SpCamera._fields_) == 12                                   # fx fy cx cy and OpenCV's eight coefficients
 
 
 def test_argument_checks():

@@ -12,73 +12,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
+    """(the types of every prototype, record and constant against the ctypes mirror: tests/test_abi_mirror.py)"""
+    import abi_header
     from super_primitive_amd import _lib
-    header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    declared = set(re.findall(r"\bint\s+(sp_[a-z0-9_]+)\s*\(", header))
-    assert declared, "no prototypes parsed"
-    assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
+    declared = set(abi_header.parse()[0])
+    assert len(declared) > 90, "no prototypes parsed"
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == 20
+    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == 20                   # the one pin of the ABI number
     # (ABI 18: sp_pairs_cost_opt is the one extended cost entry point; ABI 19: no single-launch iterate forms; ABI 20: no test-only forms)
     for retired in ("sp_pairs_cost_active", "sp_pairs_cost_rd", "sp_pairs_cost_rd_active", "sp_pairs_adam_iterate", "sp_pairs_gn_iterate",
                     "sp_kf_criterion", "sp_prepare_blur", "sp_depth_average"):
-        assert not hasattr(lib, retired), retired
-    # argument counts of the ctypes table match the prototypes
-    for name in declared:
-        proto = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", header, flags=re.S).group(1).strip()
-        n = 0 if proto in ("void", "") else proto.count(",") + 1
-        assert n == len(_lib.SIGNATURES[name]), name
-
-
-def test_abi_constants_and_struct_layout_match_header():
-    from super_primitive_amd import _lib
-    header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    for macro in ("SP_ABI_VERSION", "SP_GRAD_PARTIAL_FLOATS", "SP_GN_PARTIAL_FLOATS", "SP_LM_STATE_FLOATS"):
-        val = int(re.search(r"#define\s+" + macro + r"\s+(\d+)", header).group(1))
-        assert getattr(_lib, macro) == val, macro
-    assert ctypes.sizeof(_lib.SpPair) == 136
-    assert _lib.SpPair.K_src.offset == 64 and _lib.SpPair.N.offset == 96 and _lib.SpPair.zmin.offset == 128
-    # window optimiser structs (sizes are static_assert-ed on the device side, sp_window.hip)
-    assert ctypes.sizeof(_lib.SpWindowNode) == 176 and ctypes.sizeof(_lib.SpWindowEdge) == 16 and ctypes.sizeof(_lib.SpWindowBlock) == 32
-    assert _lib.SpWindowNode.a.offset == 64 and _lib.SpWindowNode.aff.offset == 136 and _lib.SpWindowNode.lr_pose.offset == 160
-    assert _lib.SpWindowNode.kind.offset == 168 and _lib.SpWindowBlock.N.offset == 24
-    # per-pair schedule, passed by value
-    assert int(re.search(r"#define\s+SP_MAX_PHASES\s+(\d+)", header).group(1)) == _lib.SP_MAX_PHASES
-    assert ctypes.sizeof(_lib.SpPrepTable) == 240 and _lib.SpPrepTable.bits.offset == 224 and _lib.SpPrepTable.boxes.offset == 232
-    assert ctypes.sizeof(_lib.SpPrepTable) == 240 and ctypes.sizeof(_lib.SpPrepSample) == 176 and ctypes.sizeof(_lib.SpPrepImage) == 24
-    assert _lib.SpPrepTable.stride.offset == 192 and _lib.SpPrepSample.N.offset == 152 and _lib.SpPrepImage.H.offset == 16
-    for macro in ("SP_PREP_MAX_STRIDES", "SP_PREP_MAX_LEVELS"):
-        assert int(re.search(r"#define\s+" + macro + r"\s+(\d+)", header).group(1)) == getattr(_lib, macro)
-    assert ctypes.sizeof(_lib.SpPhase) == 64 and _lib.SpPhase.n_spans.offset == 40 and _lib.SpPhase.conv_tol.offset == 52
-    assert _lib.SpPhase.flags.offset == 56
-    assert _lib.SpPhase.next.offset == 60
-    # (ABI 13: 12 phases, the third attempt's entry, the Adam phases' rates and moments; the within-pair thresholds of the verdict)
-    assert ctypes.sizeof(_lib.SpSchedule) == 800 and _lib.SpSchedule.n_phases.offset == 768 and _lib.SpSchedule.retry_entry.offset == 776
-    assert _lib.SpSchedule.retry2_entry.offset == 780 and _lib.SpSchedule.adam_lr_pose.offset == 784 and _lib.SpSchedule.adam_state.offset == 792
-    assert ctypes.sizeof(_lib.SpVerdict) == 104 and _lib.SpVerdict.evals.offset == 88 and _lib.SpVerdict.seg_product.offset == 96 and _lib.SpVerdict.kld_bound.offset == 56 and _lib.SpVerdict.lam0.offset == 76
-    assert _lib.SpVerdict.seg_max_ratio.offset == 80 and _lib.SpVerdict.seg_mean_ratio.offset == 84
-    assert ctypes.sizeof(_lib.SpQueue) == 296 and _lib.SpQueue.active.offset == 288 and _lib.SpQueue.max_spans.offset == 192 and _lib.SpQueue.head.offset == 248
-    for macro in ("SP_GN_SEG_FLOATS", "SP_GNA_SEG_FLOATS", "SP_PHASE_ADAM", "SP_VERDICT_SEGMENTS", "SP_VERDICT_SEGMENT_POINTS", "SP_VERDICT_MIN_SEGMENTS"):
-        assert int(re.search(r"#define\s+" + macro + r"\s+(\d+)", header).group(1)) == getattr(_lib, macro), macro
-    for macro in ("SP_STATUS_NONFINITE", "SP_STATUS_LAST_CAP", "SP_STATUS_DEPTH_RANGE", "SP_STATUS_COST", "SP_STATUS_VALID", "SP_STATUS_SEGMENTS",
-                  "SP_STATUS_RETRIED", "SP_STATUS_ADAM", "SP_STATUS_UNFINISHED", "SP_DIAG_FLOATS"):
-        assert int(re.search(r"#define\s+" + macro + r"\s+(0x[0-9a-fA-F]+|\d+)", header).group(1), 0) == getattr(_lib, macro), macro
-    assert int(re.search(r"#define\s+SP_PHASE_POSE_ONLY\s+(\d+)", header).group(1)) == _lib.SP_PHASE_POSE_ONLY
-    # (ABI 14: the argument record of sp_chain_step_multi; static_assert-ed in sp_chain.hip)
-    assert ctypes.sizeof(_lib.SpChainPhase) == 16 and ctypes.sizeof(_lib.SpChainWindow) == 680 and ctypes.sizeof(_lib.SpChainTarget) == 56
-    assert ctypes.sizeof(_lib.SpChainStep) == 1752 and _lib.SpChainStep.track.offset == 56 and _lib.SpChainStep.supp.offset == 808
-    assert _lib.SpChainWindow.state_host.offset == 672 and _lib.SpChainWindow.check_first.offset == 668 and _lib.SpChainStep.crit_ws.offset == 1720
-    for macro in ("SP_CHAIN_LEVELS", "SP_CHAIN_PHASES", "SP_CHAIN_TRACK", "SP_CHAIN_SUPP", "SP_CHAIN_CRITERION"):
-        assert int(re.search(r"#define\s+" + macro + r"\s+(\d+)", header).group(1)) == getattr(_lib, macro), macro
-    lib = _lib.load()
-    scratch = ctypes.c_void_p(0x2000)                                      # (never dereferenced: the checks fail first)
-    assert lib.sp_chain_step_multi(None, 1, scratch, scratch, scratch, None) == -1 and lib.sp_kf_criterion_ws_words() == 4 * 256 + 8
-    step = _lib.SpChainStep()
-    # (an all-zero record -- no frame size, no stage's pointers -- is refused before any launch)
-    assert lib.sp_chain_step_multi(ctypes.byref(step), 1, scratch, scratch, scratch, None) == -1
+        assert not hasattr(lib, retired) and retired not in declared, retired
 
 
 def test_new_entry_points_validate_arguments_and_sizes():
@@ -97,6 +43,11 @@ def test_new_entry_points_validate_arguments_and_sizes():
     assert lib.sp_pairs_schedule_gn_step(ctypes.addressof(sched), 1, 1, 8.0, 0.5, 1e-7, *([None] * 7)) == -1
     assert lib.sp_depth_accumulate(*([None] * 6), 1, 1, 1, 1, None, None) == -1
     assert lib.sp_depth_average_finish(None, 4, 4, None, None, None) == -1
+    scratch = ctypes.c_void_p(0x2000)                                      # (never dereferenced: the checks fail first)
+    assert lib.sp_chain_step_multi(None, 1, scratch, scratch, scratch, None) == -1 and lib.sp_kf_criterion_ws_words() == 4 * 256 + 8
+    step = _lib.SpChainStep()
+    # (an all-zero record -- no frame size, no stage's pointers -- is refused before any launch)
+    assert lib.sp_chain_step_multi(ctypes.byref(step), 1, scratch, scratch, scratch, None) == -1
 
 
 def test_work_list_helpers_cover_every_point_once():
@@ -563,7 +514,7 @@ def test_window_gn_scratch_size_and_profile_offset_follow_the_closed_form(E, B, 
 
 
 def test_window_gn_flag_bits_match_the_header():
+    """(that the mirror's values are the header's: tests/test_abi_mirror.py; here, which bits they are)"""
     from super_primitive_amd import _lib
-    header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
     for macro, bit in (("SP_WGN_POSE_ONLY", 1), ("SP_WGN_PREDICTED_EXIT", 2), ("SP_WGN_DEPTHS_FIXED", 4)):
-        assert int(re.search(r"#define\s+" + macro + r"\s+(\d+)", header).group(1)) == getattr(_lib, macro) == bit, macro
+        assert getattr(_lib, macro) == bit, macro

@@ -5,7 +5,6 @@ checks -- made before any device work, so they answer without a GPU --, the argu
 import ctypes
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -15,17 +14,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_symbols_match_the_header_and_the_abi_version_stays():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
     from super_primitive_amd import _lib
     header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    # (sp_map_consistency's signature -- points, owner, Q, views, view_owner, V, depth, H, W, tol, window, z_min, counts, stream -- has 14)
-    for name, n_args in (("sp_keyframe_depths", 9), ("sp_map_consistency", 14)):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", header)
-        assert decl and len(decl.group(1).split(",")) == n_args == len(_lib.SIGNATURES[name]), name
+    for name in ("sp_keyframe_depths", "sp_map_consistency"):
+        assert name in _lib.SIGNATURES, name
     for phrase in ("behind every surface, or between surfaces", "HIGHEST table index", "WRITTEN FOR EVERY ROW"):
         assert phrase in header, phrase                                      # the rules are part of the contract
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
 
 
 def test_keyframe_depths_refuses_bad_arguments_without_a_device():

@@ -4,7 +4,6 @@ their argument checks -- made before any device work, so they answer without a G
 on CPU tensors against a float64 loop, and the reference of tests/map_nearest_ref.py against itself: its three forms agree."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -16,16 +15,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_symbols_match_the_header_and_the_abi_version_stays():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
     from super_primitive_amd import _lib
     header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name, n_args in (("sp_cloud_grid_scratch_units", 1), ("sp_cloud_grid_build", 8), ("sp_cloud_grid_nearest", 9)):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", header)
-        assert decl and len(decl.group(1).split(",")) == n_args == len(_lib.SIGNATURES[name]), name
+    for name in ("sp_cloud_grid_scratch_units", "sp_cloud_grid_build", "sp_cloud_grid_nearest"):
+        assert name in _lib.SIGNATURES, name
     assert "1.0009765625" in header and "lowest row wins" in header and "Why the search is local" in header
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
-    assert int(re.search(r"#define\s+SP_CLOUD_GRID_MAX_POINTS\s+\(1LL << (\d+)\)", header).group(1)) == 28 and _lib.SP_CLOUD_GRID_MAX_POINTS == 1 << 28
+    assert _lib.SP_CLOUD_GRID_MAX_POINTS == 1 << 28
 
 
 def test_scratch_units_and_build_refuse_bad_arguments_without_a_device():

@@ -2,24 +2,16 @@
 any device work, so they answer without a GPU -- and the argument checks of the Python surface (``tool/viz.py``, ``odometery/results.py``
 ``render_map`` / ``score_map``)."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 def test_symbols_and_view_record_match_the_header():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
     from super_primitive_amd import _lib
-    header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    assert re.search(r"}\s*SpView;\s*/\*\s*100 bytes", header)
-    assert ctypes.sizeof(_lib.SpView) == 100 == 4 * _lib.SP_VIEW_FLOATS and _lib.SpView.pose.offset == 36
-    lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in ("sp_render_views", "sp_depth_lift", "sp_depth_lift_blocks"):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
+        assert name in _lib.SIGNATURES, name
 
 
 def test_render_views_refuses_bad_arguments_without_a_device():

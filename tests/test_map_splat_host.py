@@ -4,7 +4,6 @@ checks -- made before any device work, so they answer without a GPU -- and the a
 import ctypes
 import inspect
 import os
-import re
 
 import pytest
 import torch
@@ -13,15 +12,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_symbols_match_the_header_and_the_abi_version_stays():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
     from super_primitive_amd import _lib
     header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name, n_args in (("sp_render_splats", 15), ("sp_image_metrics", 8)):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", header)
-        assert decl and len(decl.group(1).split(",")) == n_args == len(_lib.SIGNATURES[name]), name
+    for name in ("sp_render_splats", "sp_image_metrics"):
+        assert name in _lib.SIGNATURES, name
     assert "NOT when its centre lies inside" in header                      # the cell rule is part of the contract
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
 
 
 def test_render_splats_refuses_bad_arguments_without_a_device():

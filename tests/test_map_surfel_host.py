@@ -5,7 +5,6 @@ feature that are host arithmetic: ``write_ply`` with normals, ``filter_map`` and
 import ctypes
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -15,17 +14,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_symbols_match_the_header_and_the_abi_version_stays():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
     from super_primitive_amd import _lib
     header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name, n_args in (("sp_map_normals", 9), ("sp_render_surfels", 17)):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", header)
-        assert decl and len(decl.group(1).split(",")) == n_args == len(_lib.SIGNATURES[name]), name
+    for name in ("sp_map_normals", "sp_render_surfels"):
+        assert name in _lib.SIGNATURES, name
     assert "strictly increasing" in header and "PRECONDITION" in header          # the table order the neighbour search relies on
     assert "sp_render_splats, bit for bit on every pixel" in header and "sp_render_views in mode 1, bit for bit on every pixel" in header
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
-    assert ctypes.sizeof(_lib.SpMapKeyframe) == 96
 
 
 def test_render_surfels_refuses_bad_arguments_without_a_device():

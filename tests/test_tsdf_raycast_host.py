@@ -4,7 +4,6 @@ depth with normals (0, 0, -1); the seeded views; a hole with a rim of NaN normal
 Python surface on ``meta`` tensors."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -19,15 +18,12 @@ NAN = float("nan")
 
 # ---- ABI and arguments ----------------------------------------------------------------------------------------------------------------------
 def test_the_symbol_matches_the_header_and_the_abi_version_stays():
+    """(the types of every prototype, record and constant against the ctypes mirror, and the ABI number: tests/test_abi_mirror.py)"""
     from super_primitive_amd import _lib
     header = open(os.path.join(ROOT, "include", "sp_hip.h")).read()
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    assert hasattr(lib, "sp_tsdf_raycast") and "sp_tsdf_raycast" in _lib.SIGNATURES
-    decl = re.search(r"\bint\s+sp_tsdf_raycast\s*\(([^;]*)\)\s*;", header)
-    assert decl and len(decl.group(1).split(",")) == 23 == len(_lib.SIGNATURES["sp_tsdf_raycast"])
+    assert "sp_tsdf_raycast" in _lib.SIGNATURES
     assert "sp_tsdf_raycast" not in _lib.RESTYPES and _lib.load().sp_tsdf_raycast.restype is ctypes.c_int
-    assert lib.sp_abi_version() == _lib.SP_ABI_VERSION == int(re.search(r"#define\s+SP_ABI_VERSION\s+(\d+)", header).group(1)) == 20
-    assert _lib.SP_TSDF_RAYCAST_MAX_STEPS == 1 << 20 and re.search(r"#define\s+SP_TSDF_RAYCAST_MAX_STEPS\s+\(1 << 20\)", header)
+    assert _lib.SP_TSDF_RAYCAST_MAX_STEPS == 1 << 20
     assert header.index("int sp_tsdf_mesh(") < header.index("int sp_tsdf_raycast(")
 
 
