@@ -53,27 +53,10 @@ def copy_state(s):
 # SE(3)
 # ---------------------------------------------------------------------------------------------------------------------------------
 def se3_exp(xi):
-    """Exp of the twist [tau, phi] as a 4x4 float64 matrix: the matrix exponential of [[phi^, tau], [0, 0]]."""
-    xi = np.asarray(xi, np.float64)
-    tau, (wx, wy, wz) = xi[:3], xi[3:]
-    X = np.zeros((4, 4))
-    X[:3, :3] = [[0, -wz, wy], [wz, 0, -wx], [-wy, wx, 0]]
-    X[:3, 3] = tau
-    try:
-        from scipy.linalg import expm
-        return expm(X)
-    except ImportError:       # Rodrigues; the series below 1e-4 avoids the cancellation in 1 - cos, theta - sin
-        W = X[:3, :3]
-        t2 = wx * wx + wy * wy + wz * wz
-        if t2 < 1e-8:
-            A, B, C = 1 - t2 / 6 + t2 * t2 / 120, 0.5 - t2 / 24 + t2 * t2 / 720, 1 / 6 - t2 / 120 + t2 * t2 / 5040
-        else:
-            t = np.sqrt(t2)
-            A, B, C = np.sin(t) / t, (1 - np.cos(t)) / t2, (t - np.sin(t)) / (t2 * t)
-        T = np.eye(4)
-        T[:3, :3] = np.eye(3) + A * W + B * W @ W
-        T[:3, 3] = (np.eye(3) + B * W + C * W @ W) @ tau
-        return T
+    """Exp of the twist [tau, phi] as a 4x4 float64 matrix: the matrix exponential of [[phi^, tau], [0, 0]] (tests/se3_ref.py, which holds
+    it against mpmath; no private fall-back with a threshold of its own)."""
+    from se3_ref import exp_se3          # (imported here: se3_ref imports window_gn_step_ref, which imports this module)
+    return exp_se3(np.asarray(xi, np.float64))
 
 
 def retract(pose, xi):

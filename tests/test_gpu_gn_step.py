@@ -29,6 +29,8 @@ Case -> branch
   test_schedule_bookkeeping      iters, leave_phase on the cap (accepted and rejected iteration), by convergence, SpPhase.next, a finished pair
   test_predicted_exit            SP_PHASE_PREDICTED_EXIT (the gain, also in the recompute path), not at lambda = 0.1, not with depth damping
   test_adam_phase                SP_PHASE_ADAM (solve_adam_sched), its cap
+  test_retract_branches          se3_retract_left: the solved twist steered into the 2-term series, the 3-term series and the closed form, from
+                                 the identity pose (every entry at 2 ulp of its own magnitude against tests/se3_ref.py) and from a general one
 """
 import numpy as np
 import pytest
@@ -348,3 +350,59 @@ def test_adam_phase():
     lm = npy(rig.lm_state)
     assert lm[:, 7].tolist() == [3, 3, 3] and lm[:, 1].tolist() == [-1] * 3 and lm[:, 2].tolist() == [3] * 3 and lm[:, 0].tolist() == [2.0] * 3
     assert (npy(rig.backup) == SENTINEL).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# se3_retract_left in each of its branches
+# ---------------------------------------------------------------------------------------------------------------------------------
+H_DIAG = np.array([4.0, 8.0, 16.0, 2.0, 4.0, 8.0])
+DIAG_COLS = 1 + np.array([0, 6, 11, 15, 18, 20])          # H_pp's diagonal in the span record's row-major upper triangle
+
+
+def steered_pair(rng, xi):
+    """A pair whose pose-only step at lambda = 1 is the twist xi (float32 values) to ~1e-12 relative: the pose system is diagonal with
+    dyadic entries and b_p = -(1 + lambda) H_pp xi, all of it in the first span record (every float64 sum exact)."""
+    mid = make_pair(rng, 5, 2, 3)          # lam0 = 2: lambda = 1 at the first step
+    span = mid["rec"]["span"]
+    span[:, 1:28] = 0
+    span[0, DIAG_COLS] = H_DIAG
+    b = -2.0 * H_DIAG * np.asarray(xi, np.float64)
+    assert np.array_equal(b.astype(f32).astype(np.float64), b)
+    span[0, 22:28] = b
+    return mid
+
+
+def retract_branch(phi):
+    t = float(np.dot(phi, phi))
+    return 0 if t < 1e-12 else 1 if t < 1e-4 else 2
+
+
+@pytest.mark.parametrize("start", ["identity", "general"])
+def test_retract_branches(start):
+    """The solved twist lands in each branch of se3_retract_left (theta^2 = 0 with tau != 0, either side of 1e-12, 1e-8, either side of 1e-4,
+    0.3).  From the identity pose the new pose IS Exp(xi), so a wrong series coefficient is not hidden under a unit-size entry: every entry
+    within PAIR_ULPS = 2 ulp of its OWN magnitude of se3_ref.retract (scipy's expm, no branch on theta); an exact zero exactly.  From a
+    general pose: the file's bound (the rig's own comparison, and the same against se3_ref).  Neighbours and every other buffer as always."""
+    import se3_ref
+    from super_primitive_amd import _lib
+    seen, worst = set(), 0.0
+    for k, (name, xi) in enumerate(se3_ref.pair_step_twists()):
+        rng = np.random.default_rng(6000 + k)
+        a, b = neighbours(rng)
+        rig = Rig([a, steered_pair(rng, xi), b], entry="sched", phases=[dict(max_iters=50, flags=_lib.SP_PHASE_POSE_ONLY), dict(max_iters=50)])
+        if start == "identity":
+            rig.poke(1, pose=dict(enumerate(np.eye(4, dtype=f32).ravel())))
+        before = rig.ref[1]["pose"].astype(np.float64)
+        info = rig.step(what=f"retract {name} from {start}")[1]
+        assert info["decision"] == "step" and info["lam"] == 1.0 and not info["active"].any()
+        np.testing.assert_allclose(info["dxi"], xi, rtol=1e-9, atol=0)
+        assert retract_branch(info["dxi"][3:]) == retract_branch(xi[3:]) and (xi[:3] != 0).all()
+        seen.add((retract_branch(xi[3:]), bool(xi[3:].any())))
+        got = npy(rig.pose)[1].reshape(4, 4)
+        want = se3_ref.retract(info["dxi"], before)
+        assert got[3].tolist() == [0, 0, 0, 1]
+        d = se3_ref.own_ulps(got[:3], want[:3]).max()
+        worst = max(worst, d)
+        assert d <= se3_ref.PAIR_ULPS, f"{name} from {start}: {d:.3g} ulp of the entry's own magnitude from Exp(xi) pose"
+    assert seen == {(0, False), (0, True), (1, True), (2, True)}
+    print(f"retract branches from {start}: at most {worst:.3g} ulp (own magnitude) from se3_ref.retract")

@@ -35,12 +35,16 @@ Case -> branch
                         nodes without an edge, a frozen block between free ones, a block no edge names, weights != 1, one NULL SpPair.aff
   test_kind1            a persistent tangent of norm 0, 1e-3, 0.7 at node 0, 31 (Dual<1> through LDS), 32 (Dual<6>) of 34 and at node 40 of 66
                         (unstaged)
+  test_kind1_around_the_series_threshold   a tangent whose rotational theta^2 is 0.5 (1 -+ 2^-20) (se3_exp_times' series | closed forms) and 2, at
+                        node 0 and node 32 of 34
+  test_fold_in_branches fixed kind-0 nodes with preset tangents of theta^2 = 1e-10, 1e-4 (1 -+ 1e-3) (se3_exp_d's series | closed form), 0.3, 9,
+                        from the identity (each entry at 1 ulp of its own magnitude against tests/se3_ref.py) and from general poses
   test_staging_limits   (edges, nodes) = (96, 64) staged | (97, 64), (96, 65) not | (1024, 3); 64 and 66 blocks with their own lr and N in {1,
                         64, 65, 130} (SP_WIN_LDS_BLOCKS, the 4-wave and the 64-lane loops), staged and not; 96x64 and 96x65 agree bitwise
   test_abs_loss_signs   r > 0, < 0, == 0 with and without abs_loss
   test_skip_first_and_counts, test_rel_tol_freeze, test_max_losses   the state machine, records swapped between calls
   test_compose_only     sp_window_compose on the (96, 64) and (97, 64) graphs: nodes untouched, the slots the step leaves
-Measured on an MI355X: the 37 tests of this file take 1.2 s (the slowest case 0.4 s, the first launch), 3.1 s with the pair file and start-up;
+Measured on an MI355X: the 45 tests of this file take 1.5 s (the slowest case 0.4 s, the first launch), 3.4 s with start-up;
 the worst distances are printed at the end of the file.
 """
 import time
@@ -346,6 +350,42 @@ def test_kind1(norm, idx, n_nodes):
     a0 = rig.ref["nodes"][idx]["a"].copy()
     assert rig.run() == ["step"] * 2
     assert (rig.ref["nodes"][idx]["a"] != a0).all(), "the persistent tangent did not move"
+
+
+@pytest.mark.parametrize("theta2,idx,n_nodes", cases.KIND1_THETA2)
+def test_kind1_around_the_series_threshold(theta2, idx, n_nodes):
+    """se3_exp_times on either side of theta^2 = 0.5 and at 2, on Dual<1> (the slots) and Dual<6> (the gradient), with test_kind1's bounds."""
+    rig = Rig(cases.kind1_case(0.3, idx, n_nodes, theta2))
+    a0 = rig.ref["nodes"][idx]["a"].copy()
+    assert ((a0[3:] * a0[3:]).sum(dtype=f32) < 0.5) == (theta2 == "0.5-")
+    assert rig.run() == ["step"] * 2
+    assert (rig.ref["nodes"][idx]["a"] != a0).all(), "the persistent tangent did not move"
+
+
+@pytest.mark.parametrize("identity", [1, 0], ids=["identity", "general"])
+def test_fold_in_branches(identity):
+    """se3_exp_d in its series and in its closed form.  The rig holds every new T to 1 ulp at max(|entry|, 1) of the yardstick; from the
+    identity the new T is Exp(-a) itself and every entry is held to FOLD_ULPS = 1 ulp of its OWN magnitude against se3_ref.exp_se3 (scipy's
+    expm, no branch on theta): a wrong series coefficient is not hidden under a unit-size entry."""
+    import se3_ref
+    rig = Rig(cases.fold_in_case(identity))
+    start = rig.ref["nodes"].copy()
+    assert rig.run() == ["step"]
+    twists = se3_ref.fold_in_twists()
+    assert {bool((a[3:] ** 2).sum() < 1e-4) for _, a in twists} == {True, False}
+    for k, (name, a) in enumerate(twists):
+        nd, nd0 = rig.ref["nodes"][2 + k], start[2 + k]
+        assert bits(nd0["a"]) == bits(a.astype(f32)) and not nd["a"].any() and nd["lr_pose"] == 0
+        want = nd0["T"].astype(np.float64).reshape(4, 4) @ se3_ref.exp_se3(-nd0["a"].astype(np.float64))
+        got = nd["T"].reshape(4, 4)
+        assert bits(got[3]) == bits(nd0["T"][12:])
+        if identity:
+            d = se3_ref.own_ulps(got[:3], want[:3]).max()
+            note("fold-in from the identity (ulp of the entry)", d)
+            assert d <= se3_ref.FOLD_ULPS, f"{name}: {d:.3g} ulp of the entry's own magnitude from Exp(-a)"
+        else:
+            d, sp = pose_ulps(got, want.astype(f32))
+            assert (d <= sp).all(), name
 
 
 @pytest.mark.parametrize("which", cases.STAGING)

@@ -121,23 +121,52 @@ def graph_shapes_case():
 KIND1 = [(norm, idx, n) for norm in (0.0, 1e-3, 0.7) for idx, n in ((0, 34), (31, 34), (32, 34), (40, 66))]
 
 
-def kind1_case(norm, idx, n_nodes):
+# theta^2 of the tangent's rotational part on either side of 0.5, where se3_exp_times leaves its series for the closed forms, and at 2; node
+# 0 (Dual<1> through LDS) and node 32 of 34 (Dual<6>)
+KIND1_THETA2 = [(name, idx, 34) for name in ("0.5-", "0.5+", "2") for idx in (0, 32)]
+THETA2 = {"0.5-": 0.5 * (1 - 2.0 ** -20), "0.5+": 0.5 * (1 + 2.0 ** -20), "2": 2.0}
+
+
+def kind1_case(norm, idx, n_nodes, theta2=None):
     """A kind-1 node with a persistent tangent of the given norm at index idx of n_nodes, the target of two identity-source edges (the SfM
     shape); the two last nodes are kind 0 and joined by an edge; every other node is idle.  The records are the first draw whose kind-1
-    sums cancel by less than 8 (the cap the host file asserts)."""
+    sums cancel by less than 8 (the cap the host file asserts).  theta2 (a key of THETA2): the rotational part has that theta^2 as the
+    kernel sums it in float32 (on the named side of 0.5), the translational part the norm."""
     for seed in range(200):
-        rng = np.random.default_rng([seed, idx, n_nodes, int(norm * 1e4)])
+        rng = np.random.default_rng([seed, idx, n_nodes, int(norm * 1e4)] + ([int(THETA2[theta2] * 1e4)] if theta2 else []))
         nodes = [node_of(rng, "PA") for _ in range(n_nodes)]
         d = rng.standard_normal(6)
-        nodes[idx] = node_of(rng, "PA", kind=1, a=(norm * d / np.linalg.norm(d)).astype(f32))
+        a = (norm * d / np.linalg.norm(d)).astype(f32)
+        if theta2:
+            a = np.concatenate([norm * d[:3] / np.linalg.norm(d[:3]), np.sqrt(THETA2[theta2]) * d[3:] / np.linalg.norm(d[3:])]).astype(f32)
+            t = a[3] * a[3] + a[4] * a[4] + a[5] * a[5]
+            assert abs(float(t) - THETA2[theta2]) <= 4 * np.spacing(f32(t)) and (t < 0.5) == (THETA2[theta2] < 0.5)
+        nodes[idx] = node_of(rng, "PA", kind=1, a=a)
         blocks = [(3, LR_KLD), (2, LR_KLD)]
         edges = [(-1, idx, 0, 1.0), (-1, idx, 1, 0.5), (n_nodes - 2, n_nodes - 1, 1, 1.0)]
         recs = records(rng, edges, blocks, n_tiles=2, rps=1, exact=False)
-        case = Case(f"kind 1, |a|={norm:g}, node {idx} of {n_nodes}", nodes, edges, blocks, [recs, recs], rng, t0=300, exact=False, abs_loss=1)
+        case = Case(f"kind 1, |a|={norm:g}{', theta2=' + theta2 if theta2 else ''}, node {idx} of {n_nodes}", nodes, edges, blocks, [recs, recs], rng, t0=300, exact=False, abs_loss=1)
         gr = case.gradients()
         if (gr["k1_terms"][idx] <= 4 * np.abs(gr["g6"][idx])).all():
             return case
     raise AssertionError("no draw without cancellation")
+
+
+def fold_in_case(identity):
+    """Fixed kind-0 nodes (lr_pose = 0) with a preset tangent each, folded in exactly as given: T <- T Exp(-a) through se3_exp_d, with
+    theta^2 = 1e-10, either side of 1e-4 (its series against its closed form), 0.3 and 9 (se3_ref.fold_in_twists).  identity: every such T
+    is the identity, so that the new T IS Exp(-a) and every entry can be judged at its own magnitude.  Nodes 0 and 1 carry the one edge."""
+    import se3_ref
+    rng = np.random.default_rng(616 + identity)
+    nodes = [node_of(rng, "F"), node_of(rng, "PA")]
+    for _, a in se3_ref.fold_in_twists():
+        nd = node_of(rng, "F", a=a.astype(f32))
+        if identity:
+            nd["T"] = np.eye(4, dtype=f32).ravel()
+        nodes.append(nd)
+    blocks = [(3, LR_KLD)]
+    edges = [(0, 1, 0, 1.0)]
+    return Case(f"fold-in from {'the identity' if identity else 'general poses'}", nodes, edges, blocks, [records(rng, edges, blocks)], rng)
 
 
 STAGING = ["96x64", "97x64", "96x65", "1024x3", "blocks64", "blocks66", "blocks66x65"]
@@ -219,6 +248,8 @@ def all_cases():
     out = [(f"reduction-{n}", lambda n=n: reduction_case(n)) for n in REDUCTION_TILES]
     out.append(("graph_shapes", graph_shapes_case))
     out += [(f"kind1-{norm:g}-{idx}of{n}", lambda a=(norm, idx, n): kind1_case(*a)) for norm, idx, n in KIND1]
+    out += [(f"kind1-theta2={t}-{idx}of{n}", lambda a=(0.3, idx, n, t): kind1_case(*a)) for t, idx, n in KIND1_THETA2]
+    out += [(f"fold_in-{i}", lambda i=i: fold_in_case(i)) for i in (1, 0)]
     out += [(f"staging-{w}", lambda w=w: staging_case(w)) for w in STAGING]
     out += [(f"abs_loss-{a}", lambda a=a: abs_loss_case(a)) for a in (1, 0)]
     out.append(("skip_first", skip_first_case))
