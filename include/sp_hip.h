@@ -1754,6 +1754,66 @@ int sp_tsdf_raycast(const float* tsdf, const float* weight, const float* colour,
                     float min_weight, const SpView* views, int V, int H, int W, float z_start, float step, int n_steps, float* depth,
                     float* normals, uint8_t* image, int32_t* index, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Mesh surfaces (sp_mesh.hip): a triangle list -- sp_tsdf_mesh's, or a ground-truth model's -- as a surface: one record per face, and an
+ * area-uniform, seeded cloud with normals sampled from those records.  Everything runs on the caller's stream without a synchronisation;
+ * argument checks come before any device work; no floating-point atomics, no float prefix sum, no sort: two runs give the same bits.
+ * THE RULE.  Float64 from the float32 inputs, every operation rounded on its own (no fma, no reciprocal); three-term sums as (x + y) + z.
+ *
+ * sp_mesh_faces: one record per face, one thread per face.
+ *     vertices : (M,3) float32;  faces : (F,3) int32
+ *     area     : (F,) float64;  normals : (F,3) float32;  state : (F,) uint8;  cross : (F,3) float64 -- each may be NULL
+ *     summary  : SP_MESH_SUMMARY_WORDS = 6 int64 on the device, zeroed and written by the call: the number of faces of state 0, 1, 2, 3, 4
+ *                (integer atomics: order-free) and, in word 5, the BITS of the largest area as float64 (a maximum over the bit patterns
+ *                of non-negative doubles, which order as the doubles do: order-free too; 0.0 when no face is valid).  The total area is not
+ *                part of the contract: a float64 sum has an order, and the caller forms it
+ * With (i0, i1, i2) the face's indices and p0, p1, p2 their vertices, the state is the first of these that applies:
+ *     1  an index outside [0, M)                   2  two equal indices
+ *     3  a non-finite coordinate among the nine    4  zero area: the area below is not > 0, or not finite
+ *     0  valid
+ *     e1 = p1 - p0,  e2 = p2 - p0  (the differences first);   c = e1 x e2, each component a difference of two products:
+ *     c_x = e1_y e2_z - e1_z e2_y,   c_y = e1_z e2_x - e1_x e2_z,   c_z = e1_x e2_y - e1_y e2_x
+ *     l = sqrt((c_x c_x + c_y c_y) + c_z c_z)  (IEEE square root);   area = 0.5 l;   normal = c / l per component, rounded to float32 once
+ * area, normal and cross (= c) are zeros unless the state is 0.
+ * Null vertices / faces / summary, F or M < 1: SP_EINVAL.  F or M > 2^28 (SP_MESH_MAX_FACES): SP_ELIMIT.  Invalid beats too large.
+ *
+ * sp_mesh_sample: the cloud.  Three launches: a count (one thread per face), one scan workgroup, and -- with a capacity -- a write with
+ * ONE THREAD PER OUTPUT ROW, which finds its face by binary search in the integer offsets: a face of 10^6 rows is 10^6 threads.
+ *     vertices, M, faces, F : the mesh, as above;  vertex_colours : (M,3) float32 or NULL
+ *     area, state : (F,) float64 and uint8, what sp_mesh_faces wrote for this mesh;  face_normals : its normals, or NULL
+ *     density  : samples per unit area, finite and > 0;   seed : any 64 bits
+ *     scratch  : sp_mesh_sample_scratch_units(F) units of 64 bytes, aligned to 8 bytes, initialised by the call: one int64 per face (the
+ *                rows of the faces before it in its 256-face block) and one per 256 faces (the rows before the block), each array a whole
+ *                number of units: 2^25 + 2^17 units at the limit, so the size is an int as those of sp_map_fuse and sp_cloud_grid_build are
+ *     points, normals, colours : (capacity,3) float32;  face : (capacity,) int32 -- CAPACITY buffers: rows at or beyond the capacity are
+ *                never written.  points is NULL iff capacity = 0; normals, colours and face are optional with a capacity and NULL without;
+ *                normals needs face_normals, colours needs vertex_colours.  Every output NULL and capacity 0 is the counting call
+ *     n_out    : one int64 on the device, always written: the true number of rows.  Should it exceed 2^31 - 1, no row is written
+ * mix is the splitmix64 finaliser (x ^= x >> 30, x *= 0xbf58476d1ce4e5b9, x ^= x >> 27, x *= 0x94d049bb133111eb, x ^= x >> 31), all
+ * integer arithmetic is modulo 2^64, and  A(x) = mix(x) >> 11  (53 bits),  U(x) = float64(A(x)) * 2^-53  in [0, 1), exact.
+ * Face i:  h = seed + 0x9E3779B97F4A7C15 * (i + 1).  Its number of rows is
+ *     t = area_i * density, and t = 2^31 unless t < 2^31;   n_i = floor(t + U(h))   (the product and the sum each rounded)
+ * and n_i = 0 for a face whose state is not 0 -- or one of whose indices is outside [0, M), whatever its state says: a record of
+ * sp_mesh_faces never differs there, the test only keeps a foreign record from reading beyond the vertices.  So |n_i - area_i density| < 1
+ * for every face below the clamp (= 1 only where the rounded sum lands on an integer the exact one stays below): stochastic rounding, unbiased.
+ * Rows are ordered by (face, k), k = 0 .. n_i - 1: the first row of face i is the exclusive int64 prefix sum of n.  Row k of face i:
+ *     a1 = A(h + 1 + 2k),  a2 = A(h + 2 + 2k);  if a1 + a2 > 2^53 (the exact integer sum), both become 2^53 - a;  u = float64(a) * 2^-53:
+ *     u1 + u2 > 1 folds the point back into the triangle by u -> 1 - u, exactly, and 1 - u1 - u2 >= 0 afterwards
+ *     points, per axis   (p0 + u1 * (p1 - p0)) + u2 * (p2 - p0),  rounded to float32 once;   colours the same from the vertices' colours
+ *     normals = face_normals[i];   face = i
+ * Null vertices / faces / area / state / scratch / n_out, a scratch not aligned to 8 bytes, F or M < 1, a negative capacity, density not
+ * finite or not > 0, points NULL with a capacity > 0 or the reverse, another output with capacity 0, normals without face_normals,
+ * colours without vertex_colours: SP_EINVAL.  F or M > 2^28, a capacity > 2^31 - 1: SP_ELIMIT.  Invalid beats too large.
+ * sp_mesh_sample_scratch_units answers F < 1 and F > 2^28 with the same codes. */
+#define SP_MESH_MAX_FACES (1LL << 28)
+#define SP_MESH_SUMMARY_WORDS 6
+int sp_mesh_faces(const float* vertices, long long M, const int32_t* faces, long long F, double* area, float* normals, uint8_t* state,
+                  double* cross, long long* summary, void* stream);
+int sp_mesh_sample_scratch_units(long long F);
+int sp_mesh_sample(const float* vertices, const float* vertex_colours, long long M, const int32_t* faces, long long F, const double* area,
+                   const float* face_normals, const uint8_t* state, double density, long long seed, void* scratch, long long capacity,
+                   float* points, float* normals, float* colours, int32_t* face, long long* n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

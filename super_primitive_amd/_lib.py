@@ -115,6 +115,9 @@ SIGNATURES = {
     "sp_tsdf_mesh_scratch_bytes": [I, I, I],
     "sp_tsdf_mesh": [P, P, P, I, I, I, F, F, F, F, F, P, ctypes.c_longlong, ctypes.c_longlong, P, P, P, P, P],
     "sp_tsdf_raycast": [P, P, P, I, I, I, F, F, F, F, F, P, I, I, I, F, F, I, P, P, P, P, P],
+    "sp_mesh_faces": [P, ctypes.c_longlong, P, ctypes.c_longlong, P, P, P, P, P, P],
+    "sp_mesh_sample_scratch_units": [ctypes.c_longlong],
+    "sp_mesh_sample": [P, P, ctypes.c_longlong, P, ctypes.c_longlong, P, P, P, ctypes.c_double, ctypes.c_longlong, P, ctypes.c_longlong, P, P, P, P, P, P],
 }
 
 # the entry points that do not return an int
@@ -295,6 +298,8 @@ SP_CLOUD_GRID_MAX_POINTS = 1 << 28
 SP_CLOUD_KNN_MAX = 32
 SP_TSDF_MAX_NODES = 1 << 30
 SP_TSDF_RAYCAST_MAX_STEPS = 1 << 20
+SP_MESH_MAX_FACES = 1 << 28
+SP_MESH_SUMMARY_WORDS = 6
 SP_CLOUD_REG_RUNNING, SP_CLOUD_REG_CONVERGED, SP_CLOUD_REG_MAX_ITERS, SP_CLOUD_REG_FEW, SP_CLOUD_REG_DEGENERATE = range(5)
 SP_CLOUD_REG_ITERS_LIMIT = 4096
 SP_CLOUD_REG_WORK_DOUBLES = 40

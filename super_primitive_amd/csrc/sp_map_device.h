@@ -1,4 +1,4 @@
-// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip, sp_register.hip, sp_tsdf.hip, sp_raycast.hip): each idiom has its one definition here.
+// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip, sp_register.hip, sp_tsdf.hip, sp_raycast.hip, sp_mesh.hip): each idiom has its one definition here.
 #pragma once
 #include "sp_device.h"
 
@@ -81,6 +81,48 @@ __device__ __forceinline__ long long block_count_scan(int32_t* __restrict__ bc, 
         const int c = bc[j];
         bc[j] = (int32_t)run;
         at_block(j, run);
+        run += c;
+    }
+    return part[SP_BLOCK - 1];
+}
+
+// The int64 forms of the two (sp_mesh.hip: one face may keep 2^31 rows, a block of faces 2^39): the same shapes and the same
+// conditions, counts and prefixes carried in 64 bits throughout.  wc: SP_WAVES long longs of LDS
+struct BlockRank64 { long long rank, count; };
+__device__ __forceinline__ BlockRank64 block_prefix64(long long count, long long* wc) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long incl = count;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const long long up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) wc[wave] = incl;
+    __syncthreads();
+    BlockRank64 r = {incl - count, (wc[0] + wc[1]) + (wc[2] + wc[3])};
+    for (int w = 0; w < wave; ++w) r.rank += wc[w];
+    return r;
+}
+
+// bc[n] (int64) becomes its exclusive prefix sum, in place; every thread gets the total.  part: SP_BLOCK long longs of LDS
+__device__ __forceinline__ long long block_count_scan64(long long* __restrict__ bc, long long n, long long* part) {
+    const int tid = threadIdx.x;
+    const long long per = (n + SP_BLOCK - 1) / SP_BLOCK;
+    const long long j0 = (long long)tid * per < n ? (long long)tid * per : n;
+    const long long j1 = j0 + per < n ? j0 + per : n;
+    long long s = 0;
+    for (long long j = j0; j < j1; ++j) s += bc[j];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        long long run = 0;
+        for (int t = 0; t < SP_BLOCK; ++t) { run += part[t]; part[t] = run; }    // inclusive over the threads' ranges
+    }
+    __syncthreads();
+    long long run = part[tid] - s;
+    for (long long j = j0; j < j1; ++j) {
+        const long long c = bc[j];
+        bc[j] = run;
         run += c;
     }
     return part[SP_BLOCK - 1];

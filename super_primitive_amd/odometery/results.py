@@ -36,7 +36,12 @@
                       the zero crossing, normals from the field's gradient, interpolated colour, the cell behind the surface;
                       ``score_surface`` / ``score_surface_images`` score those views against ground-truth depth and real images, as
                       ``score_map`` / ``score_map_images`` score the points (the scoring tails are shared).
-``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file; a mesh's faces too."""
+``sample_mesh``       a mesh -- ``extract_mesh``'s, or a ground-truth model's -- as a surface: an area-uniform, seeded cloud with exact
+                      normals (``sp_mesh_faces`` / ``sp_mesh_sample``) that every function above takes; ``mesh_faces`` is the record per
+                      face, ``clean_mesh`` drops degenerate triangles, ``mesh_normals`` gives area-weighted vertex normals and
+                      ``mesh_distance`` scores surface against surface, both meshes sampled at one density.
+``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file; a mesh's faces too;
+                      ``read_ply`` is its inverse, for binary and ASCII files of triangles."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -473,7 +478,11 @@ def fused_normals(normals, label, M):
             or tuple(label.shape) != (normals.shape[0],):
         raise ValueError("fused_normals: normals must be float32 (Q,3) with one label per row")
     q = torch.round(torch.nan_to_num(normals.detach().double(), nan=0.0, posinf=0.0, neginf=0.0) * _NORMAL_SCALE).to(torch.int32)
-    S = _pool(label.to(q.device), int(M), q).double()                                  # (|S| <= members * 2^20: exact in float64)
+    return _unit_rows(_pool(label.to(q.device), int(M), q).double())                   # (|S| <= members * 2^20: exact in float64)
+
+
+def _unit_rows(S):
+    """Integer sums S (M,3) as float64, normalised: ``S / sqrt((S0 S0 + S1 S1) + S2 S2)`` rounded to float32 once; a zero sum stays 0."""
     length = torch.sqrt((S[:, 0] * S[:, 0] + S[:, 1] * S[:, 1]) + S[:, 2] * S[:, 2])
     unit = S / torch.where(length > 0, length, torch.ones_like(length))[:, None]
     return unit.float()
@@ -828,6 +837,175 @@ def extract_mesh(volume, min_weight=1.0):
     return dict(points=points, colours=colours, faces=found['faces'], kf_index=none, seg_ids=none.clone(), offsets=np.array([0, M], dtype=np.int64))
 
 
+def _mesh_parts(mesh, what):
+    """(points (M,3) float32, faces (F,3) int32) of a mesh dict -- ``extract_mesh``'s, ``read_ply``'s or ``clean_mesh``'s."""
+    pts = mesh.get('points') if isinstance(mesh, dict) else None
+    faces = mesh.get('faces') if isinstance(mesh, dict) else None
+    if not torch.is_tensor(pts) or pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"{what}: mesh['points'] must be a float32 (M,3) tensor")
+    if not torch.is_tensor(faces) or faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: mesh['faces'] must be an int32 (F,3) tensor")
+    if faces.device != pts.device:
+        raise ValueError(f"{what}: points on {pts.device}, faces on {faces.device}")
+    if pts.shape[0] < 1 or faces.shape[0] < 1:
+        raise ValueError(f"{what}: a mesh of {int(pts.shape[0])} vertices and {int(faces.shape[0])} faces")
+    return pts, faces
+
+
+def _face_records(mesh, records, what, cross=False):
+    """``records`` checked against the mesh, or ``mesh_faces(mesh)``."""
+    pts, faces = _mesh_parts(mesh, what)
+    if records is None:
+        return mesh_faces(mesh, cross=cross)
+    F = int(faces.shape[0])
+    need = ('area', 'normals', 'state', 'area_max') + (('cross',) if cross else ())
+    if not isinstance(records, dict) or any(not torch.is_tensor(records.get(k)) for k in need):
+        raise ValueError(f"{what}: records must be what mesh_faces{'(mesh, cross=True)' if cross else ''} returned (tensors {need})")
+    if tuple(records['state'].shape) != (F,) or records['state'].dtype != torch.uint8 or tuple(records['area'].shape) != (F,) \
+            or (cross and (tuple(records['cross'].shape) != (F, 3) or records['cross'].dtype != torch.float64)):
+        raise ValueError(f"{what}: records of another mesh ({F} faces here)")
+    return records
+
+
+def mesh_faces(mesh, cross=False):
+    """One record per face of a mesh dict (``points`` (M,3) float32, ``faces`` (F,3) int32): ONE ``sp_mesh_faces`` launch
+    (``tool.viz.mesh_faces``; include/sp_hip.h has the rule).  Returns ``dict(area (F,) float64, normals (F,3) float32, state (F,) uint8 --
+    0 valid, 1 an index outside the vertices, 2 a repeated index, 3 a non-finite coordinate, 4 zero area --, counts (5,) int64 (faces per
+    state), area_max, area_total (0-dim float64))`` and, with ``cross``, the raw cross products (F,3) float64.  ``area_total`` is the
+    ``torch.sum`` of ``area``: the one figure here whose last bits depend on the order of a sum.  No synchronisation."""
+    from ..tool import viz
+    pts, faces = _mesh_parts(mesh, "mesh_faces")
+    found = viz.mesh_faces(pts, faces, cross=cross)
+    summary = found.pop('summary')
+    found.update(counts=summary[:5], area_max=summary[5:].view(torch.float64)[0], area_total=torch.sum(found['area']))
+    return found
+
+
+def clean_mesh(mesh, records=None):
+    """``mesh`` without its degenerate triangles: the faces whose state is not 0 dropped (``mesh_faces``; ``records``: what it returned
+    for this mesh, reused), then the vertices no kept face references; the order of both is preserved and duplicate positions are not
+    welded.  Plain torch over ``state`` (boolean selection and a cumulative sum for the new indices): with ``records`` it runs on CPU
+    tensors too.  Returns a NEW dict: ``points``, ``colours``, ``normals`` (when present), ``faces`` (re-indexed, int32), ``kept_vertices``
+    and ``kept_faces`` (int64: the surviving rows of the input), and ``kf_index`` / ``seg_ids`` = -1, ``offsets`` = [0, M'] as
+    ``extract_mesh`` forms them.  Two host reads on the device: the sizes of the two boolean selections."""
+    pts, faces = _mesh_parts(mesh, "clean_mesh")
+    state = _face_records(mesh, records, "clean_mesh")['state'].to(pts.device)
+    M = int(pts.shape[0])
+    kept_faces = torch.nonzero(state == 0).reshape(-1)
+    kept = faces[kept_faces].long()                                                    # (state 0: every index is inside the vertices)
+    used = torch.zeros(M, dtype=torch.bool, device=pts.device)
+    used[kept.reshape(-1)] = True
+    new_index = torch.cumsum(used.long(), dim=0) - 1
+    kept_vertices = torch.nonzero(used).reshape(-1)
+    Mk = int(kept_vertices.shape[0])
+    out = dict(points=pts[kept_vertices], faces=new_index[kept].to(torch.int32), kept_vertices=kept_vertices, kept_faces=kept_faces)
+    for key in ('colours', 'normals'):
+        if mesh.get(key) is not None:
+            if not torch.is_tensor(mesh[key]) or tuple(mesh[key].shape) != (M, 3):
+                raise ValueError(f"clean_mesh: mesh['{key}'] must be a tensor ({M},3)")
+            out[key] = mesh[key][kept_vertices]
+    none = torch.full((Mk,), -1, dtype=torch.int32, device=pts.device)
+    out.update(kf_index=none, seg_ids=none.clone(), offsets=np.array([0, Mk], dtype=np.int64))
+    return out
+
+
+_CROSS_SCALE = 2.0 ** 30           # mesh_normals: face cross products are summed as int64 round(c * (2^30 / c_max))
+
+
+def mesh_normals(mesh, records=None):
+    """Area-weighted vertex normals, bitwise repeatable: a NEW dict, ``mesh`` plus ``'normals'`` (M,3) float32.  Per valid face its cross
+    product c (``mesh_faces(mesh, cross=True)``, or ``records``: what that returned, reused -- then CPU tensors work too), whose length is
+    twice the face's area, is quantised per component to int64 ``q = round(c * (2^30 / c_max))`` (float64, ties to even; ``c_max = 2
+    area_max``, so |q| <= 2^30), summed per vertex over the face's three corners by ``pool_map``'s integer ``index_add_`` -- exact in
+    any order --, and the sum is normalised in float64 exactly as ``fused_normals`` does; a vertex of no valid face keeps (0, 0, 0).
+    Faces look into free space (``extract_mesh``), so do the normals.  No host read."""
+    pts, faces = _mesh_parts(mesh, "mesh_normals")
+    rec = _face_records(mesh, records, "mesh_normals", cross=True)
+    dev = pts.device
+    c_max = 2.0 * rec['area_max'].to(dev).double()
+    scale = torch.where(c_max > 0, _CROSS_SCALE / torch.where(c_max > 0, c_max, torch.ones_like(c_max)), torch.zeros_like(c_max))
+    q = torch.round(rec['cross'].to(dev) * scale).to(torch.int64)
+    valid = (rec['state'].to(dev) == 0)[:, None]
+    label = torch.where(valid, faces.long(), torch.full_like(faces, -1, dtype=torch.int64)).t().reshape(-1)     # corner 0 of every face, then 1, then 2
+    out = dict(mesh)
+    out['normals'] = _unit_rows(_pool(label, int(pts.shape[0]), q.repeat(3, 1)).double())
+    return out
+
+
+def _n_or_density(n, density, what):
+    if (n is None) == (density is None):
+        raise ValueError(f"{what}: exactly one of n and density must be given")
+    try:
+        if n is not None:
+            if int(n) != n or int(n) < 1:
+                raise ValueError("n must be a whole number >= 1")
+            return int(n), None
+        density = float(density)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: n {n!r}, density {density!r}: {e}") from None
+    if not (0.0 < density < float("inf")):
+        raise ValueError(f"{what}: density {density} (finite, > 0)")
+    return None, density
+
+
+def _density_of(n, records, what):
+    """``n`` samples over the records' total area: one host read."""
+    total = float(records['area_total'])
+    if not (0.0 < total < float("inf")):
+        raise ValueError(f"{what}: a mesh of total area {total} cannot take n = {n} samples")
+    return n / total
+
+
+def sample_mesh(mesh, n=None, density=None, seed=0, records=None):
+    """The mesh as an area-uniform cloud with exact normals: ``mesh_faces`` then ``tool.viz.mesh_sample`` (``sp_mesh_sample``;
+    include/sp_hip.h has the rule): every valid face i takes ``floor(area_i density + U_i)`` samples -- stochastic rounding by the
+    face's own seeded hash, so a long flat triangle takes its share and a small one its chance --, each a seeded uniform point of the
+    triangle, with the face's unit normal and the interpolated vertex colour.  Exactly one of ``density`` (samples per unit area) and
+    ``n`` must be given; ``n`` means ``density = n / area_total``, which costs ONE MORE host read, and the row count is then ``n`` give or
+    take the stochastic rounding (a standard deviation of at most sqrt(F) / 2), not ``n`` exactly.  The same mesh, density and ``seed`` (any 64
+    bits) give the same bits.  ``records``: what ``mesh_faces`` returned for this mesh, reused.  Returns a world dict -- ``points``,
+    ``colours`` (zeros without vertex colours), ``normals`` (N,3) float32, ``face`` (N,) int32 (the row of ``mesh['faces']``),
+    ``kf_index`` / ``seg_ids`` (N,) int32 = -1, ``offsets`` = [0, N] -- that ``map_distance``, ``register_map`` (which then picks the
+    ``'plane'`` residual for a reference), ``render_map`` and ``write_ply`` accept as it is.  One host read of the row count."""
+    from ..tool import viz
+    n, density = _n_or_density(n, density, "sample_mesh")
+    viz._density_seed(1.0 if density is None else density, seed, "sample_mesh")
+    pts, faces = _mesh_parts(mesh, "sample_mesh")
+    colours = mesh.get('colours')
+    if colours is not None and (not torch.is_tensor(colours) or colours.dtype != torch.float32 or tuple(colours.shape) != tuple(pts.shape)):
+        raise ValueError(f"sample_mesh: mesh['colours'] must be a float32 tensor {tuple(pts.shape)}")
+    rec = _face_records(mesh, records, "sample_mesh")
+    if n is not None:
+        density = _density_of(n, rec, "sample_mesh")
+    found = viz.mesh_sample(pts, faces, rec, density, seed=seed, colours=colours)
+    N, dev = int(found['points'].shape[0]), pts.device
+    none = torch.full((N,), -1, dtype=torch.int32, device=dev)
+    return dict(points=found['points'], colours=found['colours'] if colours is not None else torch.zeros(N, 3, dtype=torch.float32, device=dev),
+                normals=found['normals'], face=found['face'], kf_index=none, seg_ids=none.clone(), offsets=np.array([0, N], dtype=np.int64))
+
+
+def mesh_distance(mesh, reference_mesh, radius, threshold=None, n=None, density=None, seed=0):
+    """Surface against surface: both meshes sampled at ONE density per area (``sample_mesh``), then ``map_distance`` on the two clouds --
+    accuracy, completion, completion ratio (``recall``) and the rest of ``cloud_metrics`` at ``threshold`` (default ``radius``).  Exactly
+    one of ``density`` and ``n``; with ``n`` the density comes from the REFERENCE's area (``n / area_total``, one host read) and both
+    meshes are sampled at it.  ``seed``: one integer for both samplings, or a pair (mesh, reference).  Returns ``map_distance``'s dict
+    plus ``samples`` and ``reference_samples`` (the two world dicts) and ``density``."""
+    radius, threshold = _threshold(radius, threshold, "mesh_distance")
+    n, density = _n_or_density(n, density, "mesh_distance")
+    seeds = tuple(seed) if isinstance(seed, (tuple, list)) else (seed, seed)
+    if len(seeds) != 2:
+        raise ValueError(f"mesh_distance: seed {seed!r} (an integer, or a pair)")
+    _mesh_parts(mesh, "mesh_distance")
+    ref_records = _face_records(reference_mesh, None, "mesh_distance")
+    if n is not None:
+        density = _density_of(n, ref_records, "mesh_distance")
+    samples = sample_mesh(mesh, density=density, seed=seeds[0])
+    reference_samples = sample_mesh(reference_mesh, density=density, seed=seeds[1], records=ref_records)
+    out = map_distance(samples, reference_samples, radius, threshold=threshold)
+    out.update(samples=samples, reference_samples=reference_samples, density=density)
+    return out
+
+
 def render_surface(volume, Ks, poses, size, z_max, min_weight=1.0, step=None):
     """The fused surface seen from V cameras: ``render_map``'s counterpart for a volume (``fuse_tsdf`` / ``sequence_tsdf``), ONE
     ``sp_tsdf_raycast`` launch (``tool.viz.tsdf_raycast``; include/sp_hip.h has the rule).  ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4)
@@ -917,6 +1095,138 @@ def write_ply(path, world):
             lists['n'], lists['v'] = 3, faces.detach().cpu().numpy()
             f.write(lists.tobytes())
     return path
+
+
+_PLY_FLOAT, _PLY_UCHAR = ('float', 'float32'), ('uchar', 'uint8')
+_PLY_COUNT = {'uchar': 'u1', 'uint8': 'u1', 'int': '<i4', 'int32': '<i4'}
+_PLY_INDEX = {'int': '<i4', 'int32': '<i4', 'uint': '<u4', 'uint32': '<u4'}
+
+
+def read_ply(path, device='cpu'):
+    """The inverse of ``write_ply``: a PLY file, binary little-endian or ASCII, whose ``vertex`` element has ``x y z`` float, optionally
+    ``nx ny nz`` float and optionally ``red green blue`` uchar (in any order), and whose optional ``face`` element is one list property of
+    ``uchar`` or ``int`` counts over ``int`` or ``uint`` indices, TRIANGLES only.  Anything else -- another format, element, property or
+    type, a face that is not a triangle, an index beyond int32, a short file -- raises ``ValueError`` naming the line (of the header, or
+    of an ASCII body; the element's row in a binary body).  Host code, NumPy.  Returns a world dict on ``device``: ``points`` (M,3)
+    float32, ``colours`` (M,3) float32 = uchar / 255 (zeros without them), ``normals`` when the file has them, ``faces`` (F,3) int32 when
+    it has a face element, ``kf_index`` / ``seg_ids`` = -1 and ``offsets`` = [0, M]: ``write_ply``, ``sample_mesh``, ``mesh_distance``
+    and ``map_distance`` accept it as it is."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    stop = data.find(b"\n", end) if end >= 0 else -1
+    if end < 0 or stop < 0:
+        raise ValueError(f"read_ply: {path}: no end_header line")
+    try:
+        lines = data[:stop].decode('ascii').split("\n")
+    except UnicodeDecodeError as e:
+        raise ValueError(f"read_ply: {path}: the header is not ASCII: {e}") from None
+    body = data[stop + 1:]
+    bad = lambda no, why: ValueError(f"read_ply: {path}, line {no}: {why}")
+    if lines[0].strip() != "ply":
+        raise bad(1, f"{lines[0]!r} is not 'ply'")
+    fmt, elements = None, []
+    for no, line in enumerate(lines[1:], start=2):
+        words = line.split()
+        if not words or words[0] in ("comment", "obj_info", "end_header"):
+            continue
+        if words[0] == "format":
+            if words[1:] not in (["binary_little_endian", "1.0"], ["ascii", "1.0"]) or fmt is not None:
+                raise bad(no, f"{line!r}: the format must be given once, binary_little_endian 1.0 or ascii 1.0")
+            fmt = words[1]
+        elif words[0] == "element":
+            if fmt is None or len(words) != 3 or not words[2].isdigit() or words[1] != ("vertex", "face")[min(len(elements), 1)] or len(elements) > 1:
+                raise bad(no, f"{line!r}: the elements are 'vertex N' and then, optionally, 'face F', after the format")
+            elements.append(dict(name=words[1], count=int(words[2]), props=[], line=no))
+        elif words[0] == "property" and elements:
+            el = elements[-1]
+            if el['name'] == "vertex":
+                kind = 'f' if len(words) == 3 and words[1] in _PLY_FLOAT and words[2] in ('x', 'y', 'z', 'nx', 'ny', 'nz') else \
+                    'u' if len(words) == 3 and words[1] in _PLY_UCHAR and words[2] in ('red', 'green', 'blue') else None
+                if kind is None or words[2] in [p[0] for p in el['props']]:
+                    raise bad(no, f"{line!r}: a vertex has x y z (float), nx ny nz (float) and red green blue (uchar), each once")
+                el['props'].append((words[2], '<f4' if kind == 'f' else 'u1'))
+            else:
+                if len(words) != 5 or words[1] != "list" or words[2] not in _PLY_COUNT or words[3] not in _PLY_INDEX \
+                        or words[4] not in ("vertex_indices", "vertex_index") or el['props']:
+                    raise bad(no, f"{line!r}: a face is one 'property list uchar|int int|uint vertex_indices'")
+                el['props'].append((_PLY_COUNT[words[2]], _PLY_INDEX[words[3]]))
+        else:
+            raise bad(no, f"{line!r}: not a line of a PLY header this reader takes")
+    if not elements:
+        raise bad(len(lines), "no vertex element")
+    vertex = elements[0]
+    names = [p[0] for p in vertex['props']]
+    for group in (('x', 'y', 'z'), ('nx', 'ny', 'nz'), ('red', 'green', 'blue')):
+        have = [k in names for k in group]
+        if (group[0] == 'x' and not all(have)) or (any(have) and not all(have)):
+            raise bad(vertex['line'], f"the vertex has {names}: {' '.join(group)} come together" + (" and x y z are required" if group[0] == 'x' else ""))
+    face = elements[1] if len(elements) > 1 else None
+    if face is not None and not face['props']:
+        raise bad(face['line'], "the face element has no property")
+    M, F = vertex['count'], face['count'] if face else 0
+    vdt = np.dtype(vertex['props'])
+    tri = None
+    if fmt == "binary_little_endian":
+        fdt = np.dtype([('n', face['props'][0][0]), ('v', face['props'][0][1], (3,))]) if face else None
+        if len(body) < M * vdt.itemsize:
+            raise bad(len(lines) + 1, f"the body holds {len(body)} bytes, {M} vertices need {M * vdt.itemsize}")
+        rows = np.frombuffer(body, dtype=vdt, count=M)
+        if face:
+            rest = body[M * vdt.itemsize:]
+            whole = np.frombuffer(rest, dtype=fdt, count=min(F, len(rest) // fdt.itemsize))
+            odd = np.nonzero(whole['n'] != 3)[0]
+            if len(odd):
+                raise bad(len(lines) + 1, f"face {int(odd[0])} has {int(whole['n'][odd[0]])} vertices: triangles only")
+            if len(whole) < F or len(rest) != F * fdt.itemsize:
+                raise bad(len(lines) + 1, f"{len(rest)} bytes after the vertices, {F} triangles need {F * fdt.itemsize}")
+            tri = whole['v'].astype(np.int64)
+    else:
+        first = len(lines) + 1                                                          # the file's line number of the body's first line
+        numbered = [(first + j, t) for j, t in enumerate(body.decode('ascii', errors='replace').split("\n")) if t.strip()]
+        if len(numbered) != M + F:
+            raise bad(numbered[-1][0] if numbered else first, f"the body has {len(numbered)} lines, {M} vertices and {F} faces need {M + F}")
+        at, text = [a for a, _ in numbered], [t for _, t in numbered]
+        rows = np.zeros(M, dtype=vdt)
+        for r in range(M):
+            words = text[r].split()
+            try:
+                if len(words) != len(names):
+                    raise ValueError(f"{len(words)} numbers for {len(names)} properties")
+                for (name, kind), w in zip(vertex['props'], words):
+                    rows[name][r] = float(w) if kind == '<f4' else int(w)
+                    if kind == 'u1' and not 0 <= int(w) <= 255:
+                        raise ValueError(f"{w} is no uchar")
+            except (ValueError, OverflowError) as e:
+                raise bad(at[r], f"{text[r]!r}: {e}") from None
+        if face:
+            tri = np.zeros((F, 3), np.int64)
+            for r in range(F):
+                words = text[M + r].split()
+                try:
+                    nums = [int(w) for w in words]
+                    if not nums or nums[0] != len(nums) - 1:
+                        raise ValueError("a list is its length and then that many indices")
+                    if nums[0] != 3:
+                        raise ValueError(f"a face of {nums[0]} vertices: triangles only")
+                    tri[r] = nums[1:]
+                except ValueError as e:
+                    raise bad(at[M + r], f"{text[M + r]!r}: {e}") from None
+    if tri is not None and len(tri) and (tri.min() < -2 ** 31 or tri.max() > 2 ** 31 - 1):
+        raise bad(len(lines) + 1, f"a face index {int(tri.max())} is beyond int32")
+    stack = lambda keys, dtype: torch.from_numpy(np.ascontiguousarray(np.stack([rows[k] for k in keys], axis=1).astype(dtype))).to(device)
+    out = dict(points=stack(('x', 'y', 'z'), np.float32))
+    if 'red' in names:
+        out['colours'] = torch.from_numpy(np.stack([rows[k] for k in ('red', 'green', 'blue')], axis=1).astype(np.float32) / np.float32(255.0)).to(device)
+    else:
+        out['colours'] = torch.zeros(M, 3, dtype=torch.float32, device=device)
+    if 'nx' in names:
+        out['normals'] = stack(('nx', 'ny', 'nz'), np.float32)
+    if face is not None:
+        out['faces'] = torch.from_numpy(tri.astype(np.int32).reshape(F, 3)).to(device)
+    none = torch.full((M,), -1, dtype=torch.int32, device=device)
+    out.update(kf_index=none, seg_ids=none.clone(), offsets=np.array([0, M], dtype=np.int64))
+    return out
 
 
 def write_tum_format(timestamps, pred_poses, gt_poses, out_dir):

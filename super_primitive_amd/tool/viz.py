@@ -21,6 +21,9 @@ matplotlib is imported):
 ``tsdf_integrate``     depth images fused into a dense signed-distance volume, in place (``sp_tsdf_integrate``).
 ``tsdf_mesh``          the volume's zero level set as an indexed triangle mesh: a counting call, one host read, a filling call (``sp_tsdf_mesh``).
 ``tsdf_raycast``       the volume seen from V cameras: depth, world normals, colour and cell index per pixel, one ray each (``sp_tsdf_raycast``).
+``mesh_faces``         one record per face of a triangle mesh: state, area, unit normal, and the summary counts (``sp_mesh_faces``).
+``mesh_sample``        an area-uniform, seeded cloud with normals from those records: a counting call, one host read, a filling call
+                       (``sp_mesh_sample``).
 ``register_clouds``    the similarity that moves a query cloud onto such a cloud, by Gauss-Newton ICP on the device (``sp_cloud_register``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
@@ -764,4 +767,90 @@ def tsdf_raycast(volume, Ks, poses, H, W, z_max, min_weight=1.0, z_min=Z_MIN, st
     _lib.check(lib.sp_tsdf_raycast(_lib.ptr(tsdf), _lib.ptr(weight), _lib.ptr(colour), nx, ny, nz, vox, org[0], org[1], org[2], min_weight,
                                    _lib.ptr(views), V, H, W, z_min, step, n_steps, _lib.ptr(out.get('depth')), _lib.ptr(out.get('normals')),
                                    _lib.ptr(out.get('image')), _lib.ptr(out.get('index')), _lib.stream_ptr()), "sp_tsdf_raycast")
+    return out
+
+
+def _mesh(vertices, faces, what):
+    """(vertices (M,3) float32, faces (F,3) int32) contiguous, on one device, within the kernels' limits."""
+    _on_device(vertices, faces)
+    v = _f32(vertices, (None, 3), f"{what}: vertices")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: faces must be int32 (F,3), got {faces.dtype} {tuple(faces.shape)}")
+    M, F = int(v.shape[0]), int(faces.shape[0])
+    if M < 1 or F < 1:
+        raise ValueError(f"{what}: a mesh of {M} vertices and {F} faces")
+    if M > _lib.SP_MESH_MAX_FACES or F > _lib.SP_MESH_MAX_FACES:
+        raise ValueError(f"{what}: {M} vertices and {F} faces are beyond the kernel's limit of 2^28")
+    return v, faces.detach().contiguous(), M, F
+
+
+def mesh_faces(vertices, faces, cross=False):
+    """ONE ``sp_mesh_faces`` launch (include/sp_hip.h has the rule): per face of ``vertices`` (M,3) float32, ``faces`` (F,3) int32 its
+    ``state`` (F,) uint8 (0 valid, 1 an index outside the vertices, 2 a repeated index, 3 a non-finite coordinate, 4 zero area), ``area``
+    (F,) float64 and unit ``normals`` (F,3) float32 -- zeros unless the state is 0 --, with ``cross`` also the raw cross product (F,3)
+    float64; and ``summary`` (6,) int64: the faces of each state and the bits of the largest area (``summary[5:].view(torch.float64)``).
+    No synchronisation."""
+    v, f, M, F = _mesh(vertices, faces, "mesh_faces")
+    dev = v.device
+    out = dict(area=torch.empty(F, dtype=torch.float64, device=dev), normals=torch.empty(F, 3, dtype=torch.float32, device=dev),
+               state=torch.empty(F, dtype=torch.uint8, device=dev), summary=torch.empty(_lib.SP_MESH_SUMMARY_WORDS, dtype=torch.int64, device=dev))
+    if cross:
+        out['cross'] = torch.empty(F, 3, dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    _lib.check(lib.sp_mesh_faces(_lib.ptr(v), M, _lib.ptr(f), F, _lib.ptr(out['area']), _lib.ptr(out['normals']), _lib.ptr(out['state']),
+                                 _lib.ptr(out.get('cross')), _lib.ptr(out['summary']), _lib.stream_ptr()), "sp_mesh_faces")
+    return out
+
+
+def _density_seed(density, seed, what):
+    try:
+        whole = int(seed)
+        if whole != seed:
+            raise ValueError("the seed must be a whole number")
+        density, seed = float(density), whole
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: density {density!r}, seed {seed!r}: {e}") from None
+    if not (0.0 < density < float("inf")):
+        raise ValueError(f"{what}: density {density} (finite, > 0)")
+    if not -2 ** 63 <= seed < 2 ** 64:
+        raise ValueError(f"{what}: seed {seed} is not 64 bits")
+    seed &= 2 ** 64 - 1
+    return density, seed - 2 ** 64 if seed >= 2 ** 63 else seed                    # (the same 64 bits as the signed integer the ABI carries)
+
+
+def mesh_sample(vertices, faces, records, density, seed=0, colours=None):
+    """An area-uniform, seeded cloud of the mesh (``sp_mesh_sample``; include/sp_hip.h has the rule): ``records`` is what ``mesh_faces``
+    returned for this mesh, ``density`` the samples per unit area, ``colours`` (M,3) float32 vertex colours or None.  A counting call, ONE
+    host read of the count (the one synchronisation), buffers of exactly that size, and a second call that fills them.  Returns
+    ``dict(points, normals (N,3) float32, colours (N,3) float32 or None, face (N,) int32)``, rows ordered by (face, sample); the same
+    arguments give the same bits."""
+    v, f, M, F = _mesh(vertices, faces, "mesh_sample")
+    density, seed = _density_seed(density, seed, "mesh_sample")
+    if not isinstance(records, dict) or any(not torch.is_tensor(records.get(k)) for k in ('area', 'normals', 'state')):
+        raise ValueError("mesh_sample: records must be what mesh_faces returned")
+    area, nrm, state = records['area'], records['normals'], records['state']
+    if area.dtype != torch.float64 or tuple(area.shape) != (F,) or state.dtype != torch.uint8 or tuple(state.shape) != (F,) \
+            or nrm.dtype != torch.float32 or tuple(nrm.shape) != (F, 3):
+        raise ValueError(f"mesh_sample: records of another mesh: area {tuple(area.shape)}, normals {tuple(nrm.shape)}, state {tuple(state.shape)} for {F} faces")
+    cols = None if colours is None else _f32(colours, (M, 3), "mesh_sample: colours")
+    _on_device(v, f, area, nrm, state, cols)
+    area, nrm, state = area.contiguous(), nrm.contiguous(), state.contiguous()
+    lib = _lib.load()
+    dev = v.device
+    scratch = torch.empty(8 * lib.sp_mesh_sample_scratch_units(F), dtype=torch.int64, device=dev)
+    n_out = torch.empty(1, dtype=torch.int64, device=dev)
+
+    def call(cap, points, normals, out_colours, face):
+        _lib.check(lib.sp_mesh_sample(_lib.ptr(v), _lib.ptr(cols), M, _lib.ptr(f), F, _lib.ptr(area), _lib.ptr(nrm), _lib.ptr(state), density, seed,
+                                      _lib.ptr(scratch), cap, _lib.ptr(points), _lib.ptr(normals), _lib.ptr(out_colours), _lib.ptr(face),
+                                      _lib.ptr(n_out), _lib.stream_ptr()), "sp_mesh_sample")
+    call(0, None, None, None, None)
+    N = int(n_out.item())                                                        # the one host read
+    if N > 2 ** 31 - 1:
+        raise ValueError(f"mesh_sample: {N} samples are beyond 32-bit rows; lower the density")
+    out = dict(points=torch.empty(N, 3, dtype=torch.float32, device=dev), normals=torch.empty(N, 3, dtype=torch.float32, device=dev),
+               colours=None if cols is None else torch.empty(N, 3, dtype=torch.float32, device=dev),
+               face=torch.empty(N, dtype=torch.int32, device=dev))
+    if N > 0:
+        call(N, out['points'], out['normals'], out['colours'], out['face'])
     return out
