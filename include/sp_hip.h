@@ -1814,6 +1814,63 @@ int sp_mesh_sample(const float* vertices, const float* vertex_colours, long long
                    const float* face_normals, const uint8_t* state, double density, long long seed, void* scratch, long long capacity,
                    float* points, float* normals, float* colours, int32_t* face, long long* n_out, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------
+ * Mesh views (sp_mesh_render.hip): a triangle mesh rasterised into depth, normal, colour and face-index images of V cameras -- ground-
+ * truth depth from a ground-truth model, the views of an extracted or cleaned mesh, and the per-face visibility a benchmark culls by.
+ * Runs on the caller's stream without a synchronisation; argument checks come before any device work; 64-bit integer atomic maxima only:
+ * two runs give the same bits.
+ *     vertices : (M,3) float32;  vertex_colours : (M,3) float32 or NULL;  faces : (F,3) int32
+ *     face_normals : (F,3) float32, the normals of sp_mesh_faces for this mesh, or NULL
+ *     views    : V SpView records on the device, camera-to-world;  cull : 0 (two-sided) or 1 (only faces seen from their front)
+ *     scratch  : sp_mesh_render_scratch_units(F) units of 64 bytes, aligned to 8 bytes, written by the call: for ONE chunk of
+ *                SP_MESH_RENDER_VIEW_CHUNK views one int64 per (face, view) padded to 256-face blocks, one per block, and the total
+ *                (1 + 2^21 + 2^29 units at the limit: an int, like the sizes of sp_mesh_sample and sp_map_fuse)
+ *     keys     : V H W uint64 of scratch, zeroed by the call
+ *     depth    : (V,H,W) float32;  normals : (V,H,W,3) float32, world frame;  image : (V,H,W,3) uint8;  index : (V,H,W) int32 -- each may be
+ *                NULL, at least one must be given, image needs vertex_colours, normals needs face_normals.  EVERY GIVEN OUTPUT IS WRITTEN
+ *                FOR EVERY PIXEL
+ * THE RULE.  Float64 from the float32 inputs, every operation rounded on its own (no fma, no reciprocal); three-term sums as (x + y) + z.
+ * Face.  A face is USABLE iff its three indices are in [0, M) and distinct and its nine coordinates are finite (states 1 to 3 of
+ * sp_mesh_faces, tested again so that a foreign record cannot make the kernel read beyond the vertices).  An unusable face covers nothing.
+ * Camera frame.  q_k = R^T (p_k - t), k = 0, 1, 2, exactly as sp_render_views forms p_c (the same device function; an exact identity pose
+ * leaves the point untouched).
+ * Edge planes.  n_0 = q_1 x q_2,  n_1 = q_2 x q_0,  n_2 = q_0 x q_1,  each component a difference of two products in sp_mesh_faces' order:
+ *     (a x b)_x = a_y b_z - a_z b_y,   (a x b)_y = a_z b_x - a_x b_z,   (a x b)_z = a_x b_y - a_y b_x
+ * det = (q_0x n_0x + q_0y n_0y) + q_0z n_0z.  A face whose det is 0 or not finite covers nothing in that view.  det < 0 is a face seen
+ * from its front, the side its sp_mesh_faces normal points to; cull = 1 drops a face unless det < 0.
+ * Pixel.  Pixel centres are at integers, as in sp_tsdf_raycast and sp_tsdf_integrate (the depth image is what those and the depth scores
+ * consume):  a = (col - cx) / fx,  b = (row - cy) / fy,  E_k = (n_kx a + n_ky b) + n_kz,  S = (E_0 + E_1) + E_2.  With sigma the sign of
+ * det the pixel is COVERED iff sigma E_k >= 0 for k = 0, 1, 2 (a zero of either sign passes, NaN fails), sigma S > 0, and z = det / S (an
+ * IEEE division) satisfies z > z_min and z < inf.  The comparison is inclusive on purpose: for an edge shared by two faces the ordered
+ * pair (q_i, q_j) of one is (q_j, q_i) of the other, every component of the cross product and with it E negates exactly, so a pixel centre
+ * is inside one of the two faces or on the edge of both: no cracks, and no fill-rule table.  The test is homogeneous: a face that crosses
+ * the camera plane needs no clipping, and a face behind the camera fails the sign test.
+ * Rectangle.  Part of the rule, so that the result does not depend on how an implementation bounds its work.  With z_k = q_kz:
+ *   - all three z_k <= z_min: the face covers nothing (every point of it lies at or behind the plane);
+ *   - all three z_k > z_min:  (u_k, v_k) = (x fx / z + cx, y fy / z + cy) of q_k, sp_render_views' projection (the same device function).
+ *     The face is tested on the columns max(floor(min u), 0) .. min(ceil(max u), W - 1) and the rows max(floor(min v), 0) ..
+ *     min(ceil(max v), H - 1), clamped in float64 and then converted; an empty range covers nothing.  Should one of the six numbers not
+ *     be finite, the face is tested on the whole image;
+ *   - otherwise the face crosses the plane and is tested on the whole image.
+ * Contest.  Every covered pixel offers key_nearest(float32(z), face), sp_render_views mode 1's key: the smallest float32(z) wins, equal
+ * float32(z) goes to the HIGHEST face index.
+ * Resolve.  The winner's values are functions of (face, view, pixel) alone:  depth = float32(z);  index = the face;  normals =
+ * face_normals[face], in the world frame and not flipped;  lambda_k = E_k / S (IEEE divisions), and per channel colour = (lambda_0 c_0 +
+ * lambda_1 c_1) + lambda_2 c_2 from the three vertices' colours, rounded to float32 once, then sp_render_views' 8-bit rule (trunc(c * 255)
+ * clamped to 0 .. 255, NaN gives 0): perspective-correct by construction.  No winner: depth = 0, index = -1, image = 0, 0, 0, normals NaN --
+ * sp_tsdf_raycast's no-hit convention.
+ * The kernels cut the rectangle into tiles of 64 pixels, one wave per (face, view, tile); the tile's shape is a compile-time choice the
+ * result cannot depend on.
+ * Null vertices / faces / views / scratch / keys, a scratch or keys not aligned to 8 bytes or another pointer not aligned to 4, all four
+ * outputs NULL, image without vertex_colours, normals without face_normals, F, M, V, H or W < 1, z_min negative or NaN, cull outside
+ * {0, 1}: SP_EINVAL.  F or M > 2^28 (SP_MESH_MAX_FACES), V > 65535, V H W >= 2^31: SP_ELIMIT.  Invalid beats too large.
+ * sp_mesh_render_scratch_units answers F < 1 and F > 2^28 with the same codes. */
+#define SP_MESH_RENDER_VIEW_CHUNK 16
+int sp_mesh_render_scratch_units(long long F);
+int sp_mesh_render(const float* vertices, const float* vertex_colours, long long M, const int32_t* faces, long long F,
+                   const float* face_normals, const SpView* views, int V, int H, int W, float z_min, int cull, void* scratch,
+                   unsigned long long* keys, float* depth, float* normals, uint8_t* image, int32_t* index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

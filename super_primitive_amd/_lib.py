@@ -118,6 +118,8 @@ SIGNATURES = {
     "sp_mesh_faces": [P, ctypes.c_longlong, P, ctypes.c_longlong, P, P, P, P, P, P],
     "sp_mesh_sample_scratch_units": [ctypes.c_longlong],
     "sp_mesh_sample": [P, P, ctypes.c_longlong, P, ctypes.c_longlong, P, P, P, ctypes.c_double, ctypes.c_longlong, P, ctypes.c_longlong, P, P, P, P, P, P],
+    "sp_mesh_render_scratch_units": [ctypes.c_longlong],
+    "sp_mesh_render": [P, P, ctypes.c_longlong, P, ctypes.c_longlong, P, P, I, I, I, F, I, P, P, P, P, P, P, P],
 }
 
 # the entry points that do not return an int
@@ -300,6 +302,7 @@ SP_TSDF_MAX_NODES = 1 << 30
 SP_TSDF_RAYCAST_MAX_STEPS = 1 << 20
 SP_MESH_MAX_FACES = 1 << 28
 SP_MESH_SUMMARY_WORDS = 6
+SP_MESH_RENDER_VIEW_CHUNK = 16
 SP_CLOUD_REG_RUNNING, SP_CLOUD_REG_CONVERGED, SP_CLOUD_REG_MAX_ITERS, SP_CLOUD_REG_FEW, SP_CLOUD_REG_DEGENERATE = range(5)
 SP_CLOUD_REG_ITERS_LIMIT = 4096
 SP_CLOUD_REG_WORK_DOUBLES = 40

@@ -40,6 +40,10 @@
                       normals (``sp_mesh_faces`` / ``sp_mesh_sample``) that every function above takes; ``mesh_faces`` is the record per
                       face, ``clean_mesh`` drops degenerate triangles, ``mesh_normals`` gives area-weighted vertex normals and
                       ``mesh_distance`` scores surface against surface, both meshes sampled at one density.
+``render_mesh``       a mesh seen from V cameras, rasterised through the depth buffer (ONE ``sp_mesh_render`` call): depth, the winning
+                      face and its normal, interpolated colour -- ground-truth depth images from a ground-truth model; ``score_mesh`` /
+                      ``score_mesh_images`` score those views as ``score_surface`` / ``score_surface_images`` score the volume's,
+                      ``visible_faces`` counts the pixels and views every face wins, ``cull_mesh`` keeps what the cameras saw.
 ``write_ply``         the map's points, normals (when it has them) and 8-bit colours as a binary PLY file; a mesh's faces too;
                       ``read_ply`` is its inverse, for binary and ASCII files of triangles."""
 from __future__ import annotations
@@ -881,18 +885,12 @@ def mesh_faces(mesh, cross=False):
     return found
 
 
-def clean_mesh(mesh, records=None):
-    """``mesh`` without its degenerate triangles: the faces whose state is not 0 dropped (``mesh_faces``; ``records``: what it returned
-    for this mesh, reused), then the vertices no kept face references; the order of both is preserved and duplicate positions are not
-    welded.  Plain torch over ``state`` (boolean selection and a cumulative sum for the new indices): with ``records`` it runs on CPU
-    tensors too.  Returns a NEW dict: ``points``, ``colours``, ``normals`` (when present), ``faces`` (re-indexed, int32), ``kept_vertices``
-    and ``kept_faces`` (int64: the surviving rows of the input), and ``kf_index`` / ``seg_ids`` = -1, ``offsets`` = [0, M'] as
-    ``extract_mesh`` forms them.  Two host reads on the device: the sizes of the two boolean selections."""
-    pts, faces = _mesh_parts(mesh, "clean_mesh")
-    state = _face_records(mesh, records, "clean_mesh")['state'].to(pts.device)
+def _select_faces(mesh, pts, faces, keep, what):
+    """The selection ``clean_mesh`` and ``cull_mesh`` share: the faces where ``keep`` (F,) bool holds -- each with its three indices inside
+    the vertices --, then the vertices they reference, both in their order, re-indexed; ``colours`` and ``normals`` carried along."""
     M = int(pts.shape[0])
-    kept_faces = torch.nonzero(state == 0).reshape(-1)
-    kept = faces[kept_faces].long()                                                    # (state 0: every index is inside the vertices)
+    kept_faces = torch.nonzero(keep).reshape(-1)
+    kept = faces[kept_faces].long()
     used = torch.zeros(M, dtype=torch.bool, device=pts.device)
     used[kept.reshape(-1)] = True
     new_index = torch.cumsum(used.long(), dim=0) - 1
@@ -902,11 +900,23 @@ def clean_mesh(mesh, records=None):
     for key in ('colours', 'normals'):
         if mesh.get(key) is not None:
             if not torch.is_tensor(mesh[key]) or tuple(mesh[key].shape) != (M, 3):
-                raise ValueError(f"clean_mesh: mesh['{key}'] must be a tensor ({M},3)")
+                raise ValueError(f"{what}: mesh['{key}'] must be a tensor ({M},3)")
             out[key] = mesh[key][kept_vertices]
     none = torch.full((Mk,), -1, dtype=torch.int32, device=pts.device)
     out.update(kf_index=none, seg_ids=none.clone(), offsets=np.array([0, Mk], dtype=np.int64))
     return out
+
+
+def clean_mesh(mesh, records=None):
+    """``mesh`` without its degenerate triangles: the faces whose state is not 0 dropped (``mesh_faces``; ``records``: what it returned
+    for this mesh, reused), then the vertices no kept face references; the order of both is preserved and duplicate positions are not
+    welded.  Plain torch over ``state`` (boolean selection and a cumulative sum for the new indices): with ``records`` it runs on CPU
+    tensors too.  Returns a NEW dict: ``points``, ``colours``, ``normals`` (when present), ``faces`` (re-indexed, int32), ``kept_vertices``
+    and ``kept_faces`` (int64: the surviving rows of the input), and ``kf_index`` / ``seg_ids`` = -1, ``offsets`` = [0, M'] as
+    ``extract_mesh`` forms them.  Two host reads on the device: the sizes of the two boolean selections."""
+    pts, faces = _mesh_parts(mesh, "clean_mesh")
+    state = _face_records(mesh, records, "clean_mesh")['state'].to(pts.device)
+    return _select_faces(mesh, pts, faces, state == 0, "clean_mesh")                   # (state 0: every index is inside the vertices)
 
 
 _CROSS_SCALE = 2.0 ** 30           # mesh_normals: face cross products are summed as int64 round(c * (2^30 / c_max))
@@ -1057,6 +1067,108 @@ def score_surface_images(volume, images, Ks, poses, z_max, min_weight=1.0, step=
     viz._on_device(images)
     out = viz.tsdf_raycast(volume, Ks, poses, H, W, z_max, min_weight=min_weight, step=step, depth=False, normals=False, image=True)
     return _image_scores(out['image'], images, out['index'])
+
+
+def _mesh_colours(mesh, pts, what):
+    """``mesh['colours']`` as the float32 (M,3) vertex colours of the mesh, or None."""
+    colours = mesh.get('colours')
+    if colours is not None and (not torch.is_tensor(colours) or colours.dtype != torch.float32 or tuple(colours.shape) != tuple(pts.shape)):
+        raise ValueError(f"{what}: mesh['colours'] must be a float32 tensor {tuple(pts.shape)}")
+    return colours
+
+
+def render_mesh(mesh, Ks, poses, size, cull=False, records=None):
+    """The mesh seen from V cameras: ``render_surface``'s counterpart for a triangle mesh -- ``extract_mesh``'s, ``clean_mesh``'s, one moved
+    by ``transform_map``, or a ground-truth model from ``read_ply`` --, ONE ``sp_mesh_render`` call (``tool.viz.mesh_render``;
+    include/sp_hip.h has the rule).  ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world in the mesh's frame, ``size`` = (H, W);
+    ``cull=True`` keeps only faces seen from their front.  The face normals come from ``mesh_faces`` (one more launch) unless
+    ``records``, what it returned for this mesh, is passed.  Returns ``render_surface``'s dict: depth (V,H,W) float32 -- 0 where no face
+    lies --, normals (V,H,W,3) float32, the winning face's unit normal in the mesh's frame (NaN there; zeros for a degenerate winner),
+    image (V,H,W,3) uint8 -- vertex colours interpolated perspective-correctly, zeros for a mesh without colours --, index (V,H,W) int32 --
+    the winning row of ``mesh['faces']``, -1 there.  ``render_mesh(gt_mesh, Ks, gt_poses, (H, W))['depth']`` is the ground-truth depth
+    ``score_map``, ``score_surface``, ``map_consistency`` and ``fuse_tsdf`` take.  No synchronisation."""
+    from ..tool import viz
+    Ks, poses = _view_cameras(Ks, poses, "render_mesh")
+    pts, faces = _mesh_parts(mesh, "render_mesh")
+    colours = _mesh_colours(mesh, pts, "render_mesh")
+    H, W = size
+    viz._on_device(pts, faces)
+    rec = _face_records(mesh, records, "render_mesh")
+    out = viz.mesh_render(pts, faces, Ks, poses, H, W, colours=colours, face_normals=rec['normals'], cull=bool(cull))
+    if 'image' not in out:
+        out['image'] = torch.zeros(*out['index'].shape, 3, dtype=torch.uint8, device=out['index'].device)
+    return out
+
+
+def score_mesh(mesh, gt_depths, Ks, gt_poses, min_depth=0.2, max_depth=5.0, cull=False):
+    """The mesh against ground-truth depth images: ``score_surface`` for a triangle mesh.  The mesh is rasterised into each of the V
+    ground-truth views (``render_mesh``'s call, depth and index only) and scored where a face won the pixel (``index >= 0``) and
+    ``min_depth <= gt <= max_depth``.  Returns ``score_map``'s dict (metrics (V,12), columns, coverage).  No synchronisation."""
+    from ..tool import viz
+    Ks, gt_poses = _view_cameras(Ks, gt_poses, "score_mesh")
+    V, H, W = _target_depths(gt_depths, gt_poses, min_depth, max_depth, "score_mesh")
+    pts, faces = _mesh_parts(mesh, "score_mesh")
+    viz._on_device(gt_depths, pts, faces)
+    out = viz.mesh_render(pts, faces, Ks, gt_poses, H, W, cull=bool(cull))
+    return _depth_scores(out['depth'], out['index'] >= 0, gt_depths, min_depth, max_depth)
+
+
+def score_mesh_images(mesh, images, Ks, poses, cull=False):
+    """The mesh's colour views against real images: ``score_surface_images`` for a mesh with vertex colours.  ``images`` (V,3,H,W) float32
+    in 0..1; one ``sp_mesh_render`` call (image and index) plus ONE ``sp_image_metrics`` launch over the pixels a face won.  Returns
+    ``score_map_images``' dict (sums, psnr, l1, coverage).  No synchronisation."""
+    from ..tool import viz
+    Ks, poses = _view_cameras(Ks, poses, "score_mesh_images")
+    H, W = _target_images(images, poses, "score_mesh_images")
+    pts, faces = _mesh_parts(mesh, "score_mesh_images")
+    colours = _mesh_colours(mesh, pts, "score_mesh_images")
+    if colours is None:
+        raise ValueError("score_mesh_images: the mesh has no colours")
+    viz._on_device(images, pts, faces)
+    out = viz.mesh_render(pts, faces, Ks, poses, H, W, colours=colours, cull=bool(cull), depth=False, image=True)
+    return _image_scores(out['image'], images, out['index'])
+
+
+def visible_faces(mesh, Ks, poses, size, cull=False, index=None):
+    """Which faces of the mesh the cameras see: ``dict(pixels (F,) int64, views (F,) int32)`` -- the pixels each face wins over all V views
+    and the number of views in which it wins at least one --, both integer ``bincount``s of ``render_mesh``'s ``index``: exact in any
+    order.  ``index``: a (V,H,W) int32 face image of this mesh made before (``render_mesh``'s, or any rasteriser's), reused -- then no
+    view is rendered, ``Ks``, ``poses``, ``size`` and ``cull`` are not read, and CPU tensors work too.  No synchronisation."""
+    pts, faces = _mesh_parts(mesh, "visible_faces")
+    F = int(faces.shape[0])
+    if index is None:
+        from ..tool import viz
+        Ks, poses = _view_cameras(Ks, poses, "visible_faces")
+        H, W = size
+        index = viz.mesh_render(pts, faces, Ks, poses, H, W, cull=bool(cull), depth=False)['index']
+    elif not torch.is_tensor(index) or index.dtype != torch.int32 or index.dim() != 3:
+        raise ValueError("visible_faces: index must be an int32 (V,H,W) tensor")
+    V = int(index.shape[0])
+    # row v of the table counts into its own F + 1 bins (bin 0: the pixels no face won)
+    flat = (index.long() + 1 + (F + 1) * torch.arange(V, device=index.device)[:, None, None]).reshape(-1)
+    per_view = torch.bincount(flat, minlength=V * (F + 1)).reshape(V, F + 1)[:, 1:]
+    return dict(pixels=per_view.sum(dim=0), views=(per_view > 0).sum(dim=0).to(torch.int32))
+
+
+def cull_mesh(mesh, Ks, poses, size, min_pixels=1, cull=False, visible=None):
+    """The mesh reduced to what the cameras saw, as benchmarks cull a ground-truth model before surface-against-surface scores: the faces
+    with ``visible_faces(...)['pixels'] >= min_pixels`` (a whole number >= 1), then the vertices they reference -- ``clean_mesh``'s
+    selection: order kept, re-indexed, ``colours`` and ``normals`` carried along, ``kept_faces`` and ``kept_vertices`` (int64: the
+    surviving rows of the input) reported.  ``visible``: what ``visible_faces`` returned for this mesh, reused -- then plain torch, and
+    CPU tensors work too.  Two host reads: the sizes of the two boolean selections."""
+    pts, faces = _mesh_parts(mesh, "cull_mesh")
+    try:
+        if int(min_pixels) != min_pixels or int(min_pixels) < 1:
+            raise ValueError("a whole number >= 1")
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"cull_mesh: min_pixels {min_pixels!r}: {e}") from None
+    if visible is None:
+        visible = visible_faces(mesh, Ks, poses, size, cull=cull)
+    pixels = visible.get('pixels') if isinstance(visible, dict) else None
+    if not torch.is_tensor(pixels) or tuple(pixels.shape) != (int(faces.shape[0]),):
+        raise ValueError(f"cull_mesh: visible must be what visible_faces returned for this mesh ({int(faces.shape[0])} faces)")
+    # (a face that won a pixel is usable by the rule: its indices are inside the vertices)
+    return _select_faces(mesh, pts, faces, pixels.to(pts.device) >= int(min_pixels), "cull_mesh")
 
 
 def write_ply(path, world):

@@ -24,6 +24,8 @@ matplotlib is imported):
 ``mesh_faces``         one record per face of a triangle mesh: state, area, unit normal, and the summary counts (``sp_mesh_faces``).
 ``mesh_sample``        an area-uniform, seeded cloud with normals from those records: a counting call, one host read, a filling call
                        (``sp_mesh_sample``).
+``mesh_render``       the mesh seen from V cameras: depth, world normals, interpolated colour and winning face per pixel, rasterised
+                       through the depth buffer (``sp_mesh_render``).
 ``register_clouds``    the similarity that moves a query cloud onto such a cloud, by Gauss-Newton ICP on the device (``sp_cloud_register``).
 
 Argument errors raise ``ValueError`` before anything is launched."""
@@ -853,4 +855,59 @@ def mesh_sample(vertices, faces, records, density, seed=0, colours=None):
                face=torch.empty(N, dtype=torch.int32, device=dev))
     if N > 0:
         call(N, out['points'], out['normals'], out['colours'], out['face'])
+    return out
+
+
+def mesh_render(vertices, faces, Ks, poses, H, W, colours=None, face_normals=None, z_min=Z_MIN, cull=False, depth=True, normals=None, image=None,
+                index=True):
+    """ONE ``sp_mesh_render`` call (include/sp_hip.h has the rule): the mesh ``vertices`` (M,3) float32, ``faces`` (F,3) int32 rasterised
+    into V views, ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world in the mesh's frame.  A pixel whose centre lies inside a face
+    (edges included: no cracks between neighbours) at a camera depth > ``z_min`` is contested through the depth buffer: the nearest face
+    wins, equal depths go to the highest face.  ``cull=True`` keeps only faces seen from their front, the side their ``mesh_faces`` normal
+    points to.  ``colours`` (M,3) float32 vertex colours in 0..1, ``face_normals`` (F,3) float32 (``mesh_faces``' ``normals``).  Returns
+    the requested of ``depth`` (V,H,W) float32 (0 where no face lies), ``normals`` (V,H,W,3) float32, the winning face's (NaN there),
+    ``image`` (V,H,W,3) uint8, interpolated perspective-correctly (0) and ``index`` (V,H,W) int32, the winning face (-1), as a dict.
+    ``normals=None`` / ``image=None``: that output iff ``face_normals`` / ``colours`` is given; asking for one without its input is an
+    error.  No synchronisation."""
+    v, f, M, F = _mesh(vertices, faces, "mesh_render")
+    _on_device(v, f, Ks, poses, colours, face_normals)
+    if poses.dim() != 3:
+        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
+    V = int(poses.shape[0])
+    if V == 0:
+        raise ValueError("mesh_render: poses of no views")
+    H, W = _size(H, W)
+    views = _views(Ks, poses, V)
+    try:
+        z_min = float(z_min)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"mesh_render: z_min {z_min!r}: {e}") from None
+    _z_min(z_min)
+    cols = None if colours is None else _f32(colours, (M, 3), "mesh_render: colours")
+    nrm = None if face_normals is None else _f32(face_normals, (F, 3), "mesh_render: face_normals")
+    if image and cols is None:
+        raise ValueError("mesh_render: an image needs colours")
+    if normals and nrm is None:
+        raise ValueError("mesh_render: normals need face_normals (mesh_faces' normals)")
+    image = cols is not None if image is None else bool(image)
+    normals = nrm is not None if normals is None else bool(normals)
+    if not (depth or normals or image or index):
+        raise ValueError("mesh_render: no output asked for")
+    _limits("mesh_render", V, H, W)
+    lib = _lib.load()
+    dev = v.device
+    scratch = torch.empty(8 * lib.sp_mesh_render_scratch_units(F), dtype=torch.int64, device=dev)
+    keys = torch.empty(V * H * W, dtype=torch.int64, device=dev)
+    out = {}
+    if depth:
+        out['depth'] = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    if normals:
+        out['normals'] = torch.empty(V, H, W, 3, dtype=torch.float32, device=dev)
+    if image:
+        out['image'] = torch.empty(V, H, W, 3, dtype=torch.uint8, device=dev)
+    if index:
+        out['index'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    _lib.check(lib.sp_mesh_render(_lib.ptr(v), _lib.ptr(cols), M, _lib.ptr(f), F, _lib.ptr(nrm), _lib.ptr(views), V, H, W, z_min, 1 if cull else 0,
+                                  _lib.ptr(scratch), _lib.ptr(keys), _lib.ptr(out.get('depth')), _lib.ptr(out.get('normals')),
+                                  _lib.ptr(out.get('image')), _lib.ptr(out.get('index')), _lib.stream_ptr()), "sp_mesh_render")
     return out
