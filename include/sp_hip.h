@@ -1329,7 +1329,7 @@ int sp_render_views(const float* points, const float* colours, long long Q, cons
 int sp_render_splats(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, float z_min,
                      const float* radii, int max_px, unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream);
 
-/* sp_render_surfels (sp_surfel.hip): sp_render_splats' depth buffer with an ORIENTED footprint per point: the depth of every covered
+/* sp_render_surfels (sp_views.hip): sp_render_splats' depth buffer with an ORIENTED footprint per point: the depth of every covered
  * pixel is taken on the point's tangent plane, so a slanted surface renders at its true depth.  The arguments, limits and error codes of
  * sp_render_splats, plus
  *     normals : (Q,3) float32 in the frame of the points (sp_map_normals'), required

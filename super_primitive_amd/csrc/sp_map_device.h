@@ -1,4 +1,4 @@
-// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip, sp_register.hip, sp_tsdf.hip, sp_raycast.hip, sp_mesh.hip): each idiom has its one definition here.
+// Device-side pieces shared by the map kernels (sp_views.hip, sp_results.hip, sp_fuse.hip, sp_surfel.hip, sp_nearest.hip, sp_register.hip, sp_tsdf.hip, sp_raycast.hip, sp_mesh.hip, sp_mesh_render.hip) and the host side of a view set (its limits, a depth buffer's launch tail): each idiom has its one definition here.
 #pragma once
 #include "sp_device.h"
 
@@ -277,7 +277,7 @@ __device__ __forceinline__ int keyframe_of_block(const SpMapKeyframe* __restrict
 // the segment of table point i of a keyframe
 __device__ __forceinline__ int map_point_segment(const SpMapKeyframe& kf, int i) { return segment_of(kf.seg_off, kf.N, i); }
 
-// ---- views: one record per view in float64, the projection, a footprint's half-width (sp_views.hip and sp_surfel.hip; the arithmetic
+// ---- views: one record per view in float64, the projection, a footprint's half-width (every kernel that projects; the arithmetic
 // carries its own contraction pragma: every operation is rounded on its own whatever the including file allows) ----------------------
 constexpr int VIEW_CHUNK = 16;
 
@@ -362,10 +362,25 @@ inline long long volume_nodes(int nx, int ny, int nz) {
     return xy * nz;
 }
 
+// neither NaN nor +-inf: finite_f on the host (the entry points' arguments), finite_d on either side
 inline bool finite_f(float x) { return fabsf(x) < HUGE_VALF; }
+__host__ __device__ __forceinline__ bool finite_d(double x) { return fabs(x) < HUGE_VAL; }
 
-// ---- the resolve pass of every depth buffer of keys (sp_render_views, sp_render_splats, sp_render_surfels): one definition here, one
-// static copy in every file that launches it and says so by defining SP_MAP_DEVICE_RESOLVE before this header ----------------------
+// ---- the host side of a view set: its limits, a depth buffer's empty keys and pixel grid -------------------------------------------
+// ids and pixels are 32-bit, a grid dimension 16-bit: 0, or SP_ELIMIT beyond 65535 views, 2^31 - 1 pixels in all or 2^31 - 2 points
+inline int view_limits(int V, int H, int W, long long Q = 0) {
+    const long long HW = (long long)H * W;
+    return Q > 0x7ffffffeLL || V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL ? SP_ELIMIT : 0;
+}
+// every key word 0: nothing landed
+inline hipError_t keys_clear(unsigned long long* keys, long long n_pix, hipStream_t s) {
+    return hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)n_pix, s);
+}
+// one thread per pixel
+inline dim3 pixel_grid(long long n_pix) { return dim3((unsigned)((n_pix + SP_BLOCK - 1) / SP_BLOCK)); }
+
+// ---- the resolve pass and the launch tail of every depth buffer of keys (sp_render_views, sp_render_splats, sp_render_surfels): one
+// definition here, one static copy in every file that launches it and says so by defining SP_MAP_DEVICE_RESOLVE before this header --
 #ifdef SP_MAP_DEVICE_RESOLVE
 // grid ceil(V H W / 256), block SP_BLOCK
 static __global__ __launch_bounds__(SP_BLOCK) void k_render_resolve(const unsigned long long* __restrict__ keys, const float* __restrict__ colours,
@@ -387,5 +402,21 @@ static __global__ __launch_bounds__(SP_BLOCK) void k_render_resolve(const unsign
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) image[3 * (size_t)at + ch] = rgb[ch];
     }
+}
+
+// The launch tail of a depth buffer of n_pix keys: empty keys, the caller's key pass -- key_pass() launches it -- and, if any output is
+// asked for, the resolve pass
+template <class KeyPass>
+int depth_buffer_launch(unsigned long long* keys, const float* colours, long long n_pix, int mode, uint8_t* image, float* depth, int32_t* index,
+                        hipStream_t s, KeyPass key_pass) {
+    const hipError_t e = keys_clear(keys, n_pix, s);
+    if (e != hipSuccess) return (int)e;
+    key_pass();
+    SP_CHECK_LAUNCH();
+    if (image || depth || index) {
+        hipLaunchKernelGGL(k_render_resolve, pixel_grid(n_pix), dim3(SP_BLOCK), 0, s, keys, colours, (int)n_pix, mode, image, depth, index);
+        SP_CHECK_LAUNCH();
+    }
+    return 0;
 }
 #endif

@@ -47,8 +47,6 @@ __device__ __forceinline__ void mr_cross(const double* a, const double* b, doubl
     c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-__device__ __forceinline__ bool mr_finite(double x) { return fabs(x) < HUGE_VAL; }
-
 // the range of one axis: lo = the smallest of the three pixel coordinates, hi the largest, n the image's size there
 __device__ __forceinline__ bool mr_range(double lo, double hi, int n, int& first, int& last) {
     const double a = fmax(floor(lo), 0.0), b = fmin(ceil(hi), (double)n - 1.0);     // clamped in float64, then converted
@@ -77,7 +75,7 @@ __device__ __forceinline__ bool face_setup(const float* __restrict__ vertices, i
     mr_cross(q2, q0, s.n[1]);
     mr_cross(q0, q1, s.n[2]);
     s.det = (q0[0] * s.n[0][0] + q0[1] * s.n[0][1]) + q0[2] * s.n[0][2];
-    if (s.det == 0.0 || !mr_finite(s.det)) return false;
+    if (s.det == 0.0 || !finite_d(s.det)) return false;
     if (cull && !(s.det < 0.0)) return false;
     const bool f0 = q0[2] > zmin, f1 = q1[2] > zmin, f2 = q2[2] > zmin;
     if (!f0 && !f1 && !f2) return false;                   // every point of it lies at or behind the plane
@@ -87,7 +85,7 @@ __device__ __forceinline__ bool face_setup(const float* __restrict__ vertices, i
         pixel_of(w, q0[0], q0[1], q0[2], u0, v0);
         pixel_of(w, q1[0], q1[1], q1[2], u1, v1);
         pixel_of(w, q2[0], q2[1], q2[2], u2, v2);
-        if (mr_finite(u0) && mr_finite(u1) && mr_finite(u2) && mr_finite(v0) && mr_finite(v1) && mr_finite(v2)) {
+        if (finite_d(u0) && finite_d(u1) && finite_d(u2) && finite_d(v0) && finite_d(v1) && finite_d(v2)) {
             if (!mr_range(fmin(fmin(u0, u1), u2), fmax(fmax(u0, u1), u2), W, s.c0, s.c1)) return false;
             if (!mr_range(fmin(fmin(v0, v1), v2), fmax(fmax(v0, v1), v2), H, s.r0, s.r1)) return false;
         }
@@ -291,15 +289,14 @@ int sp_mesh_render(const float* vertices, const float* vertex_colours, long long
         ((uintptr_t)face_normals & 3) || ((uintptr_t)depth & 3) || ((uintptr_t)normals & 3) || ((uintptr_t)index & 3))
         return SP_EINVAL;
     if (F < 1 || M < 1 || V < 1 || H < 1 || W < 1 || !(z_min >= 0.f) || (cull != 0 && cull != 1)) return SP_EINVAL;
-    const long long HW = (long long)H * W;
-    if (F > SP_MESH_MAX_FACES || M > SP_MESH_MAX_FACES || V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
+    if (F > SP_MESH_MAX_FACES || M > SP_MESH_MAX_FACES || view_limits(V, H, W)) return SP_ELIMIT;
     const RenderLayout l = render_layout(F);
     long long* total = static_cast<long long*>(scratch);
     long long* blocks = total + 8;
     long long* prefix = blocks + 8 * (size_t)l.block_units;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long n_pix = (long long)V * HW;
-    const hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)n_pix, s);
+    const long long HW = (long long)H * W, n_pix = (long long)V * HW;
+    const hipError_t e = keys_clear(keys, n_pix, s);
     if (e != hipSuccess) return (int)e;
     const long long tiles = (long long)((W + MR_TW - 1) / MR_TW) * ((H + MR_TH - 1) / MR_TH);      // of a whole image
 #ifdef SP_MESH_RENDER_COUNTERS
@@ -321,8 +318,8 @@ int sp_mesh_render(const float* vertices, const float* vertex_colours, long long
                            views + v0, nv, H, W, z_min, cull, prefix, blocks, (int)l.blocks_per_view, total, keys + (size_t)v0 * HW);
         SP_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_mr_resolve, dim3((unsigned)((n_pix + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, vertices, vertex_colours, (int)M,
-                       faces, face_normals, views, H, W, z_min, keys, n_pix, depth, normals, image, index);
+    hipLaunchKernelGGL(k_mr_resolve, pixel_grid(n_pix), dim3(SP_BLOCK), 0, s, vertices, vertex_colours, (int)M, faces, face_normals, views, H, W,
+                       z_min, keys, n_pix, depth, normals, image, index);
     SP_CHECK_LAUNCH();
     return 0;
 }

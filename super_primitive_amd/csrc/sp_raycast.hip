@@ -248,9 +248,7 @@ int sp_tsdf_raycast(const float* tsdf, const float* weight, const float* colour,
     if (nx < 2 || ny < 2 || nz < 2 || V < 1 || H < 1 || W < 1 || n_steps < 2) return SP_EINVAL;
     if (!(voxel > 0.f && finite_f(voxel)) || !(step > 0.f && finite_f(step)) || !(finite_f(ox) && finite_f(oy) && finite_f(oz))) return SP_EINVAL;
     if (min_weight != min_weight || !(z_start >= 0.f && finite_f(z_start))) return SP_EINVAL;
-    const long long HW = (long long)H * W;
-    if (V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL || volume_nodes(nx, ny, nz) < 0 || n_steps > SP_TSDF_RAYCAST_MAX_STEPS)
-        return SP_ELIMIT;
+    if (view_limits(V, H, W) || volume_nodes(nx, ny, nz) < 0 || n_steps > SP_TSDF_RAYCAST_MAX_STEPS) return SP_ELIMIT;
     const int tiles_x = (W + RAY_BLOCK_TILE - 1) / RAY_BLOCK_TILE, tiles_y = (H + RAY_BLOCK_TILE - 1) / RAY_BLOCK_TILE;
     const long long n_tiles = (long long)V * tiles_x * tiles_y;                        // <= V H W < 2^31
     const long long grid = SP_RAYCAST_XCD_CHUNKS ? 8 * ((n_tiles + 7) / 8) : n_tiles;

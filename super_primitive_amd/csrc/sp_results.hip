@@ -333,16 +333,14 @@ int sp_map_points(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int stri
 int sp_keyframe_depths(const SpMapKeyframe* kfs, int n_kf, int total_blocks, int H, int W, unsigned long long* keys, float* depth,
                        int32_t* seg, void* stream) {
     if (!kfs || !keys || !depth || n_kf <= 0 || n_kf > 65535 || total_blocks < 1 || H <= 0 || W <= 0) return SP_EINVAL;
-    const long long HW = (long long)H * W;
-    if (HW >= 0x80000000LL || (long long)n_kf * HW >= 0x80000000LL) return SP_ELIMIT;
+    if (view_limits(n_kf, H, W)) return SP_ELIMIT;         // (n_kf <= 65535 stands: the keyframes are the views)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long n_pix = (long long)n_kf * HW;
-    hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)n_pix, s);
+    const long long HW = (long long)H * W, n_pix = (long long)n_kf * HW;
+    hipError_t e = keys_clear(keys, n_pix, s);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_keyframe_depth_keys, dim3(total_blocks), dim3(SP_BLOCK), 0, s, kfs, n_kf, H, W, keys);
     SP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_keyframe_depth_resolve, dim3((unsigned)((n_pix + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, keys, kfs, (int)HW,
-                       (int)n_pix, depth, seg);
+    hipLaunchKernelGGL(k_keyframe_depth_resolve, pixel_grid(n_pix), dim3(SP_BLOCK), 0, s, keys, kfs, (int)HW, (int)n_pix, depth, seg);
     SP_CHECK_LAUNCH();
     return 0;
 }

@@ -348,8 +348,7 @@ int sp_tsdf_integrate(const float* depth, const float* images, const SpView* vie
     if (V <= 0 || H <= 0 || W <= 0 || nodes == 0) return SP_EINVAL;
     if (!(voxel > 0.f && finite_f(voxel)) || !(trunc > 0.f && finite_f(trunc)) || !(z_min >= 0.f) || !(depth_max > 0.f)) return SP_EINVAL;
     if (!(finite_f(ox) && finite_f(oy) && finite_f(oz))) return SP_EINVAL;
-    const long long HW = (long long)H * W;
-    if (V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL || nodes < 0) return SP_ELIMIT;
+    if (view_limits(V, H, W) || nodes < 0) return SP_ELIMIT;
     hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)((nodes + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, static_cast<hipStream_t>(stream),
                        depth, images, views, V, H, W, nx, ny, (int)nodes, voxel, ox, oy, oz, trunc, z_min, depth_max, tsdf, weight, colour);
     SP_CHECK_LAUNCH();

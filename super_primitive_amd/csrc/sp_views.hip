@@ -2,8 +2,9 @@
 // it, plus a depth-buffer mode the reference does not have) and depth images lifted into a point cloud (tool/viz.py:30-51
 // depth_image_lift, i.e. Open3D's PointCloud.create_from_depth_image with depth_scale 1, stride 1, then transform).
 //
-// sp_render_views and sp_render_splats check their own arguments and share everything after that (render_launch): the limits, the empty
-// keys, ONE key pass -- k_view_keys, a template on "a point is a pixel" / "a point is a footprint" -- and the resolve pass.
+// sp_render_views, sp_render_splats and sp_render_surfels check their own arguments and share everything after that (render_launch): the
+// limits and the launch tail of sp_map_device.h -- the empty keys, ONE key pass, and the resolve pass.  The key pass is k_view_keys, a
+// template on "a point is a pixel" / "a point is a footprint" / "a point is an oriented footprint".
 //
 // Key pass, common part: one thread per point, its three floats staged through LDS (one coalesced read of the workgroup's 3 x 256
 // floats), then a loop over the views.  Every 16 views the workgroup forms their float64 numbers once into LDS -- R^T (9), t (3), fx, fy,
@@ -20,6 +21,10 @@
 //                    finite u, v; the half-widths ru = (r fx) / z, rv = (r fy) / z in float64, not >= 0 -> 0, capped at max_px; the
 //                    thread loops over the pixels whose cell meets [u - ru, u + ru] x [v - rv, v + rv], clipped to the image (bounds
 //                    clamped in float64 before the conversion: at most 33 x 33) with the point's one "nearest" key: a splat is flat
+//     surfel         (sp_render_surfels; normals staged beside coordinates and radii, in this instantiation only) the footprint's test
+//                    and rectangle, so coverage is identical.  Per (point, view) the normal is turned into the view once and
+//                    s = n_c . p_c formed once; the row's b sits in the outer loop, the inner loop has one float64 division, one key
+//                    and one offer per pixel.  A point without a usable normal takes the footprint's flat loop
 // Resolve pass: one thread per pixel decodes the winner: index (or -1), depth = float32 z (or 0), image = trunc(c * 255) from the exact
 // float64 product, clamped to 0 .. 255, NaN -> 0 (or 0, 0, 0).  Integer maxima commute: two runs give the same bits.
 //
@@ -39,6 +44,7 @@
 // at block offset + rank: row-major order, image after image.  Point arithmetic in float64, every operation rounded on its own, rounded
 // to float32 once at the end:
 //     x = ((c - cx) d) / fx;   y = ((r - cy) d) / fy;   z = d;   world = ((T0 x + T1 y) + T2 z) + T3 per row (no pose: the point itself).
+#include <type_traits>
 #define SP_MAP_DEVICE_RESOLVE                       // this file launches k_render_resolve
 #include "sp_map_device.h"
 
@@ -46,54 +52,79 @@
 
 namespace {
 
-// the radii of a workgroup's points: LDS that only the footprint instantiation of k_view_keys has
-template <bool FOOTPRINT>
+enum KeyKind { KEY_PIXEL, KEY_FOOTPRINT, KEY_SURFEL };     // what a point is to k_view_keys
+
+// the radii and the normals of a workgroup's points: LDS that only the instantiations of k_view_keys that read them have
+template <bool HAS>
 __device__ __forceinline__ float* radius_stage() {
-    if constexpr (!FOOTPRINT) return nullptr;
+    if constexpr (!HAS) return nullptr;
     else { __shared__ float sr[SP_BLOCK]; return sr; }
 }
+template <bool HAS>
+__device__ __forceinline__ float* normal_stage() {
+    if constexpr (!HAS) return nullptr;
+    else { __shared__ float sn[3 * SP_BLOCK]; return sn; }
+}
 
-// grid ceil(Q / 256), block SP_BLOCK: the key pass of sp_render_views (FOOTPRINT = false: one pixel per kept (point, view), mode 0 or
-// 1) and of sp_render_splats (FOOTPRINT = true: mode 1 with a rectangle of pixels per kept (point, view), at most 33 x 33; `mode` is
-// not read).  `mode` comes last, after the arguments the footprint pass had before the two passes became one: its instantiation is then
-// that pass instruction for instruction, pixel loops at the same offsets.  Those short loops (load, compare, atomic) are sensitive to
-// where they fall: the same instructions 16 bytes earlier cost 2 - 4 % at large footprints (profiles/map_kernels_refactor.txt)
-template <bool FOOTPRINT>
+// k_view_keys' last argument: `mode` for the pixel and the footprint kind, what the surfel kind alone reads for that one
+struct SurfelArgs { int cull; const float* normals; };
+template <KeyKind KIND> using KeyLast = std::conditional_t<KIND == KEY_SURFEL, SurfelArgs, int>;
+
+// grid ceil(Q / 256), block SP_BLOCK: the key pass of sp_render_views (KEY_PIXEL: one pixel per kept (point, view), mode 0 or 1), of
+// sp_render_splats (KEY_FOOTPRINT: mode 1 with a rectangle of pixels per kept (point, view), at most 33 x 33; `mode` is not read) and of
+// sp_render_surfels (KEY_SURFEL: that rectangle -- the same lines, so coverage is identical --, the depth of every covered pixel taken
+// on the point's tangent plane; a point without a usable normal takes the footprint's flat loop).  `last` comes after the arguments the
+// footprint pass had before the passes became one, and is `mode` for the first two kinds: their instantiations are then those passes
+// instruction for instruction, pixel loops at the same offsets.  Those short loops (load, compare, atomic) are sensitive to where they
+// fall: the same instructions 16 bytes earlier cost 2 - 4 % at large footprints (profiles/map_kernels_refactor.txt)
+template <KeyKind KIND>
 __global__ __launch_bounds__(SP_BLOCK) void k_view_keys(const float* __restrict__ points, const float* __restrict__ radii, int Q,
                                                         const SpView* __restrict__ views, int V, int H, int W, float z_min,
-                                                        int max_px, unsigned long long* __restrict__ keys, int mode) {
+                                                        int max_px, unsigned long long* __restrict__ keys, KeyLast<KIND> last) {
     __shared__ float sp[3 * SP_BLOCK];
     __shared__ ViewD vd[VIEW_CHUNK];
-    float* sr = radius_stage<FOOTPRINT>();
+    float* sr = radius_stage<KIND != KEY_PIXEL>();
+    float* sn = normal_stage<KIND == KEY_SURFEL>();
     const int tid = threadIdx.x;
     // the workgroups take the points from the END of the set: in mode 0 the highest index wins, so the early workgroups set keys that
     // most later points lose against, and the load before the atomic skips them (ascending, every point would beat what it finds);
     // in mode 1 equal float32 z goes to the highest index
     const long long first = (long long)(gridDim.x - 1 - blockIdx.x) * SP_BLOCK;
     const int n = (int)((long long)Q - first < SP_BLOCK ? (long long)Q - first : SP_BLOCK);
-    for (int j = tid; j < 3 * n; j += SP_BLOCK) sp[j] = points[3 * first + j];
-    if (FOOTPRINT && tid < n) sr[tid] = radii[first + tid];
+    for (int j = tid; j < 3 * n; j += SP_BLOCK) {
+        sp[j] = points[3 * first + j];
+        if constexpr (KIND == KEY_SURFEL) sn[j] = last.normals[3 * first + j];
+    }
+    if (KIND != KEY_PIXEL && tid < n) sr[tid] = radii[first + tid];
     const size_t HW = (size_t)H * W;
     const double Wd = (double)W, Hd = (double)H, zmin = (double)z_min;
     const uint32_t id = (uint32_t)(first + tid);           // (Q <= 2^31 - 2)
     for (int v0 = 0; v0 < V; v0 += VIEW_CHUNK) {
         const int nv = V - v0 < VIEW_CHUNK ? V - v0 : VIEW_CHUNK;
-        __syncthreads();                                   // (sp is written; the previous chunk has been read)
+        __syncthreads();                                   // (sp, sr, sn are written; the previous chunk has been read)
         if (tid < nv) view_setup(views[v0 + tid], vd[tid]);
         __syncthreads();
         if (tid >= n) continue;
         const double px = (double)sp[3 * tid], py = (double)sp[3 * tid + 1], pz = (double)sp[3 * tid + 2];
-        const double rad = FOOTPRINT ? (double)sr[tid] : 0.0, cap = (double)max_px;       // (footprints only)
+        const double rad = KIND != KEY_PIXEL ? (double)sr[tid] : 0.0, cap = (double)max_px;       // (footprints and surfels only)
+        double n0 = 0.0, n1 = 0.0, n2 = 0.0, h = 0.0;      // (surfels only: the normal, usable or not, and the reach of the clamp)
+        bool usable = false;
+        if constexpr (KIND == KEY_SURFEL) {
+            const float nf0 = sn[3 * tid], nf1 = sn[3 * tid + 1], nf2 = sn[3 * tid + 2];
+            usable = fabsf(nf0) < HUGE_VALF && fabsf(nf1) < HUGE_VALF && fabsf(nf2) < HUGE_VALF && (nf0 != 0.f || nf1 != 0.f || nf2 != 0.f);
+            n0 = (double)nf0; n1 = (double)nf1; n2 = (double)nf2;
+            h = 2.0 * (rad >= 0.0 ? rad : 0.0);            // a disc reaching the square's corners stays within z -+ 2 rad however it is tilted
+        }
         for (int k = 0; k < nv; ++k) {
             const ViewD& w = vd[k];
             double x, y, z, u, v;
             camera_point(w, px, py, pz, x, y, z);
             pixel_of(w, x, y, z, u, v);
             unsigned long long* view_keys = keys + (size_t)(v0 + k) * HW;
-            if constexpr (!FOOTPRINT) {
+            if constexpr (KIND == KEY_PIXEL) {
                 if (!(u >= 0.0 && u < Wd && v >= 0.0 && v < Hd)) continue;
-                if (mode == 1 && !(z > zmin)) continue;
-                key_offer(view_keys + (size_t)(int)v * W + (size_t)(int)u, mode == 1 ? key_nearest((float)z, id) : key_highest_id((float)z, id));
+                if (last == 1 && !(z > zmin)) continue;
+                key_offer(view_keys + (size_t)(int)v * W + (size_t)(int)u, last == 1 ? key_nearest((float)z, id) : key_highest_id((float)z, id));
             } else {
                 if (!(z > zmin) || !(fabs(u) < HUGE_VAL) || !(fabs(v) < HUGE_VAL)) continue;
                 const double ru = half_width((rad * w.fx) / z, cap), rv = half_width((rad * w.fy) / z, cap);
@@ -102,6 +133,33 @@ __global__ __launch_bounds__(SP_BLOCK) void k_view_keys(const float* __restrict_
                 // clamped in float64, then converted: 0 <= c0 <= c1 <= W - 1 and 0 <= r0 <= r1 <= H - 1
                 const int c0 = (int)fmax(floor(ul), 0.0), c1 = (int)fmin(floor(uh), Wd - 1.0);
                 const int r0 = (int)fmax(floor(vl), 0.0), r1 = (int)fmin(floor(vh), Hd - 1.0);
+                if constexpr (KIND == KEY_SURFEL) {
+                    if (usable) {                          // a depth per pixel, on the tangent plane
+                        double nc0 = n0, nc1 = n1, nc2 = n2;                             // n_c = R^T n; an exact identity pose leaves it untouched
+                        if (!w.ident) {
+                            nc0 = (w.Rt[0] * n0 + w.Rt[1] * n1) + w.Rt[2] * n2;
+                            nc1 = (w.Rt[3] * n0 + w.Rt[4] * n1) + w.Rt[5] * n2;
+                            nc2 = (w.Rt[6] * n0 + w.Rt[7] * n1) + w.Rt[8] * n2;
+                        }
+                        const double s = (nc0 * x + nc1 * y) + nc2 * z;
+                        if (last.cull && s >= 0.0) continue;                             // the surface seen from behind
+                        const double tl = z - h, th = z + h;
+                        for (int r = r0; r <= r1; ++r) {
+                            const double b = (((double)r + 0.5) - w.cy) / w.fy;
+                            unsigned long long* row_keys = view_keys + (size_t)r * W;
+                            for (int c = c0; c <= c1; ++c) {
+                                const double a = (((double)c + 0.5) - w.cx) / w.fx;
+                                const double den = (nc0 * a + nc1 * b) + nc2;
+                                double t = s / den;
+                                if (t != t) t = z;
+                                if (t < tl) t = tl;
+                                if (t > th) t = th;
+                                if (t > zmin && t < HUGE_VAL) key_offer(row_keys + c, key_nearest((float)t, id));
+                            }
+                        }
+                        continue;
+                    }
+                }
                 const unsigned long long key = key_nearest((float)z, id);                // a splat is flat: the point's one key
                 for (int r = r0; r <= r1; ++r)
                     for (int c = c0; c <= c1; ++c) key_offer(view_keys + (size_t)r * W + c, key);
@@ -291,25 +349,23 @@ __global__ __launch_bounds__(SP_BLOCK) void k_lift_write(const float* __restrict
     pixel[row] = p;
 }
 
-// what sp_render_views (radii = NULL) and sp_render_splats launch once their own arguments are checked: the limits, empty keys, the key
-// pass and, if any output is asked for, the resolve pass
+// what sp_render_views (radii = NULL), sp_render_splats (normals = NULL) and sp_render_surfels launch once their own arguments are
+// checked: the limits, then the depth buffer's launch tail around the key pass of their kind.  The kind is told by two argument pairs:
+// (radii, max_px) is (NULL, 0) for pixels, (normals, cull) is (NULL, 0) for pixels and footprints; a pair given makes the kind
 int render_launch(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, int mode, float z_min,
-                  const float* radii, int max_px, unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream) {
-    const long long HW = (long long)H * W;
-    if (Q > 0x7ffffffeLL || V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
+                  const float* radii, int max_px, const float* normals, int cull, unsigned long long* keys, uint8_t* image, float* depth,
+                  int32_t* index, void* stream) {
+    if (view_limits(V, H, W, Q)) return SP_ELIMIT;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long n_pix = (long long)V * HW;
-    hipError_t e = hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)n_pix, s);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(radii ? k_view_keys<true> : k_view_keys<false>, dim3((unsigned)((Q + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s,
-                       points, radii, (int)Q, views, V, H, W, z_min, max_px, keys, mode);
-    SP_CHECK_LAUNCH();
-    if (image || depth || index) {
-        hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((n_pix + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK), 0, s, keys, colours,
-                           (int)n_pix, mode, image, depth, index);
-        SP_CHECK_LAUNCH();
-    }
-    return 0;
+    return depth_buffer_launch(keys, colours, (long long)V * H * W, mode, image, depth, index, s, [&] {
+        const dim3 grid((unsigned)((Q + SP_BLOCK - 1) / SP_BLOCK)), block(SP_BLOCK);
+        if (normals)
+            hipLaunchKernelGGL(k_view_keys<KEY_SURFEL>, grid, block, 0, s, points, radii, (int)Q, views, V, H, W, z_min, max_px, keys,
+                               SurfelArgs{cull, normals});
+        else
+            hipLaunchKernelGGL(radii ? k_view_keys<KEY_FOOTPRINT> : k_view_keys<KEY_PIXEL>, grid, block, 0, s, points, radii, (int)Q, views, V, H,
+                               W, z_min, max_px, keys, mode);
+    });
 }
 
 }  // namespace
@@ -320,22 +376,29 @@ int sp_render_views(const float* points, const float* colours, long long Q, cons
                     unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream) {
     if (!points || !views || !keys || (image && !colours)) return SP_EINVAL;
     if (Q <= 0 || V <= 0 || H <= 0 || W <= 0 || (mode != 0 && mode != 1) || !(z_min >= 0.f)) return SP_EINVAL;
-    return render_launch(points, colours, Q, views, V, H, W, mode, z_min, nullptr, 0, keys, image, depth, index, stream);
+    return render_launch(points, colours, Q, views, V, H, W, mode, z_min, nullptr, 0, nullptr, 0, keys, image, depth, index, stream);
 }
 
 int sp_render_splats(const float* points, const float* colours, long long Q, const SpView* views, int V, int H, int W, float z_min,
                      const float* radii, int max_px, unsigned long long* keys, uint8_t* image, float* depth, int32_t* index, void* stream) {
     if (!points || !views || !keys || !radii || (image && !colours)) return SP_EINVAL;
     if (Q <= 0 || V <= 0 || H <= 0 || W <= 0 || !(z_min >= 0.f) || max_px < 0 || max_px > 16) return SP_EINVAL;
-    return render_launch(points, colours, Q, views, V, H, W, 1, z_min, radii, max_px, keys, image, depth, index, stream);
+    return render_launch(points, colours, Q, views, V, H, W, 1, z_min, radii, max_px, nullptr, 0, keys, image, depth, index, stream);
+}
+
+int sp_render_surfels(const float* points, const float* colours, const float* normals, long long Q, const SpView* views, int V, int H, int W,
+                      float z_min, const float* radii, int max_px, int cull, unsigned long long* keys, uint8_t* image, float* depth,
+                      int32_t* index, void* stream) {
+    if (!points || !views || !keys || !radii || !normals || (image && !colours)) return SP_EINVAL;
+    if (Q <= 0 || V <= 0 || H <= 0 || W <= 0 || !(z_min >= 0.f) || max_px < 0 || max_px > 16 || (cull != 0 && cull != 1)) return SP_EINVAL;
+    return render_launch(points, colours, Q, views, V, H, W, 1, z_min, radii, max_px, normals, cull, keys, image, depth, index, stream);
 }
 
 int sp_map_consistency(const float* points, const int32_t* owner, long long Q, const SpView* views, const int32_t* view_owner, int V,
                        const float* depth, int H, int W, float tol, int window, float z_min, int32_t* counts, void* stream) {
     if (!points || !views || !depth || !counts || Q <= 0 || V <= 0 || H <= 0 || W <= 0) return SP_EINVAL;
     if (!(tol >= 0.f && tol < 1.f) || window < 0 || window > 2 || !(z_min >= 0.f)) return SP_EINVAL;
-    const long long HW = (long long)H * W;
-    if (Q > 0x7ffffffeLL || V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
+    if (view_limits(V, H, W, Q)) return SP_ELIMIT;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int chunks = (V + CONS_CHUNK - 1) / CONS_CHUNK;
     if (chunks > 1) {
@@ -356,8 +419,8 @@ int sp_map_consistency(const float* points, const int32_t* owner, long long Q, c
 
 int sp_image_metrics(const uint8_t* rendered, const float* target, const int32_t* index, int V, int H, int W, long long* out, void* stream) {
     if (!rendered || !target || !index || !out || V <= 0 || H <= 0 || W <= 0) return SP_EINVAL;
+    if (view_limits(V, H, W)) return SP_ELIMIT;
     const long long HW = (long long)H * W;
-    if (V > 65535 || HW >= 0x80000000LL || (long long)V * HW >= 0x80000000LL) return SP_ELIMIT;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(out, 0, sizeof(long long) * 3 * (size_t)V, s);
     if (e != hipSuccess) return (int)e;
@@ -370,9 +433,8 @@ int sp_image_metrics(const uint8_t* rendered, const float* target, const int32_t
 
 int sp_depth_lift_blocks(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return SP_EINVAL;
-    const long long HW = (long long)H * W;
-    if (B > 65535 || HW >= 0x80000000LL || (long long)B * HW >= 0x80000000LL) return SP_ELIMIT;
-    return (int)((long long)B * ((HW + SP_BLOCK - 1) / SP_BLOCK));
+    if (view_limits(B, H, W)) return SP_ELIMIT;
+    return (int)((long long)B * (((long long)H * W + SP_BLOCK - 1) / SP_BLOCK));
 }
 
 int sp_depth_lift(const float* depth, const float* K, const float* pose, const float* image, int B, int H, int W, float depth_trunc,

@@ -93,6 +93,33 @@ def _limits(what, V, H, W, Q=0, views="views"):
         raise ValueError(f"{what}: {f'{Q} points, ' if Q else ''}{V} {views} of {H}x{W} are beyond the kernel's limits")
 
 
+def _view_count(poses, what=None):
+    """V of ``poses`` (V,4,4), the first check of every launcher over a view set; with ``what``, V = 0 is that launcher's error (a
+    launcher that takes points reports an empty set of either in one message of its own, once it has seen the points)."""
+    if poses.dim() != 3:
+        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
+    V = int(poses.shape[0])
+    if what and V == 0:
+        raise ValueError(f"{what}: poses of no views")
+    return V
+
+
+def _view_set(Ks, poses, V, H, W):
+    """The rest of that prologue, where nothing comes between its two checks: the image size is positive, and ``Ks`` and ``poses`` make
+    V ``SpView`` records.  Returns (views, H, W)."""
+    H, W = _size(H, W)
+    return _views(Ks, poses, V), H, W
+
+
+_VIEW_IMAGES = dict(depth=((), torch.float32), normals=((3,), torch.float32), image=((3,), torch.uint8), index=((), torch.int32))
+
+
+def _view_images(V, H, W, device, **wanted):
+    """The wanted of the view images as a dict, uninitialised, in the order given: ``depth`` (V,H,W) float32, ``normals`` (V,H,W,3)
+    float32, ``image`` (V,H,W,3) uint8, ``index`` (V,H,W) int32."""
+    return {k: torch.empty(V, H, W, *_VIEW_IMAGES[k][0], dtype=_VIEW_IMAGES[k][1], device=device) for k, want in wanted.items() if want}
+
+
 def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_MIN, image=True, depth=True, index=True, radii=None,
                  max_px=8, normals=None, cull=False):
     """ONE ``sp_render_views`` launch (include/sp_hip.h has the arithmetic): ``points`` (Q,3) float32 in the world, ``colours`` (Q,3)
@@ -105,9 +132,7 @@ def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_M
     footprint; ``cull=True`` drops surfels seen from behind.  No synchronisation."""
     _on_device(points, colours, Ks, poses, radii, normals)
     H, W = _size(H, W)
-    if poses.dim() != 3:
-        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
-    V = int(poses.shape[0])
+    V = _view_count(poses)
     pts = _f32(points, (None, 3), "points")
     Q = int(pts.shape[0])
     if Q == 0 or V == 0:
@@ -133,15 +158,8 @@ def render_views(points, colours, Ks, poses, H, W, depth_buffer=False, z_min=Z_M
         raise ValueError("render_views: cull needs normals")
     _limits("render_views", V, H, W, Q)
     lib = _lib.load()
-    dev = pts.device
-    keys = torch.empty(V * H * W, dtype=torch.int64, device=dev)
-    out = {}
-    if image:
-        out['image'] = torch.empty(V, H, W, 3, dtype=torch.uint8, device=dev)
-    if depth:
-        out['depth'] = torch.empty(V, H, W, dtype=torch.float32, device=dev)
-    if index:
-        out['index'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    keys = torch.empty(V * H * W, dtype=torch.int64, device=pts.device)
+    out = _view_images(V, H, W, pts.device, image=image, depth=depth, index=index)
     if nrm is not None:
         _lib.check(lib.sp_render_surfels(_lib.ptr(pts), _lib.ptr(cols), _lib.ptr(nrm), Q, _lib.ptr(views), V, H, W, float(z_min), _lib.ptr(rad),
                                          int(max_px), 1 if cull else 0, _lib.ptr(keys), _lib.ptr(out.get('image')), _lib.ptr(out.get('depth')),
@@ -332,16 +350,13 @@ def map_consistency(points, Ks, poses, depths, owner=None, view_owner=None, tol=
     ``view_owner`` (V,) int32: a point is not tested against a view of its own owner (>= 0).  Returns (Q,3) int32 on the device: per
     point the number of views it agrees with, is in front of, is behind.  No synchronisation."""
     _on_device(points, Ks, poses, depths, owner, view_owner)
-    if poses.dim() != 3:
-        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
-    V = int(poses.shape[0])
+    V = _view_count(poses)
     pts = _f32(points, (None, 3), "points")
     Q = int(pts.shape[0])
     if Q == 0 or V == 0:
         raise ValueError(f"map_consistency: {Q} points against {V} views")
     d = _f32(depths, (V, None, None), "depths")
-    H, W = _size(d.shape[1], d.shape[2])
-    views = _views(Ks, poses, V)
+    views, H, W = _view_set(Ks, poses, V, d.shape[1], d.shape[2])
     own = None if owner is None else _i32(owner, Q, "owner")
     vown = None if view_owner is None else _i32(view_owner, V, "view_owner")
     if not 0.0 <= float(tol) < 1.0:
@@ -644,6 +659,14 @@ def _volume(volume, what):
     return tsdf, weight, colour, (nx, ny, nz), vox, org, trunc
 
 
+def _min_weight(what, min_weight, nx, ny, nz):
+    """``min_weight``, a float already, is not NaN, and the volume has a cell."""
+    if min_weight != min_weight:
+        raise ValueError(f"{what}: min_weight is NaN")
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"{what}: a volume of {nx}x{ny}x{nz} nodes has no cell (every size must be >= 2)")
+
+
 def tsdf_integrate(volume, depths, Ks, poses, images=None, z_min=Z_MIN, depth_max=float("inf")):
     """ONE ``sp_tsdf_integrate`` launch (include/sp_hip.h has the rule): ``depths`` (V,H,W) float32 fused into ``volume`` (what
     ``odometery.results.tsdf_volume`` returned) IN PLACE, view after view; ``Ks`` (V,3,3) or (3,3), ``poses`` (V,4,4) camera-to-world in the
@@ -652,14 +675,9 @@ def tsdf_integrate(volume, depths, Ks, poses, images=None, z_min=Z_MIN, depth_ma
     ``volume``.  No synchronisation."""
     tsdf, weight, colour, (nx, ny, nz), vox, org, trunc = _volume(volume, "tsdf_integrate")
     _on_device(tsdf, weight, colour, depths, Ks, poses, images)
-    if poses.dim() != 3:
-        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
-    V = int(poses.shape[0])
-    if V == 0:
-        raise ValueError("tsdf_integrate: poses of no views")
+    V = _view_count(poses, "tsdf_integrate")
     d = _f32(depths, (V, None, None), "depths")
-    H, W = _size(d.shape[1], d.shape[2])
-    views = _views(Ks, poses, V)
+    views, H, W = _view_set(Ks, poses, V, d.shape[1], d.shape[2])
     img = None
     if images is not None:
         if colour is None:
@@ -687,10 +705,7 @@ def tsdf_mesh(volume, min_weight=1.0):
         min_weight = float(min_weight)
     except (TypeError, ValueError) as e:
         raise ValueError(f"tsdf_mesh: min_weight {min_weight!r}: {e}") from None
-    if min_weight != min_weight:
-        raise ValueError("tsdf_mesh: min_weight is NaN")
-    if min(nx, ny, nz) < 2:
-        raise ValueError(f"tsdf_mesh: a volume of {nx}x{ny}x{nz} nodes has no cell (every size must be >= 2)")
+    _min_weight("tsdf_mesh", min_weight, nx, ny, nz)
     lib = _lib.load()
     dev = tsdf.device
     scratch = torch.empty(lib.sp_tsdf_mesh_scratch_bytes(nx, ny, nz) // 4, dtype=torch.int32, device=dev)
@@ -724,23 +739,15 @@ def tsdf_raycast(volume, Ks, poses, H, W, z_max, min_weight=1.0, z_min=Z_MIN, st
     one is an error.  No synchronisation."""
     tsdf, weight, colour, (nx, ny, nz), vox, org, _ = _volume(volume, "tsdf_raycast")
     _on_device(tsdf, weight, colour, Ks, poses)
-    if poses.dim() != 3:
-        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
-    V = int(poses.shape[0])
-    if V == 0:
-        raise ValueError("tsdf_raycast: poses of no views")
-    H, W = _size(H, W)
-    views = _views(Ks, poses, V)
+    V = _view_count(poses, "tsdf_raycast")
+    views, H, W = _view_set(Ks, poses, V, H, W)
     try:
         min_weight, z_min, z_max = float(min_weight), float(z_min), float(z_max)
         step = vox if step is None else float(torch.tensor(float(step), dtype=torch.float32))
     except (TypeError, ValueError) as e:
         raise ValueError(f"tsdf_raycast: min_weight {min_weight!r}, z_min {z_min!r}, z_max {z_max!r}, step {step!r}: {e}") from None
     _z_min(z_min)
-    if min_weight != min_weight:
-        raise ValueError("tsdf_raycast: min_weight is NaN")
-    if min(nx, ny, nz) < 2:
-        raise ValueError(f"tsdf_raycast: a volume of {nx}x{ny}x{nz} nodes has no cell (every size must be >= 2)")
+    _min_weight("tsdf_raycast", min_weight, nx, ny, nz)
     if not (0.0 < step < float("inf")):
         raise ValueError(f"tsdf_raycast: step {step} (finite float32 > 0)")
     if not (z_min < z_max < float("inf")):
@@ -756,16 +763,7 @@ def tsdf_raycast(volume, Ks, poses, H, W, z_max, min_weight=1.0, z_min=Z_MIN, st
         raise ValueError("tsdf_raycast: no output asked for")
     _limits("tsdf_raycast", V, H, W)
     lib = _lib.load()
-    dev = tsdf.device
-    out = {}
-    if depth:
-        out['depth'] = torch.empty(V, H, W, dtype=torch.float32, device=dev)
-    if normals:
-        out['normals'] = torch.empty(V, H, W, 3, dtype=torch.float32, device=dev)
-    if image:
-        out['image'] = torch.empty(V, H, W, 3, dtype=torch.uint8, device=dev)
-    if index:
-        out['index'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    out = _view_images(V, H, W, tsdf.device, depth=depth, normals=normals, image=image, index=index)
     _lib.check(lib.sp_tsdf_raycast(_lib.ptr(tsdf), _lib.ptr(weight), _lib.ptr(colour), nx, ny, nz, vox, org[0], org[1], org[2], min_weight,
                                    _lib.ptr(views), V, H, W, z_min, step, n_steps, _lib.ptr(out.get('depth')), _lib.ptr(out.get('normals')),
                                    _lib.ptr(out.get('image')), _lib.ptr(out.get('index')), _lib.stream_ptr()), "sp_tsdf_raycast")
@@ -871,13 +869,8 @@ def mesh_render(vertices, faces, Ks, poses, H, W, colours=None, face_normals=Non
     error.  No synchronisation."""
     v, f, M, F = _mesh(vertices, faces, "mesh_render")
     _on_device(v, f, Ks, poses, colours, face_normals)
-    if poses.dim() != 3:
-        raise ValueError(f"poses must be (V,4,4), got {tuple(poses.shape)}")
-    V = int(poses.shape[0])
-    if V == 0:
-        raise ValueError("mesh_render: poses of no views")
-    H, W = _size(H, W)
-    views = _views(Ks, poses, V)
+    V = _view_count(poses, "mesh_render")
+    views, H, W = _view_set(Ks, poses, V, H, W)
     try:
         z_min = float(z_min)
     except (TypeError, ValueError) as e:
@@ -898,15 +891,7 @@ def mesh_render(vertices, faces, Ks, poses, H, W, colours=None, face_normals=Non
     dev = v.device
     scratch = torch.empty(8 * lib.sp_mesh_render_scratch_units(F), dtype=torch.int64, device=dev)
     keys = torch.empty(V * H * W, dtype=torch.int64, device=dev)
-    out = {}
-    if depth:
-        out['depth'] = torch.empty(V, H, W, dtype=torch.float32, device=dev)
-    if normals:
-        out['normals'] = torch.empty(V, H, W, 3, dtype=torch.float32, device=dev)
-    if image:
-        out['image'] = torch.empty(V, H, W, 3, dtype=torch.uint8, device=dev)
-    if index:
-        out['index'] = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    out = _view_images(V, H, W, dev, depth=depth, normals=normals, image=image, index=index)
     _lib.check(lib.sp_mesh_render(_lib.ptr(v), _lib.ptr(cols), M, _lib.ptr(f), F, _lib.ptr(nrm), _lib.ptr(views), V, H, W, z_min, 1 if cull else 0,
                                   _lib.ptr(scratch), _lib.ptr(keys), _lib.ptr(out.get('depth')), _lib.ptr(out.get('normals')),
                                   _lib.ptr(out.get('image')), _lib.ptr(out.get('index')), _lib.stream_ptr()), "sp_mesh_render")

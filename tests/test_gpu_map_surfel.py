@@ -1,4 +1,4 @@
-"""-m gpu: map normals and oriented surfels (csrc/sp_surfel.hip: sp_map_normals, sp_render_surfels, through ``tool/viz.py`` and
+"""-m gpu: map normals and oriented surfels (csrc/sp_surfel.hip: sp_map_normals; csrc/sp_views.hip: sp_render_surfels; through ``tool/viz.py`` and
 ``odometery/results.py``) against the float64 statements of tests/map_surfel_ref.py.
 
 What is compared how.  Normals: every component within 1 float32 ulp of the statement rounded once (the statement reads the device's own

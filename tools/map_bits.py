@@ -1,12 +1,15 @@
 #!/usr/bin/env python
-"""Developer tool: one sha256 per output tensor of the map entry points (csrc/sp_views.hip, sp_results.hip, sp_fuse.hip through
-``tool/viz.py`` and ``odometery/results.py``) on the small cases the tests define.  Every output is an integer or decided by integer
-maxima, so two builds that compute the same give the same listing, line for line: run it on both and compare.
+"""Developer tool: one sha256 per output tensor of the map entry points (csrc/sp_views.hip, sp_results.hip, sp_fuse.hip, sp_tsdf.hip,
+sp_raycast.hip, sp_mesh_render.hip through ``tool/viz.py`` and ``odometery/results.py``) on the small cases the tests define.  Every
+output is an integer, decided by integer maxima, or one thread's float arithmetic in a fixed order, so two builds that compute the same
+give the same listing, line for line: run it on both (``SP_HIP_LIB`` names the library) and compare.
 
-Cases: map_render_ref posed / collide / duplicates in both modes; map_splat_ref splat_posed / splat_views17 / splat_edges;
-map_consistency_ref posed / owners / many_views / collide at windows 0, 1, 2; its keyframes through ``keyframe_depths``; the lift cases;
-map_fuse_ref's random case at every setting and at Q = 70001; ``metrics_inputs``; the scene of tests/test_gpu_map_points.py at strides
-1 and 3.  Capacity buffers are trimmed to their counts.
+Cases: map_render_ref posed / collide / duplicates in both modes; map_splat_ref splat_posed / splat_views17 / splat_edges; map_surfel_ref's
+four cases at cull 0 and 1; tsdf_ref's main case integrated into a fresh volume, and that volume ray-cast from its own three cameras;
+mesh_render_ref's mixed, skewed and strip meshes with face normals and, where the mesh has them, colours; map_consistency_ref posed /
+owners / many_views / collide at windows 0, 1, 2; its keyframes through ``keyframe_depths``; the lift cases; map_fuse_ref's random case
+at every setting and at Q = 70001; ``metrics_inputs``; the scene of tests/test_gpu_map_points.py at strides 1 and 3.  Capacity buffers
+are trimmed to their counts.
 
     python tools/map_bits.py [--out listing.txt]
 """
@@ -41,7 +44,10 @@ def main():
     import map_fuse_ref as fuse_ref
     import map_render_ref as render_ref
     import map_splat_ref as splat_ref
+    import map_surfel_ref as surfel_ref
+    import mesh_render_ref
     import test_gpu_map_points as points_test
+    import tsdf_ref
     from gpu_util import T
     from super_primitive_amd.image.keyframe import KeyFrame
     from super_primitive_amd.odometery import results
@@ -61,6 +67,26 @@ def main():
         out = viz.render_views(T(c['points']), T(c['colours']), T(c['K']), T(c.get('poses', eye)), c['H'], c['W'], depth_buffer=True,
                                radii=T(c['radii']), max_px=c['max_px'])
         put_all(f"render.{name}", out)
+    for name, make in surfel_ref.CASES.items():
+        c = make()
+        for cull in (0, 1):
+            out = viz.render_views(T(c['points']), T(c['colours']), T(c['K']), T(c.get('poses', eye)), c['H'], c['W'], depth_buffer=True,
+                                   radii=T(c['radii']), max_px=c['max_px'], normals=T(c['normals']), cull=bool(cull))
+            put_all(f"render.{name}.cull{cull}", out)
+    c = tsdf_ref.case_main()
+    nx, ny, nz = c['dims']
+    zeros = lambda *s: torch.zeros(*s, dtype=torch.float32, device="cuda")
+    vol = dict(tsdf=zeros(nz, ny, nx), weight=zeros(nz, ny, nx), colour=zeros(nz, ny, nx, 3), origin=c['origin'], voxel=c['voxel'], trunc=c['trunc'],
+               dims=c['dims'])
+    viz.tsdf_integrate(vol, T(c['depth']), T(c['Ks']), T(c['poses']), images=T(c['images']), z_min=c['z_min'], depth_max=c['depth_max'])
+    put_all("tsdf.main", vol, keys=('tsdf', 'weight', 'colour'))
+    put_all("tsdf.main.raycast", viz.tsdf_raycast(vol, T(c['Ks']), T(c['poses']), c['H'], c['W'], 3.0, z_min=0.0, step=0.125))
+    for name in ("mixed", "skewed", "strip"):
+        mesh, Ks, poses, h, w = mesh_render_ref.cases()[name]
+        rec = viz.mesh_faces(T(mesh['vertices']), T(mesh['faces']))
+        out = viz.mesh_render(T(mesh['vertices']), T(mesh['faces']), T(Ks.astype(np.float32)), T(poses.astype(np.float32)), h, w,
+                              colours=None if mesh['colours'] is None else T(mesh['colours']), face_normals=rec['normals'])
+        put_all(f"mesh_render.{name}", out)
     for name, make in cons_ref.RANDOM_CASES.items():
         c = make()
         own = lambda key: None if c.get(key) is None else T(c[key])

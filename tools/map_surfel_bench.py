@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Developer tool: time of the map normals and of the surfel render (csrc/sp_surfel.hip) on the GPU, by the protocol of
+"""Developer tool: time of the map normals and of the surfel render (csrc/sp_surfel.hip, csrc/sp_views.hip) on the GPU, by the protocol of
 tools/map_splat_bench.py: ONE call on preallocated buffers, HIP events around blocks of calls, warm-up of every shape first, then the
 median (min - max) over alternating rounds.
 
